@@ -2,7 +2,7 @@
 # -*- coding: utf-8 -*-
 """bench.py -- CAVI sweeps/s on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4]
+    python bench.py --gpus N --steps K --warmup W [--workload c4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one CAVI sweep (model.step(): E-step + M-step).  The default workload is pCMF (GaP) over the
@@ -14,11 +14,17 @@ accumulators over RCCL.  `python bench.py --gpus N` without a torch.distributed 
 from the reference generator's distribution (oriana/singlecell/generation.py:68-86) with expression probability
 z = 0.10 (~90 % zeros), is resident in HBM before the timed region starts.
 
-Prints ONE JSON line on rank 0.  `roofline` prices the kernels of the pass (timed with HIP events on their stream
-inside the timed region) against the ALGORITHMIC bytes of SURVEY.md 8(d).  `cpu_baseline` times the CPU oracle --
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K sweeps (nothing else in the timed region),
+writes the outputs of the last timed sweep if --dump-outputs is given, and prints the headline: `value` (sweeps/s),
+`ms_per_step`, the workload's `config` and `check`.
+
+--full adds everything beside the headline.  `roofline` prices the kernels of the pass (timed with HIP events on their
+stream inside the timed region) against the ALGORITHMIC bytes of SURVEY.md 8(d).  `cpu_baseline` times the CPU oracle --
 one full sweep of the restated reference (oracle/: the C loop nest, 1 thread like the reference's un-parallel
 numba kernel, plus the NumPy updates) on a bounded row sample of the same matrix (rank 0, N = 1 only) -- and an
-OpenMP all-cores variant of the loop nest, labelled as not the reference's behaviour.
+OpenMP all-cores variant of the loop nest, labelled as not the reference's behaviour.  Also the parity slab, the C-ABI
+binding timings, the float64 leg of the ZI models, graph replay at launch-bound sizes, the per-rank and exchange figures
+of a multi-GPU run and, for the default workload, the secondary workloads (configs[2], configs[4], the NMF start).
 """
 import argparse
 import json
@@ -37,6 +43,12 @@ HBM_PEAK_GBS = 8000.0      # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s sp
 VALU_PEAK_TFLOPS = 157.3   # FP32 vector peak (same guide); v_pk_fma_f32 measured: 131 TFLOP/s (tools/ubench/fma_rate.hip)
 LDS_PEAK_GBS = 256 * 256 * 2.4   # 256 CUs x 256 B/clk (ds_read_b128, same guide) x 2.4 GHz = 157 TB/s
 MATRIX_BF16_PEAK_TFLOPS = 2500.0   # dense bf16 matrix peak (same guide: ~2.5 PFLOP/s; never the 2:1-sparsity headline)
+
+# --dump-outputs: at most this many bytes in all; cell-side (n, K) and gene-side (m, K) arrays are written for a fixed, seeded
+# sample of DUMP_ROWS cells / genes (all of them when there are fewer), the (n, m) D_hat for every 4th sampled cell and gene
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS = 4096
+DUMP_SEED = 0
 
 WORKLOADS = {
     # name: (model, n_total, m, K, zero_inflation_level, BASELINE.json config)
@@ -71,6 +83,12 @@ def parse():
     ap.add_argument('--dense-density', default=os.environ.get('ORIANA_DENSE_DENSITY', 'auto'),
                     help="pCMF: genes expressed in at least this share of the cells are evaluated on the bf16 matrix cores "
                          "(hybrid layout); 'auto' = the engine's default, 0 = sliced layout only")
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beside the headline too: per-kernel roofline, CPU baseline, parity slab, binding '
+                         'timings, the secondary workloads and the multi-GPU exchange figures (off: the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed sweep computed as DIR/<name>.npy (model parameters; fixed, seeded '
+                         'cell / gene samples of the large ones; %d MB at most)' % (DUMP_MAX_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -200,7 +218,7 @@ def main():
         sys.stdout.flush()
         os.dup2(2, 1)
     out = measure(args, args.workload, args.steps, args.warmup, world, rank, dev, np, torch, dist,
-                  cpu_rows=(None if args.no_cpu else args.cpu_rows), brief=args.brief)
+                  cpu_rows=(None if args.no_cpu or not args.full else args.cpu_rows), brief=args.brief)
     if world > 1 or force_pg:
         dist.barrier()
         dist.destroy_process_group()
@@ -211,8 +229,8 @@ def main():
         # (sparse pCMF), a short run each after the headline measurement, with their own roofline objects and parity slabs.
         # [r5] Each runs in a FRESH CHILD PROCESS under a wall-clock budget: a fault, an abort or a hang there cannot cost
         # the headline, which is also written to gpurun_out/bench_headline.json before they start.  ORIANA_BENCH_SECONDARY=0
-        # skips them; ORIANA_BENCH_SECONDARY_BUDGET_S (default 420) bounds their total time.
-        if (world == 1 and args.workload == 'c4' and not args.no_cpu and not args.brief
+        # skips them; ORIANA_BENCH_SECONDARY_BUDGET_S (default 420) bounds their total time.  Only with --full.
+        if (args.full and world == 1 and args.workload == 'c4' and not args.no_cpu and not args.brief
                 and os.environ.get('ORIANA_BENCH_SECONDARY', '1') != '0'):
             try:
                 os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
@@ -241,7 +259,7 @@ def run_secondaries(names):
         for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'ORIANA_BENCH_FORCE_PG', 'ORIANA_FORCE_SHARDED'):
             env.pop(k, None)
         cmd = [sys.executable, os.path.abspath(__file__), '--workload', wl, '--steps', '26' if wl.endswith('_nmf') else '10',
-               '--warmup', '0' if wl.endswith('_nmf') else '3', '--cpu-rows', '400', '--brief']
+               '--warmup', '0' if wl.endswith('_nmf') else '3', '--cpu-rows', '400', '--brief', '--full']
         try:
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=left)
             lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -320,19 +338,21 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
 
     for _ in range(args.warmup):
         model.step()
-    timer = engine.KernelTimer(prealloc=8 * args.steps)
-    # The passes are timed with HIP events on the stream they run on, inside the timed region.  An event costs ~4.5 us
-    # of stream time: nothing against a 50 ms sweep, a third of a 0.11 ms one -- launch-bound sizes (below 2e8 entries)
-    # time the passes of every 4th sweep and take the per-sweep median from the same sweeps.
+    full = args.full
+    # --full: the passes are timed with HIP events on the stream they run on, inside the timed region.  An event costs
+    # ~4.5 us of stream time: nothing against a 50 ms sweep, a third of a 0.11 ms one -- launch-bound sizes (below 2e8
+    # entries) time the passes of every 4th sweep and take the per-sweep median from the same sweeps.  A plain run times
+    # the bare sweeps.
     stride = 1 if float(n_total) * m >= 2e8 else 4
-    sampled = [i for i in range(args.steps) if i % stride == 0]
+    sampled = [i for i in range(args.steps) if i % stride == 0] if full else []
+    timer = engine.KernelTimer(prealloc=8 * len(sampled))
     marks = {i: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for i in sampled}
-    if world > 1 or odist.sharded():
+    if full and (world > 1 or odist.sharded()):
         model._xch.timing = True         # events around every blocking exchange: allreduce_exposed_ms
     # (NMF-start workload: slow-path tiles of every sweep, summed on the device into one slot per sweep and read AFTER the timed
     #  region -- a host read per sweep would put a device-to-host round trip into every step of `value`)
     ntiles = counts.nrb * counts.ncb
-    flagged_dev = torch.zeros(max(args.steps, 1), dtype=torch.int64, device=dev) if nmf_start else None
+    flagged_dev = torch.zeros(max(args.steps, 1), dtype=torch.int64, device=dev) if nmf_start and full else None
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -344,13 +364,13 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
             model._ws.timer = None
         else:
             model.step()
-        if nmf_start:
+        if flagged_dev is not None:
             flagged_dev[i].copy_(model._ws.tile_flag[:max(ntiles, 1)].sum())
     barrier()
     elapsed = time.perf_counter() - t0
     model._ws.timer = None
-    flagged = [int(v) for v in flagged_dev.tolist()] if nmf_start else []
-    exposed_ms = model._xch.exposed_ms() if (world > 1 or odist.sharded()) else None
+    flagged = [int(v) for v in flagged_dev.tolist()] if flagged_dev is not None else []
+    exposed_ms = model._xch.exposed_ms() if full and (world > 1 or odist.sharded()) else None
     model._xch.timing = False
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -360,6 +380,38 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
     # collectives of one sweep's exchange (counted over the sweeps run so far: warm-up + timed)
     coll_per_sweep = round(model._xch.n_collectives / max(model._xch.n_reduces, 1))
     value = args.steps / elapsed
+    hbm_gb = torch.cuda.max_memory_allocated() / 1e9
+    # the state the last timed sweep left, before anything below runs another sweep (rank 0: its rows, and the gene side)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, np, torch)
+    check = float(model.alpha1.tensor.sum().item() + model.beta1.tensor.sum().item())
+    nnz_total = odist.sum_int(counts.nnz, None if world == 1 else dist.group.WORLD, dev)
+    out = None
+    if rank == 0:
+        out = {
+            'metric': 'CAVI sweeps/sec (%s, %s x %s, K=%d)' % (MODEL_LABEL[mname], fmt_dim(n_total), fmt_dim(m), K),
+            'value': value, 'unit': 'sweeps/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
+            'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32',
+            'data': 'synthetic',
+            'config': {'workload': '%s (%s): %s (%s) CAVI sweep, %d cells x %d genes, K=%d, z=%.2f (%.1f%% zeros), '
+                                   'cells row-sharded over %d GPU(s)' % (args.workload, cfg_label, MODEL_LABEL[mname], mname,
+                                                                         n_total, m, K, z,
+                                                                         100.0 * (1.0 - nnz_total / (float(n_total) * m)), world),
+                       'n_cells': n_total, 'n_genes': m, 'K': K, 'nnz': nnz_total, 'rows_per_rank': n,
+                       'parallelism': 'rows/%d' % world, 'setup_s': round(t_setup, 1),
+                       'hbm_gb_rank0': round(hbm_gb, 1),
+                       'collectives_per_sweep': (coll_per_sweep + (1 if model.zi else 0)) if (world > 1 or odist.sharded()) else 0,
+                       'layout': ('hybrid: %d genes (expressed in >= %.0f%% of the cells, %.1f%% of the non-zeros) as a dense block on the '
+                                  'bf16 matrix cores (float32-equivalent: exact three-way splits, six cross products), %d genes sliced'
+                                  % (counts.gd, 100.0 * counts.dense_density, 100.0 * counts.dense.nnz / max(counts.nnz, 1), counts.ms))
+                                 if counts.gd else 'sliced non-zero layout'},
+            'check': check,
+        }
+    if not full:
+        del model, counts, gen, timer
+        torch.cuda.empty_cache()
+        return out
     sweep_ms = [marks[i][0].elapsed_time(marks[i][1]) for i in sorted(marks)]
     step_ms = sorted(sweep_ms)
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
@@ -368,7 +420,6 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
     pass_names = ['row_pass', 'dense_images', 'dense_row', 'fixup', 'row_spmm', 'col_pass', 'dense_col', 'col_pass_log', 'DV', 'DtU',
                   'D_update']
     pass_ms = sum(ks.get(k, 0.0) for k in pass_names)
-    nnz_total = odist.sum_int(counts.nnz, None if world == 1 else dist.group.WORLD, dev)
     alg_bytes = algorithmic_bytes(mname, n, m, K)
     Kp = engine.kpad(K)
     # bytes the responsibility kernels are designed to move (tiled non-zero layout): 8 B record + 4 B s (write) in
@@ -379,7 +430,6 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
     resp_ms = sum(ks.get(k, 0.0) for k in ('row_pass', 'fixup', 'col_pass'))
     useful_tflops = 6.0 * counts.nnz_sparse * K / (resp_ms * 1e-3) / 1e12 if resp_ms > 0 else 0.0
     useful_lds_gbs = 8.0 * counts.nnz_sparse * K / (resp_ms * 1e-3) / 1e9 if resp_ms > 0 else 0.0
-    check = float(model.alpha1.tensor.sum().item() + model.beta1.tensor.sum().item())
     # SURVEY 8(d)'s second regime (z = 0.5, the reference generator's default: ~53 % zeros): the pass is no longer priced by the
     # bytes of X but by its arithmetic -- the sliced non-zeros on the vector ALUs, the dense block on the bf16 matrix cores (six
     # cross products of three-way splits per float32 product: 36 K bf16 flops per dense entry for den, R and C)
@@ -434,25 +484,9 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
     if rank == 0:
         traffic, traffic_src = recorded_traffic(args.workload, world, counts.gd > 0)
         frac_step = alg_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS if ms_per_step > 0 else 0.0
-        out = {
-            'metric': 'CAVI sweeps/sec (%s, %s x %s, K=%d)' % (MODEL_LABEL[mname], fmt_dim(n_total), fmt_dim(m), K),
-            'value': value, 'unit': 'sweeps/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
-            'ms_per_step_median': median_ms,
-            'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32',
-            'data': 'synthetic',
-            'config': {'workload': '%s (%s): %s (%s) CAVI sweep, %d cells x %d genes, K=%d, z=%.2f (%.1f%% zeros), '
-                                   'cells row-sharded over %d GPU(s)' % (args.workload, cfg_label, MODEL_LABEL[mname], mname,
-                                                                         n_total, m, K, z,
-                                                                         100.0 * (1.0 - nnz_total / (float(n_total) * m)), world),
-                       'n_cells': n_total, 'n_genes': m, 'K': K, 'nnz': nnz_total, 'rows_per_rank': n,
-                       'parallelism': 'rows/%d' % world, 'setup_s': round(t_setup, 1),
-                       'hbm_gb_rank0': round(torch.cuda.max_memory_allocated() / 1e9, 1),
-                       'collectives_per_sweep': (coll_per_sweep + (1 if model.zi else 0)) if (world > 1 or odist.sharded()) else 0,
-                       'layout': ('hybrid: %d genes (expressed in >= %.0f%% of the cells, %.1f%% of the non-zeros) as a dense block on the '
-                                  'bf16 matrix cores (float32-equivalent: exact three-way splits, six cross products), %d genes sliced'
-                                  % (counts.gd, 100.0 * counts.dense_density, 100.0 * counts.dense.nnz / max(counts.nnz, 1), counts.ms))
-                                 if counts.gd else 'sliced non-zero layout'},
+        out['ms_per_step_median'] = median_ms
+        out['config']['hbm_gb_rank0'] = round(torch.cuda.max_memory_allocated() / 1e9, 1)     # (with the legs above)
+        out.update({
             'roofline': {'bound': 'valu+matrix' if compute_bound else 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': achieved / HBM_PEAK_GBS,
                          # the same algorithmic bytes over the WHOLE sweep's wall time (updates, launches and gaps included)
@@ -488,8 +522,7 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
             'cpu_baseline': cpu,
             'parity_slab': slab,
             'f64_reference_arithmetic_ms': f64_ms,
-            'check': check,
-        }
+        })
         # launch-bound sizes: the same sweep replayed from a captured hipGraph (after, and outside, the timed region; the
         # headline `value` stays the eager figure).  Informative only: at configs[1] a sweep is ~30 launches of a few
         # microseconds of work each.
@@ -559,6 +592,51 @@ def measure(args, workload, steps, warmup, world, rank, dev, np, torch, dist, cp
     del model, counts, gen, timer
     torch.cuda.empty_cache()
     return out
+
+
+def dump_sample(n, np):
+    """Sorted indices of the DUMP_ROWS rows of an n-row array that --dump-outputs writes (all rows when n is smaller)."""
+    if n <= DUMP_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+
+
+def dump_outputs(path, model, np, torch):
+    """The model's state as the last sweep left it -- what model.state() / factors() hand a caller, under the reference's
+    attribute names -- as path/<name>.npy in the dtype the model holds (float64 parameters, float32 log-expectations,
+    D_hat and S_hat).  Cell- and gene-side arrays are sampled (dump_sample); p_d is not materialised (that would change
+    the next sweep's path), its float32 image D_hat is written instead."""
+    dev = model.alpha1.tensor.device
+    cells = torch.from_numpy(dump_sample(model.n, np)).to(dev)
+    genes = torch.from_numpy(dump_sample(model.m, np)).to(dev)
+    arrays = {}
+    for name in ('alpha1', 'alpha2', 'beta1', 'beta2', 'pi_d', 'pi_s'):
+        if hasattr(model, name):
+            arrays[name] = getattr(model, name).tensor
+    for name in ('a1', 'a2'):
+        arrays[name] = getattr(model, name).tensor[cells]
+    arrays['U_hat'] = model._U_hat[cells]
+    arrays['log_U_hat'] = model._log_U_hat[cells]
+    for name in ('b1', 'b2') + (('p_s',) if hasattr(model, 'p_s') else ()):
+        arrays[name] = getattr(model, name).tensor[genes]
+    arrays['V_hat'] = model._V_hat[genes]
+    arrays['log_V_hat'] = model._log_V_hat[genes]
+    if hasattr(model, '_S_hat'):
+        arrays['S_hat'] = model._S_hat[genes]
+    if hasattr(model, '_D_hat'):
+        arrays['D_hat'] = model._D_hat[cells[::4]][:, genes[::4]]
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
 
 
 def fmt_dim(v):

@@ -249,3 +249,43 @@ def test_bench_secondaries_cannot_cost_the_headline(monkeypatch):
     monkeypatch.setenv('ORIANA_BENCH_SECONDARY_BUDGET_S', '5')
     res = bench.run_secondaries(('c3_zi', 'c5_sparse'))
     assert [r['workload'] for r in res] == ['c3_zi', 'c5_sparse'] and all('skipped' in r['error'] for r in res)
+
+
+def test_bench_dump_outputs_samples_and_bounds(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on a stand-in ZI model (host tensors): the large arrays are written for the same seeded cell /
+    gene sample on every run, in the model's float32 / float64, and a dump above the byte limit is refused before anything
+    is written."""
+    import importlib.util
+    import types
+    import torch
+    from oriana_amd.parameters import Parameter
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, m, K = 9000, 5000, 20
+    g = torch.Generator().manual_seed(0)
+    f64 = dict(dtype=torch.float64)
+    model = types.SimpleNamespace(n=n, m=m, _U_hat=torch.rand(n, K, generator=g, **f64), _log_U_hat=torch.rand(n, K, generator=g),
+                                  _V_hat=torch.rand(m, K, generator=g, **f64), _log_V_hat=torch.rand(m, K, generator=g),
+                                  _D_hat=torch.rand(n, m, generator=g))
+    for name, shape in (('alpha1', (K,)), ('alpha2', (K,)), ('beta1', (K,)), ('beta2', (K,)), ('pi_d', (m,)), ('a1', (n, K)),
+                        ('a2', (n, K)), ('b1', (m, K)), ('b2', (m, K))):
+        setattr(model, name, Parameter(torch.rand(*shape, generator=g, **f64), device='cpu'))
+    bench.dump_outputs(str(tmp_path / 'd'), model, np, torch)
+    got = {f[:-4]: np.load(str(tmp_path / 'd' / f)) for f in os.listdir(str(tmp_path / 'd'))}
+    assert set(got) == {'alpha1', 'alpha2', 'beta1', 'beta2', 'pi_d', 'a1', 'a2', 'U_hat', 'log_U_hat', 'b1', 'b2', 'V_hat',
+                        'log_V_hat', 'D_hat'}
+    cells, genes = bench.dump_sample(n, np), bench.dump_sample(m, np)
+    assert len(cells) == bench.DUMP_ROWS and len(np.unique(cells)) == len(cells) and (cells == bench.dump_sample(n, np)).all()
+    assert len(genes) == bench.DUMP_ROWS and (bench.dump_sample(100, np) == np.arange(100)).all()
+    np.testing.assert_array_equal(got['a1'], model.a1.tensor.numpy()[cells])
+    np.testing.assert_array_equal(got['log_V_hat'], model._log_V_hat.numpy()[genes])
+    np.testing.assert_array_equal(got['D_hat'], model._D_hat.numpy()[cells[::4]][:, genes[::4]])
+    np.testing.assert_array_equal(got['pi_d'], model.pi_d.tensor.numpy())
+    assert got['log_U_hat'].dtype == np.float32 and got['U_hat'].dtype == np.float64
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 1 << 20)
+    with pytest.raises(RuntimeError, match='limit'):
+        bench.dump_outputs(str(tmp_path / 'e'), model, np, torch)
+    assert not os.path.exists(str(tmp_path / 'e'))

@@ -282,7 +282,7 @@ def test_bench_self_launch_two_ranks():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--workload', 'c4_eighth'], env=env, capture_output=True, text=True, timeout=900)
+                        '--workload', 'c4_eighth', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -308,7 +308,7 @@ def test_bench_under_torch_distributed_run():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-           '--workload', 'c2']
+           '--workload', 'c2', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -332,7 +332,7 @@ def test_rccl_single_rank_rehearsal():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'ORIANA_FORCE_SHARDED', 'ORIANA_BENCH_FORCE_PG'):
         base.pop(k, None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--workload', 'c2',
-           '--no-cpu']
+           '--no-cpu', '--full']
     out = {}
     for tag, extra in (('plain', {}), ('rccl', {'ORIANA_BENCH_FORCE_PG': '1', 'MASTER_PORT': str(_free_port())})):
         r = subprocess.run(cmd, env=dict(base, **extra), capture_output=True, text=True, timeout=600)
@@ -350,3 +350,43 @@ def test_rccl_single_rank_rehearsal():
     assert d['config']['collectives_per_sweep'] == 2
     assert 'exchange_rehearsal' not in out['plain']
     assert abs(d['check'] / out['plain']['check'] - 1.0) < 1e-6
+
+
+@pytest.mark.parametrize('workload', ['c2', 'c3_zi'])
+def test_bench_plain_line_and_dumped_outputs(tmp_path, workload):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` without --full: one JSON line with the headline alone
+    (N timed sweeps, ms_per_step), and the state of the last timed sweep as DIR/<name>.npy in float32 / float64, 64 MB at
+    most.  The inputs are seeded: two runs write the same outputs (up to the order of the float atomics)."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'ORIANA_FORCE_SHARDED', 'ORIANA_BENCH_FORCE_PG'):
+        env.pop(k, None)
+    runs = []
+    for r in range(2):
+        d = str(tmp_path / ('run%d' % r))
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', workload,
+               '--dump-outputs', d]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1 and p.stdout.strip().splitlines()[-1] == lines[0], p.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['unit'] == 'sweeps/s' and line['higher_is_better'] is True
+        assert line['dtype'] == 'f32' and line['ms_per_step'] > 0 and abs(line['value'] * line['ms_per_step'] - 1e3) < 1e-6 * 1e3
+        for k in ('roofline', 'cpu_baseline', 'parity_slab', 'secondary_workloads', 'ms_per_step_median'):
+            assert k not in line, k
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(f.endswith('.npy') for f in files)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        runs.append((line, arrays))
+    (l0, a0), (l1, a1) = runs
+    assert {'a1', 'a2', 'b1', 'b2', 'U_hat', 'V_hat', 'alpha1', 'beta1'} <= set(a0) and set(a0) == set(a1)
+    if workload == 'c3_zi':
+        assert {'pi_d', 'D_hat'} <= set(a0)
+    assert abs(l0['check'] / l1['check'] - 1.0) < 1e-6
+    for k in a0:
+        np.testing.assert_allclose(a1[k], a0[k], rtol=1e-5, atol=1e-5 * float(np.abs(a0[k]).max()), err_msg=k)

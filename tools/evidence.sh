@@ -15,17 +15,17 @@ mkdir -p $O
 export TMPDIR=/tmp
 echo "tools/evidence.sh $RND" > $O/command.txt
 timeout 2700 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-timeout 1800 python3 bench.py --steps 20 --warmup 5 > $O/bench_c4.json 2> $O/bench_c4.err
-timeout 900 python3 bench.py --steps 20 --warmup 5 --no-cpu --dense-density 0 > $O/bench_c4_sliced.json 2>/dev/null
+timeout 1800 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 900 python3 bench.py --full --steps 20 --warmup 5 --no-cpu --dense-density 0 > $O/bench_c4_sliced.json 2>/dev/null
 for w in c4_half c4_quarter c4_eighth; do
-  ORIANA_BENCH_FORCE_PG=1 timeout 900 python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu > $O/bench_$w.json 2> $O/bench_$w.err
+  ORIANA_BENCH_FORCE_PG=1 timeout 900 python3 bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu > $O/bench_$w.json 2> $O/bench_$w.err
 done
 python3 tools/scaling_projection.py $O/bench_c4.json $O/bench_c4_half.json $O/bench_c4_quarter.json $O/bench_c4_eighth.json $O/scaling_projection.json > $O/scaling_projection.md
 cat $O/scaling_projection.md
 for w in c2 c3_zi c5_sparse c4_eighth_z05 c3_zi_z05 c5_sparse_z05; do
-  timeout 900 python3 bench.py --workload $w --steps 20 --warmup 5 > $O/bench_$w.json 2> $O/bench_$w.err
+  timeout 900 python3 bench.py --full --workload $w --steps 20 --warmup 5 > $O/bench_$w.json 2> $O/bench_$w.err
 done
-timeout 900 python3 bench.py --workload c3_zi_nmf --steps 26 --warmup 0 --cpu-rows 400 > $O/bench_c3_zi_nmf.json 2> $O/bench_c3_zi_nmf.err
+timeout 900 python3 bench.py --full --workload c3_zi_nmf --steps 26 --warmup 0 --cpu-rows 400 > $O/bench_c3_zi_nmf.json 2> $O/bench_c3_zi_nmf.err
 INIT=nmf SWEEPS=40 timeout 600 python3 tools/zi_slow_path_trace.py > $O/zi_trace_nmf.txt 2>&1
 timeout 300 python3 tools/perf_zi_dense.py 100000 20000 50 > $O/perf_zi_dense_k50.txt 2>&1
 timeout 300 python3 tools/perf_zi_dense.py 100000 20000 100 > $O/perf_zi_dense_k100.txt 2>&1

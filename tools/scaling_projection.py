@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """A PROJECTED 1 / 2 / 4 / 8-GPU table for the headline configuration (1M x 30k, K = 100) from ONE-GPU measurements of the
-shares a rank would own (bench.py --workload c4 | c4_half | c4_quarter | c4_eighth).  No multi-GPU node has been available in
+shares a rank would own (bench.py --full --workload c4 | c4_half | c4_quarter | c4_eighth).  No multi-GPU node has been available in
 any round: every figure below the one-GPU rows is a projection, labelled as such, never a measurement.
 
     python tools/scaling_projection.py c4.json c4_half.json c4_quarter.json c4_eighth.json [out.json]
