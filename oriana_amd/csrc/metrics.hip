@@ -41,12 +41,12 @@ __device__ __forceinline__ double block_sum(double v, double *sh) {
 // out[0] += sum (x log x - x), out[1] += sum x^2, over the stored entries.  One work-group per tile.
 __global__ __launch_bounds__(256) void k_count_stats(oriana_counts cm, double *__restrict__ colsum,
                                                      double *__restrict__ colnnz, double *__restrict__ out) {
-    __shared__ float cs[TILE];
+    __shared__ double cs[TILE];
     __shared__ int cn[TILE];
     __shared__ double sh[4];
     const int64_t t = blockIdx.x;
     const int64_t cb = t % cm.ncb;
-    cs[threadIdx.x] = 0.f;
+    cs[threadIdx.x] = 0.0;
     cn[threadIdx.x] = 0;
     __syncthreads();
     const int64_t rbase = cm.roff[t];
@@ -58,14 +58,16 @@ __global__ __launch_bounds__(256) void k_count_stats(oriana_counts cm, double *_
         const double x = (double)rec.x;
         a0 += x * log(x) - x;
         a1 += x * x;
-        atomicAdd(&cs[rec.col], rec.x);          // <= 256 counts below 2^24 per column: exact in f32
+        // (float64: a column's sum over one tile's 256 rows leaves float32's exact range once counts reach ~2^16 --
+        //  17 counts of 10^6 already round -- and counts of 65535 and above always live in this sliced layout)
+        atomicAdd(&cs[rec.col], x);
         atomicAdd(&cn[rec.col], 1);
     }
     __syncthreads();
     const int64_t jp = cb * TILE + threadIdx.x;
     if (jp < cm.m && cn[threadIdx.x] != 0) {
         const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
-        atomicAdd(&colsum[j], (double)cs[threadIdx.x]);
+        atomicAdd(&colsum[j], cs[threadIdx.x]);
         atomicAdd(&colnnz[j], (double)cn[threadIdx.x]);
     }
     a0 = block_sum(a0, sh);

@@ -508,7 +508,10 @@ class FactorModel:
         ll_uv = zz[0] + nnz_lpi - nz[0] + nz[1]
         ntot = float(self.n_total)
         mu = colsum / ntot
-        zero_term = (ntot - colnnz) * torch.log(pi * torch.exp(-mu) + (1.0 - pi))
+        # log(pi e^-mu + 1 - pi) as a log-sum-exp.  Without a dropout node (pi = 1) the literal form is log e^-mu, which
+        # underflows to log 0 = -inf once mu passes ~745: -inf for such a gene with a zero among its counts, 0 * -inf = NaN
+        # for one without, and explained_deviance NaN either way.  (With pi <= 1 - 1e-10 the 1 - pi keeps it finite.)
+        zero_term = (ntot - colnnz) * torch.logaddexp(lpi - mu, torch.log1p(-pi))
         nz_term = torch.where(has, colnnz * (lpi - mu) + colsum * torch.log(torch.where(has, mu, torch.ones_like(mu))),
                               torch.zeros_like(mu))
         ll_mean = (zero_term + nz_term).sum()

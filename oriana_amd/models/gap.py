@@ -91,6 +91,13 @@ class GaP(FactorModel):
         self.a2.defer(lambda: row.clone().expand(n, K).contiguous())
         self._u_stale = True
 
+    def load_state(self, st):
+        # U_hat is formed from the a1 / a2 it belongs to BEFORE a loaded a1 replaces them: load_state recomputes nothing, so
+        # keys that are not loaded keep their values, as in the storing form.  The loaded a2, if any, is then the
+        # materialised parameter; _a2_row is only read while U_hat is stale, which the next sweep's kernel decides anew.
+        self._U_hat
+        FactorModel.load_state(self, st)
+
     def step(self):
         FactorModel.step(self)
         if self._graph is not None and self._a2_row is not None and self._lazy_ok:
