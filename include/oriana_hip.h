@@ -181,21 +181,11 @@ int oriana_row_pass(const oriana_counts *cm,
 /* The plain row pass (w_nz = NULL, no row-side copy of s) with the gene tiles of every row block split over
  * `gene_splits` work-groups: a row block is one work-group, so a matrix of 10,000 cells (configs[1]) ran the pass on 40
  * of the 256 CUs.  R is then (gene_splits, n, Kp): every group stores the row sums of its gene range in its own slab
- * (no atomics, nothing to clear); oriana_finalize_slabs / oriana_gamma_update_finalize add the slabs up.
- * oriana_row_pass_gene_splits: the split that fills the chip for a SHORT matrix (below 256 row-side work-groups; 1 from
- * there on).  [r4] Long matrices: see oriana_row_pass_plan below, which splits the row blocks of the last round only. */
-int64_t oriana_row_pass_gene_splits(const oriana_counts *cm, int64_t K);
+ * (no atomics, nothing to clear); oriana_finalize_slabs / oriana_gamma_update_finalize add the slabs up.  The split that
+ * fills the chip: oriana_row_pass_plan below (a short matrix: every row block; a long one: the row blocks of the last round).
+ * Forwards to oriana_row_pass_general (as oriana_row_pass does: the arguments are validated there). */
 int oriana_row_pass_split(const oriana_counts *cm, const float *FU, const float *FV, float *R, float *s_cs,
                           int32_t *tile_flag, int64_t K, int64_t gene_splits, void *stream);
-
-/* The row pass of the sparse models with the S_hat-weighted sums folded in (sparse_gap.py:88-95): the dot product
- * runs against FV (= exp-shifted E[log V] masked by S_tilde), the accumulation against FV2 (= FV * S_hat), both staged
- * side by side in LDS -- R[i,:] = sum_j w_ij s_ij FV2[j,:] comes out of this pass and oriana_row_spmm is not needed.
- * Returns ORIANA_EKRANGE when the two images of 256 factor rows do not fit (Kp > 64): use oriana_row_pass (with s_rs)
- * followed by oriana_row_spmm then. */
-int oriana_row_pass_masked(const oriana_counts *cm, const float *FU, const float *FV, const float *FV2,
-                           const float *w_nz, float *R, float *s_cs, float *sw_cs, int32_t *tile_flag, int64_t K,
-                           void *stream);
 
 /* [r4] Which work-groups of the row pass share a row block.  The two-lane kernels (33 <= Kp <= 64, 85 <= K <= 100) run one
  * 512-thread group per CU, so the pass advances in ROUNDS of 256 row blocks and the last, partly filled round costs a whole
@@ -210,7 +200,7 @@ typedef struct oriana_row_split {
     int32_t edge[9];        /* edge[0] = 0 <= ... <= edge[parts] = ncb */
 } oriana_row_split;
 
-/* The split that fills the chip for this matrix and K (what oriana_row_pass_gene_splits decided alone in round 3).
+/* The split that fills the chip for this matrix and K.
  * tile_cost: HOST array of ncb relative costs of the gene tiles (the ranges are cut at equal-cost points; genes are packed
  * by decreasing density, so equal tile counts are not equal work) or NULL = equal.  ORIANA_ROW_SPLIT_ROUNDS=off: only the
  * short-matrix rule. */
@@ -223,8 +213,11 @@ int oriana_row_pass_plan_cus(const oriana_counts *cm, int64_t K, const double *t
  * the environment's ORIANA_CUS overrides; 256 where no device is visible): the "rounds of the chip" every plan counts in. */
 int64_t oriana_device_cus(void);
 
-/* [r4] Every variant of the row pass behind one entry: oriana_row_pass (FV2 = NULL) or oriana_row_pass_masked (FV2 given,
- * s_rs must be NULL; ORIANA_EKRANGE where the two images do not fit) under a split (NULL = none); s_rs given: R untouched.
+/* [r4] Every variant of the row pass behind one entry, under a split (NULL = none); s_rs given: R untouched.  FV2 given (s_rs
+ * must be NULL): the row pass of the sparse models with the S_hat-weighted sums folded in (sparse_gap.py:88-95) -- the dot
+ * product runs against FV (= exp-shifted E[log V] masked by S_tilde), the accumulation against FV2 (= FV * S_hat), both staged
+ * side by side in LDS, so R[i,:] = sum_j w_ij s_ij FV2[j,:] comes out of this pass and oriana_row_spmm is not needed;
+ * ORIANA_EKRANGE when the two images of 256 factor rows do not fit (Kp > 64): run the pass with s_rs, then oriana_row_spmm.
  * Kernels other than the two-lane ones take nfull = 0 only (ORIANA_EINVAL otherwise) and cut their ranges evenly. */
 int oriana_row_pass_general(const oriana_counts *cm, const float *FU, const float *FV, const float *FV2,
                             const float *w_nz, float *R, float *s_cs, float *sw_cs, float *s_rs, int32_t *tile_flag,
@@ -305,31 +298,20 @@ int oriana_dense_pack(const void *X, int xdtype, int64_t rows, int64_t gd, int64
 int oriana_dense_images(void *img, const float *F, int64_t rows, int64_t K, int side, void *stream);
 /* Row side: S (nct * gd/32 * 1024 floats, out) and R[i,:] += sum_j s_ij FV[j,:] over the dense genes (R must hold the
  * sparse genes' sums or zeros; added with atomics when gene_splits > 1).  flag: [nct][gd / 32] out (every entry written:
- * 1 where the tile of s holds sentinels). */
-int oriana_dense_row_pass(const oriana_dense *d, const float *FU, const void *imgV, float *R, float *S,
-                          int32_t *flag, int64_t K, int64_t gene_splits, void *stream);
-/* [r4] ... with the 256-cell blocks from tail_nfull on split into tail_parts even gene-tile ranges, part p ADDING into slab p
- * of R = (tail_parts, n, Kp) (struct oriana_row_split: the same rows as the sliced row pass of a hybrid layout splits; gene_splits
- * must be 1 then).  tail_parts <= 1: oriana_dense_row_pass. */
+ * 1 where the tile of s holds sentinels).  [r4] tail_parts > 1: the 256-cell blocks from tail_nfull on are split into
+ * tail_parts even gene-tile ranges, part p ADDING into slab p of R = (tail_parts, n, Kp) (struct oriana_row_split: the same rows
+ * as the sliced row pass of a hybrid layout splits; gene_splits must be 1 then).  tail_parts <= 1: no such split. */
 int oriana_dense_row_pass_tail(const oriana_dense *d, const float *FU, const void *imgV, float *R, float *S,
                           int32_t *flag, int64_t K, int64_t gene_splits, int64_t tail_nfull, int64_t tail_parts,
                                const float *den_min /* as oriana_row_pass_general */, void *stream);
 /* Gene side: C[j,:] += sum_i s_ij FU[i,:] for the dense genes (atomics: zero C first), imgU = the cell-side images. */
 int oriana_dense_col_pass(const oriana_dense *d, const void *imgU, const float *S, float *C, int64_t K,
                           int64_t cell_splits, void *stream);
-/* Exact slow path for the flagged tiles (adds to the dense outputs Z_hat_i, Z_hat_j; clears the sentinels in S). */
-int oriana_dense_fixup(const oriana_dense *d, const int32_t *flag, float *S, const float *logU, const float *logV,
-                       const int32_t *row_perm, const int32_t *col_perm, float *Z_hat_i, float *Z_hat_j, int64_t K,
-                       void *stream);
-
-/* The same with the D_hat[i, k] weight of zigap.py:94 on the gene side: Z_hat_j[j, k] += dq[i, k] r_ijk (dq: (n, K) float32,
- * caller's cell order; NULL = oriana_dense_fixup). */
-int oriana_dense_fixup_weighted(const oriana_dense *d, const int32_t *flag, float *S, const float *logU, const float *logV,
-                                const int32_t *row_perm, const int32_t *col_perm, float *Z_hat_i, float *Z_hat_j,
-                                const float *dq, int64_t K, void *stream);
-/* The slow path of every nest: Z_log (zigap.py:95, sparse_gap.py:97; may be NULL), the D_hat[i, k] weight (dq, may be NULL),
- * the masks of the sparse models (S_tilde, S_hat: both or neither; (m, K) float32, caller's gene order).  zj_packed != 0:
- * Z_hat_j is indexed by the PACKED gene index (the row-sharded pCMF sweep exchanges the per-gene sums in packed order). */
+/* Exact slow path for the flagged tiles of every nest (adds to the dense outputs Z_hat_i, Z_hat_j; clears the sentinels in S):
+ * Z_log (zigap.py:95, sparse_gap.py:97; may be NULL), the D_hat[i, k] weight of zigap.py:94 on the gene side (Z_hat_j[j, k] +=
+ * dq[i, k] r_ijk; dq: (n, K) float32, caller's cell order; may be NULL), the masks of the sparse models (S_tilde, S_hat: both or
+ * neither; (m, K) float32, caller's gene order).  zj_packed != 0: Z_hat_j is indexed by the PACKED gene index (the row-sharded
+ * pCMF sweep exchanges the per-gene sums in packed order). */
 int oriana_dense_fixup_variant(const oriana_dense *d, const int32_t *flag, float *S, const float *logU, const float *logV,
                                const int32_t *row_perm, const int32_t *col_perm, float *Z_hat_i, float *Z_hat_j,
                                float *Z_log, const float *dq, const float *S_tilde, const float *S_hat, int64_t K,
@@ -454,19 +436,13 @@ int oriana_gamma_update_finalize(double *a1, double *a2, double *E, float *Elog,
                                  const double *prior1, const double *prior2,
                                  float *Z, const float *F, const float *R, int64_t nslab, const int32_t *row_index,
                                  const double *rate_vec, int64_t r, int64_t K, void *stream);
-/* [r4] ... with oriana_finalize_slabs_from's slab_row0. */
-int oriana_gamma_update_finalize_from(double *a1, double *a2, double *E, float *Elog,
-                                 double *colsum_E, double *colsum_Elog,
-                                 const double *prior1, const double *prior2,
-                                 float *Z, const float *F, const float *R, int64_t nslab, int64_t slab_row0, const int32_t *row_index,
-                                 const double *rate_vec, int64_t r, int64_t K, void *stream);
-
 /* [r5] Both updates with the cell-side half of the NEXT sweep's factor preparation folded in (FU_next != NULL; see
  * oriana_factor_prep_pair_fused): FU_next (r, Kp) float32, zero-filled once by the caller (padding columns are never written),
  * gets exp(Elog - row maximum) in the packed row order of F / R (finalize form) or in the caller's row order (plain form: only
  * for counts without a row permutation); mu_out [r]; upart [4 * oriana_gamma_update_prep_blocks(r, K)].  The blocks query
  * returns 0 when no vector kernel serves this K (odd K above 64, K above 256): the caller then keeps the separate preparation.
- * FU_next = NULL: exactly oriana_gamma_update / oriana_gamma_update_finalize_from. */
+ * FU_next = NULL: exactly oriana_gamma_update / oriana_gamma_update_finalize (the latter with slab_row0: only the rows from
+ * slab_row0 on have more than slab 0, as oriana_finalize_slabs_from). */
 int64_t oriana_gamma_update_prep_blocks(int64_t r, int64_t K);
 int oriana_gamma_update_prep(double *a1, double *a2, double *E, float *Elog,
                              double *colsum_E, double *colsum_Elog,
@@ -516,7 +492,7 @@ int oriana_colsum_f64(double *out, const double *A, const float *mul, int64_t r,
  *   oriana_dropout_update : p_d = sigmoid(logit(pi_d)[None, :] - Lambda), columns with pi_d <= 0 -> 1e-10,
  *                           pi_d >= 1 -> 1 - 1e-10; D_hat = float32(p_d).  Lambda = U_hat V_hat^T, dense
  *                           (rows, m) f64, may alias p_d.
- *   oriana_dropout_fix_nz : p_d[X != 0] = value (1 - 1e-10; 1.0 at initialisation, zigap.py:77) and D_hat,
+ *   oriana_dropout_fix_nz_ld : p_d[X != 0] = value (1 - 1e-10; 1.0 at initialisation, zigap.py:77) and D_hat,
  *                           from the tiled layout.
  *   oriana_colsum_wide_f64: out[j] += sum_i A[i, j]  (pi_d = mean(p_d, axis=0), zigap.py:158).
  */
@@ -586,9 +562,8 @@ int oriana_nzmask_tiles(uint32_t *tiles, const uint32_t *nzmask, int64_t n, int6
 int oriana_dense_t_times_factor_f32(double *out, const float *D, const double *W, float *scratch, int arithmetic,
                                     int64_t n, int64_t m, int64_t K, void *stream);
 int64_t oriana_dense_t_scratch_floats(int64_t n, int64_t K);
-/* either output may be NULL */
-int oriana_dropout_fix_nz(const oriana_counts *cm, double *p_d, float *D_hat, double value, void *stream);
-/* the same with an explicit leading dimension of p_d / D_hat (the sliced part of a hybrid layout: cm->m counts its own genes only) */
+/* ld: the leading dimension of p_d / D_hat (the sliced part of a hybrid layout: cm->m counts its own genes only); either output
+ * may be NULL */
 int oriana_dropout_fix_nz_ld(const oriana_counts *cm, double *p_d, float *D_hat, double value, int64_t ld, void *stream);
 int oriana_colsum_wide_f64(double *out, const double *A, int64_t rows, int64_t m, void *stream);
 /* the same for a float32 matrix (D_hat, while p_d == D_hat exactly: zigap.py:77) */
@@ -659,7 +634,7 @@ int oriana_plan_gene_order(const int64_t *col_nnz, const int64_t *bad, int64_t m
 int64_t oriana_plan_col_work_capacity(int64_t nrb, int64_t ncb, int64_t width);
 int oriana_plan_col_work(const int32_t *tile_iters, int64_t nrb, int64_t ncb, int64_t width, int64_t cus,
                          int64_t target_items, int rounds, int sum_price, int32_t *items, int64_t cap, int64_t *n_items);
-/* Splits of the dense-gene kernels of a hybrid layout: gene ranges of oriana_dense_row_pass (at most two work-groups per CU)
+/* Splits of the dense-gene kernels of a hybrid layout: gene ranges of oriana_dense_row_pass_tail (at most two work-groups per CU)
  * and cell ranges of oriana_dense_col_pass (four per CU, a multiple of 8 cell tiles). */
 int oriana_plan_dense_splits(int64_t n, int64_t gd, int64_t cus, int64_t *gene_splits, int64_t *cell_splits);
 

@@ -53,10 +53,8 @@ _SIGS = {
     'oriana_factor_prep_pair_fused': (c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, ctypes.POINTER(OrianaClearList), _P]),
     'oriana_prep_scratch_bytes': (_I, []),
     'oriana_row_pass': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
-    'oriana_row_pass_gene_splits': (_I, [ctypes.POINTER(OrianaCounts), _I]),
     'oriana_row_pass_split': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _I, _I, _P]),
     'oriana_row_spmm': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _I, _P]),
-    'oriana_row_pass_masked': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'oriana_row_pass_general': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.POINTER(OrianaRowSplit), _P, _P]),
     'oriana_prep_den_threshold_offset': (_I, []),
     'oriana_row_pass_plan': (c_int, [ctypes.POINTER(OrianaCounts), _I, _P, ctypes.POINTER(OrianaRowSplit)]),
@@ -84,12 +82,9 @@ _SIGS = {
     'oriana_dense_image_pieces': (c_int64, [_I, c_int]),
     'oriana_dense_pack': (c_int, [_P, c_int, _I, _I, _I, _I, _P, _P]),
     'oriana_dense_images': (c_int, [_P, _P, _I, _I, c_int, _P]),
-    'oriana_dense_row_pass': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _I, _I, _P]),
     'oriana_dense_row_pass_tail': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'oriana_dense_col_pass': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _I, _I, _P]),
-    'oriana_dense_fixup': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'oriana_dense_metric': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
-    'oriana_dense_fixup_weighted': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'oriana_dense_fixup_variant': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, c_int, _P]),
     'oriana_dense_images2': (c_int, [_P, _P, _P, _I, _I, c_int, _P]),
     'oriana_dense_fix_nz': (c_int, [ctypes.POINTER(OrianaDense), _P, _I, _P, _P, c_double, _P]),
@@ -106,7 +101,6 @@ _SIGS = {
     'oriana_gamma_update': (c_int, [_P] * 13 + [_I, _I, _P]),
     'oriana_mstep_gamma': (c_int, [_P, _P, _P, _P, c_double, _I, _P]),
     'oriana_gamma_update_finalize': (c_int, [_P] * 11 + [_I, _P, _P, _I, _I, _P]),
-    'oriana_gamma_update_finalize_from': (c_int, [_P] * 11 + [_I, _I, _P, _P, _I, _I, _P]),
     'oriana_gamma_update_prep_blocks': (_I, [_I, _I]),
     'oriana_gamma_update_prep': (c_int, [_P] * 13 + [_I, _I, _P, _P, _P, _P]),
     'oriana_gamma_update_finalize_prep': (c_int, [_P] * 11 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
@@ -128,7 +122,6 @@ _SIGS = {
     'oriana_count_stats': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P]),
     'oriana_dropout_metric': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'oriana_nzmask_f32': (c_int, [_P, _P, _I, _I, _P]),
-    'oriana_dropout_fix_nz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, c_double, _P]),
     'oriana_dropout_fix_nz_ld': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, c_double, _I, _P]),
     'oriana_mul_f64_f32': (c_int, [_P, _P, _P, _I, _P]),
     'oriana_colsum_wide_f64': (c_int, [_P, _P, _I, _I, _P]),

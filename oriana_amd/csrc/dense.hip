@@ -296,10 +296,6 @@ extern "C" int oriana_dropout_fix_nz_ld(const oriana_counts *cm, double *p_d, fl
     return 0;
 }
 
-extern "C" int oriana_dropout_fix_nz(const oriana_counts *cm, double *p_d, float *D_hat, double value, void *stream) {
-    return cm ? oriana_dropout_fix_nz_ld(cm, p_d, D_hat, value, cm->m, stream) : ORIANA_EINVAL;
-}
-
 extern "C" int oriana_colsum_wide_f64(double *out, const double *A, int64_t rows, int64_t m, void *stream) {
     if (rows < 0 || m < 0) return ORIANA_EINVAL;
     if (rows == 0 || m == 0) return 0;

@@ -850,11 +850,6 @@ extern "C" int oriana_dense_row_pass_tail(const oriana_dense *d, const float *FU
     return 0;
 }
 
-extern "C" int oriana_dense_row_pass(const oriana_dense *d, const float *FU, const void *imgV, float *R, float *S,
-                                     int32_t *flag, int64_t K, int64_t gene_splits, void *stream) {
-    return oriana_dense_row_pass_tail(d, FU, imgV, R, S, flag, K, gene_splits, 0, 1, nullptr, stream);
-}
-
 extern "C" int oriana_dense_col_pass(const oriana_dense *d, const void *imgU, const float *S, float *C, int64_t K,
                                      int64_t cell_splits, void *stream) {
     int kc, tl, kp;
@@ -896,18 +891,6 @@ extern "C" int oriana_dense_fixup_variant(const oriana_dense *d, const int32_t *
                        flag, logU, logV, row_perm, col_perm, Zi, Zj, d->n, ngt, (int)K, dq, S_tilde, S_hat, Zlog, zj_packed);
     ORIANA_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int oriana_dense_fixup_weighted(const oriana_dense *d, const int32_t *flag, float *S, const float *logU,
-                                           const float *logV, const int32_t *row_perm, const int32_t *col_perm, float *Zi,
-                                           float *Zj, const float *dq, int64_t K, void *stream) {
-    return oriana_dense_fixup_variant(d, flag, S, logU, logV, row_perm, col_perm, Zi, Zj, nullptr, dq, nullptr, nullptr, K, 0, stream);
-}
-
-extern "C" int oriana_dense_fixup(const oriana_dense *d, const int32_t *flag, float *S, const float *logU,
-                                  const float *logV, const int32_t *row_perm, const int32_t *col_perm, float *Zi,
-                                  float *Zj, int64_t K, void *stream) {
-    return oriana_dense_fixup_weighted(d, flag, S, logU, logV, row_perm, col_perm, Zi, Zj, nullptr, K, stream);
 }
 
 extern "C" int oriana_dense_fix_nz(const oriana_dense *d, float *D_hat, int64_t ld, const int32_t *row_perm,

@@ -342,7 +342,7 @@ extern "C" int64_t oriana_kpad(int64_t K) {
     return 4 * c.G * c.T4 + c.G * c.TAIL;
 }
 
-extern "C" const char *oriana_version(void) { return "oriana_hip gfx950 0.4"; }
+extern "C" const char *oriana_version(void) { return "oriana_hip gfx950 0.5"; }
 
 extern "C" int64_t oriana_col_block_tiles(int64_t K) {
     KCfg c;
@@ -443,9 +443,10 @@ static oriana_row_split no_split(const oriana_counts *cm) {
     sp.nfull = (int32_t)cm->nrb; sp.parts = 1; sp.edge[0] = 0; sp.edge[1] = (int32_t)cm->ncb;
     return sp;
 }
-static oriana_row_split even_split(const oriana_counts *cm, int64_t gene_splits) {        // oriana_row_pass_split
+// oriana_row_pass_split: every row block in gene_splits even ranges (a count split_ok rejects stays rejected as parts = 0)
+static oriana_row_split even_split(int64_t gene_splits) {
     oriana_row_split sp = {};
-    sp.nfull = 0; sp.parts = (int32_t)gene_splits; sp.edge[0] = -1;
+    sp.nfull = 0; sp.parts = (gene_splits < 1 || gene_splits > 65535) ? 0 : (int32_t)gene_splits; sp.edge[0] = -1;
     return sp;
 }
 static bool split_ok(const oriana_counts *cm, const oriana_row_split &sp) {
@@ -461,18 +462,7 @@ static bool split_ok(const oriana_counts *cm, const oriana_row_split &sp) {
 extern "C" int oriana_row_pass(const oriana_counts *cm, const float *FU, const float *FV, const float *w_nz,
                                float *R, float *s_cs, float *sw_cs, float *s_rs, int32_t *tile_flag, int64_t K,
                                void *stream) {
-    if (!counts_ok(cm) || K <= 0) return ORIANA_EINVAL;
-    KCfg cfg;
-    if (!pick_cfg(K, &cfg)) return ORIANA_EKRANGE;
-    if (cm->n == 0) return 0;
-    if (!FU || !R || (cm->m > 0 && !FV) || (cm->m > 0 && (!s_cs || !tile_flag))) return ORIANA_EINVAL;
-    if ((w_nz != nullptr) != (sw_cs != nullptr)) return ORIANA_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const oriana_row_split sp = no_split(cm);
-#define CALL(G, T, L) return launch_row_pass<G, T, L>(cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, s, nullptr, sp)
-    ORIANA_FOR_CFG(cfg, CALL);
-#undef CALL
-    return 0;
+    return oriana_row_pass_general(cm, FU, FV, nullptr, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, K, nullptr, nullptr, stream);
 }
 
 // Gene-tile split of the plain row pass for short matrices: a row block is one work-group (two for K > 116), so a
@@ -548,49 +538,15 @@ extern "C" int oriana_row_pass_plan(const oriana_counts *cm, int64_t K, const do
     return oriana_row_pass_plan_cus(cm, K, tile_cost, oriana_device_cus(), out);
 }
 
-// (round 3's interface: the number of gene ranges of a whole-grid split; 1 when the plan splits the last round only)
-extern "C" int64_t oriana_row_pass_gene_splits(const oriana_counts *cm, int64_t K) {
-    oriana_row_split sp;
-    if (oriana_row_pass_plan(cm, K, nullptr, &sp) != 0) return 1;
-    return sp.nfull == 0 ? sp.parts : 1;
-}
-
 extern "C" int oriana_row_pass_split(const oriana_counts *cm, const float *FU, const float *FV, float *R, float *s_cs,
                                      int32_t *tile_flag, int64_t K, int64_t gene_splits, void *stream) {
-    if (!counts_ok(cm) || K <= 0) return ORIANA_EINVAL;
-    KCfg cfg;
-    if (!pick_cfg(K, &cfg)) return ORIANA_EKRANGE;
-    if (cm->n == 0) return 0;
-    if (!FU || !R || (cm->m > 0 && !FV) || (cm->m > 0 && (!s_cs || !tile_flag))) return ORIANA_EINVAL;
-    if (gene_splits < 1 || gene_splits > 65535 || (cm->ncb > 0 && gene_splits > cm->ncb)) return ORIANA_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const oriana_row_split sp = even_split(cm, gene_splits);
-#define CALL(G, T, L) return launch_row_pass<G, T, L>(cm, FU, FV, nullptr, R, s_cs, nullptr, nullptr, tile_flag, s, nullptr, sp)
-    ORIANA_FOR_CFG(cfg, CALL);
-#undef CALL
-    return 0;
+    const oriana_row_split sp = even_split(gene_splits);
+    return oriana_row_pass_general(cm, FU, FV, nullptr, nullptr, R, s_cs, nullptr, nullptr, tile_flag, K, &sp, nullptr, stream);
 }
 
-extern "C" int oriana_row_pass_masked(const oriana_counts *cm, const float *FU, const float *FV, const float *FV2,
-                                      const float *w_nz, float *R, float *s_cs, float *sw_cs, int32_t *tile_flag,
-                                      int64_t K, void *stream) {
-    if (!counts_ok(cm) || K <= 0) return ORIANA_EINVAL;
-    KCfg cfg;
-    if (!pick_cfg(K, &cfg)) return ORIANA_EKRANGE;
-    if (cm->n == 0) return 0;
-    if (!FU || !R || (cm->m > 0 && (!FV || !FV2)) || (cm->m > 0 && (!s_cs || !tile_flag))) return ORIANA_EINVAL;
-    if ((w_nz != nullptr) != (sw_cs != nullptr)) return ORIANA_EINVAL;
-    if (cm->m == 0) return oriana_row_pass(cm, FU, FV, w_nz, R, s_cs, sw_cs, nullptr, tile_flag, K, stream);
-    hipStream_t s = (hipStream_t)stream;
-    const oriana_row_split sp = no_split(cm);
-#define CALL(G, T, L) return launch_row_pass<G, T, L>(cm, FU, FV, w_nz, R, s_cs, sw_cs, nullptr, tile_flag, s, FV2, sp)
-    ORIANA_FOR_CFG(cfg, CALL);
-#undef CALL
-    return 0;
-}
-
-// The row pass in full generality: every variant of oriana_row_pass / oriana_row_pass_masked (FV2 may be null) with the gene
-// tiles of a row block split over gene_splits work-groups, each storing its row sums in its own slab of R.
+// The row pass in full generality: the plain pass, or (FV2 given) the sparse models' two-image form, with the gene tiles of a
+// row block split over work-groups (split; NULL = none), each storing its row sums in its own slab of R.  The one place the
+// arguments of a row pass are validated: oriana_row_pass and oriana_row_pass_split forward here.
 extern "C" int oriana_row_pass_general(const oriana_counts *cm, const float *FU, const float *FV, const float *FV2,
                                        const float *w_nz, float *R, float *s_cs, float *sw_cs, float *s_rs,
                                        int32_t *tile_flag, int64_t K, const oriana_row_split *split, const float *den_min,

@@ -7,7 +7,7 @@
 // CPU against a NumPy restatement), engine.py calls them, and oriana_counts_create_* / oriana_zq_*_resident keep a count
 // matrix packed across calls for a non-Python host: the reference calls its loop nest once per step() with the same X
 // (oriana/models/gap.py:89-94).
-#include "common.h"
+#include "zq_nest.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -311,7 +311,7 @@ struct oriana_resident {
     // plans
     oriana_row_split split;
     int32_t *col_work = nullptr;
-    int64_t n_col_work = 0, dn_gene_splits = 1, dn_cell_splits = 1, nslab = 1;
+    int64_t n_col_work = 0, dn_gene_splits = 1, dn_cell_splits = 1;
     // workspace of a call
     float *FU = nullptr, *FV = nullptr, *R = nullptr, *C = nullptr, *s_cs = nullptr, *prep = nullptr;
     float *dn_S = nullptr, *dn_imgV = nullptr, *dn_imgU = nullptr;
@@ -344,8 +344,6 @@ void resident_free(oriana_resident *h) {
     for (void *q : h->allocs) (void)hipFree(q);
     delete h;
 }
-
-#define RES_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // A source of dense float32 row chunks in the caller's gene order: a dense device matrix (no copy) or CSR host arrays
 // (expanded into a device buffer, chunk by chunk)
@@ -395,21 +393,21 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
             max_e = std::max(max_e, src.indptr[r1] - src.indptr[r0]);
         }
         src.max_e = max_e;
-        RES_TRY(tmp_alloc((void **)&src.buf, sizeof(float) * chunk * m));
-        RES_TRY(tmp_alloc((void **)&src.d_indptr, sizeof(int64_t) * (chunk + 1)));
-        RES_TRY(tmp_alloc((void **)&src.d_indices, sizeof(int32_t) * std::max<int64_t>(max_e, 1)));
-        RES_TRY(tmp_alloc((void **)&src.d_data, sizeof(float) * std::max<int64_t>(max_e, 1)));
+        ORIANA_TRY(tmp_alloc((void **)&src.buf, sizeof(float) * chunk * m));
+        ORIANA_TRY(tmp_alloc((void **)&src.d_indptr, sizeof(int64_t) * (chunk + 1)));
+        ORIANA_TRY(tmp_alloc((void **)&src.d_indices, sizeof(int32_t) * std::max<int64_t>(max_e, 1)));
+        ORIANA_TRY(tmp_alloc((void **)&src.d_data, sizeof(float) * std::max<int64_t>(max_e, 1)));
     }
     // ---- 1. per-gene statistics -> gene order, dense set
     unsigned long long *d_nnz = nullptr, *d_bad = nullptr;
-    RES_TRY(tmp_alloc((void **)&d_nnz, sizeof(unsigned long long) * m));
-    RES_TRY(tmp_alloc((void **)&d_bad, sizeof(unsigned long long) * m));
+    ORIANA_TRY(tmp_alloc((void **)&d_nnz, sizeof(unsigned long long) * m));
+    ORIANA_TRY(tmp_alloc((void **)&d_bad, sizeof(unsigned long long) * m));
     ORIANA_HIP_CHECK(hipMemsetAsync(d_nnz, 0, sizeof(unsigned long long) * m, s));
     ORIANA_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long) * m, s));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = std::min(n, r0 + chunk) - r0;
         const float *Xc; int64_t ld;
-        RES_TRY(src.get(r0, rows, &Xc, &ld, s));
+        ORIANA_TRY(src.get(r0, rows, &Xc, &ld, s));
         hipLaunchKernelGGL(k_col_stats, dim3((unsigned)((m + 255) / 256), (unsigned)((rows + 255) / 256)), dim3(256), 0, s, Xc, rows, m, ld, d_nnz, d_bad);
         ORIANA_LAUNCH_CHECK();
     }
@@ -420,26 +418,26 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
     std::vector<int32_t> order((size_t)m);
     int64_t gd = 0;
     const double dd = (dense_density > 0.0 && oriana_dense_supported(K)) ? dense_density : 0.0;
-    RES_TRY(oriana_plan_gene_order(col_nnz.data(), bad.data(), m, n, dd, 0.0, order.data(), &gd));
+    ORIANA_TRY(oriana_plan_gene_order(col_nnz.data(), bad.data(), m, n, dd, 0.0, order.data(), &gd));
     h->gd = gd; h->ms = m - gd;
     h->nrb = (n + TILE - 1) / TILE; h->ncb = (h->ms + TILE - 1) / TILE; h->nt = h->nrb * h->ncb;
-    RES_TRY(dev_alloc(h, &h->col_perm, (size_t)m, false, s));
+    ORIANA_TRY(dev_alloc(h, &h->col_perm, (size_t)m, false, s));
     ORIANA_HIP_CHECK(hipMemcpyAsync(h->col_perm, order.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, s));
     // ---- 2. tile tables
     const size_t nt1 = (size_t)std::max<int64_t>(h->nt, 1);
-    RES_TRY(dev_alloc(h, &h->tile_nnz, nt1, true, s));
-    RES_TRY(dev_alloc(h, &h->tile_rslots, nt1, true, s));
-    RES_TRY(dev_alloc(h, &h->tile_cslots, nt1, true, s));
-    RES_TRY(dev_alloc(h, &h->tile_flag, nt1, true, s));
-    RES_TRY(dev_alloc(h, &h->rslice, nt1 * 17, true, s));
-    RES_TRY(dev_alloc(h, &h->cslice, nt1 * 17, true, s));
-    RES_TRY(dev_alloc(h, &h->roff, nt1 + 1, true, s));
-    RES_TRY(dev_alloc(h, &h->coff, nt1 + 1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->tile_nnz, nt1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->tile_rslots, nt1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->tile_cslots, nt1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->tile_flag, nt1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->rslice, nt1 * 17, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->cslice, nt1 * 17, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->roff, nt1 + 1, true, s));
+    ORIANA_TRY(dev_alloc(h, &h->coff, nt1 + 1, true, s));
     float *perm_buf = nullptr;
-    RES_TRY(tmp_alloc((void **)&perm_buf, sizeof(float) * chunk * m));
+    ORIANA_TRY(tmp_alloc((void **)&perm_buf, sizeof(float) * chunk * m));
     auto permuted = [&](int64_t r0, int64_t rows) -> int {
         const float *Xc; int64_t ld;
-        RES_TRY(src.get(r0, rows, &Xc, &ld, s));
+        ORIANA_TRY(src.get(r0, rows, &Xc, &ld, s));
         hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)((m + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, s, perm_buf, Xc,
                            h->col_perm, rows, m, ld);
         ORIANA_LAUNCH_CHECK();
@@ -448,8 +446,8 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
     if (h->ms > 0) {
         for (int64_t r0 = 0; r0 < n; r0 += chunk) {
             const int64_t rows = std::min(n, r0 + chunk) - r0;
-            RES_TRY(permuted(r0, rows));
-            RES_TRY(oriana_pack_count(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->tile_nnz, h->tile_rslots, h->tile_cslots,
+            ORIANA_TRY(permuted(r0, rows));
+            ORIANA_TRY(oriana_pack_count(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->tile_nnz, h->tile_rslots, h->tile_cslots,
                                       h->rslice, h->cslice, s));
         }
         hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, h->roff, h->tile_rslots, h->nt);
@@ -469,16 +467,16 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
     int64_t nnz_sparse = 0;
     for (int64_t t = 0; t < h->nt; ++t) nnz_sparse += tile_nnz_h[(size_t)t];
     // ---- 3. records (padding slots: x == 0, row index 0), the dense block
-    RES_TRY(dev_alloc(h, &h->rowrec, (size_t)std::max<int64_t>(h->rslots, 1), true, s));
-    RES_TRY(dev_alloc(h, &h->ridx, (size_t)std::max<int64_t>(h->cslots, 1), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->rowrec, (size_t)std::max<int64_t>(h->rslots, 1), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->ridx, (size_t)std::max<int64_t>(h->cslots, 1), true, s));
     const int64_t nct = h->nrb * 8, ngt = gd / 32;
-    if (gd > 0) RES_TRY(dev_alloc(h, &h->dense_x, (size_t)(nct * ngt * 1024), true, s));
+    if (gd > 0) ORIANA_TRY(dev_alloc(h, &h->dense_x, (size_t)(nct * ngt * 1024), true, s));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = std::min(n, r0 + chunk) - r0;
-        RES_TRY(permuted(r0, rows));
-        if (gd > 0) RES_TRY(oriana_dense_pack(perm_buf, 0, rows, gd, m, r0 / 32, h->dense_x, s));
+        ORIANA_TRY(permuted(r0, rows));
+        if (gd > 0) ORIANA_TRY(oriana_dense_pack(perm_buf, 0, rows, gd, m, r0 / 32, h->dense_x, s));
         if (h->ms > 0)
-            RES_TRY(oriana_pack_fill(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->roff, h->coff, h->rslice, h->cslice, h->rowrec,
+            ORIANA_TRY(oriana_pack_fill(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->roff, h->coff, h->rslice, h->cslice, h->rowrec,
                                      h->ridx, nullptr, 0, nullptr, s));
     }
     int64_t nnz_dense = 0;
@@ -498,9 +496,9 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
             for (int64_t rb = 0; rb < h->nrb; ++rb) sum += (double)tile_rslots_h[(size_t)(rb * h->ncb + c)];
             tile_cost[(size_t)c] = sum / (double)h->nrb / (16.0 * 64.0) + 2.0;
         }
-        RES_TRY(oriana_row_pass_plan_cus(&cm, K, tile_cost.data(), h->cus, &h->split));
+        ORIANA_TRY(oriana_row_pass_plan_cus(&cm, K, tile_cost.data(), h->cus, &h->split));
         int32_t *d_longest = nullptr;
-        RES_TRY(tmp_alloc((void **)&d_longest, sizeof(int32_t) * h->nt));
+        ORIANA_TRY(tmp_alloc((void **)&d_longest, sizeof(int32_t) * h->nt));
         hipLaunchKernelGGL(k_tile_longest, dim3((unsigned)((h->nt + 255) / 256)), dim3(256), 0, s, d_longest, h->cslice, h->nt);
         ORIANA_LAUNCH_CHECK();
         std::vector<int32_t> longest((size_t)h->nt);
@@ -510,8 +508,8 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
         const int64_t cap = oriana_plan_col_work_capacity(h->nrb, h->ncb, width);
         std::vector<int32_t> items((size_t)cap * 3);
         if (h->cslots > 0) {
-            RES_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, width, h->cus, 0, 1, 0, items.data(), cap, &h->n_col_work));
-            RES_TRY(dev_alloc(h, &h->col_work, (size_t)std::max<int64_t>(h->n_col_work * 3, 1), false, s));
+            ORIANA_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, width, h->cus, 0, 1, 0, items.data(), cap, &h->n_col_work));
+            ORIANA_TRY(dev_alloc(h, &h->col_work, (size_t)std::max<int64_t>(h->n_col_work * 3, 1), false, s));
             ORIANA_HIP_CHECK(hipMemcpyAsync(h->col_work, items.data(), sizeof(int32_t) * h->n_col_work * 3, hipMemcpyHostToDevice, s));
             ORIANA_HIP_CHECK(hipStreamSynchronize(s));
             // the dual column pass of the sparse nests (two factor images per tile: one column tile per item)
@@ -519,29 +517,28 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
             else {
                 const int64_t cap1 = oriana_plan_col_work_capacity(h->nrb, h->ncb, 1);
                 std::vector<int32_t> items1((size_t)cap1 * 3);
-                RES_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, 1, h->cus, 0, 1, 0, items1.data(), cap1, &h->n_col_work1));
-                RES_TRY(dev_alloc(h, &h->col_work1, (size_t)std::max<int64_t>(h->n_col_work1 * 3, 1), false, s));
+                ORIANA_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, 1, h->cus, 0, 1, 0, items1.data(), cap1, &h->n_col_work1));
+                ORIANA_TRY(dev_alloc(h, &h->col_work1, (size_t)std::max<int64_t>(h->n_col_work1 * 3, 1), false, s));
                 ORIANA_HIP_CHECK(hipMemcpyAsync(h->col_work1, items1.data(), sizeof(int32_t) * h->n_col_work1 * 3, hipMemcpyHostToDevice, s));
                 ORIANA_HIP_CHECK(hipStreamSynchronize(s));
             }
         }
     }
-    h->nslab = h->split.parts;
-    if (gd > 0) RES_TRY(oriana_plan_dense_splits(n, gd, h->cus, &h->dn_gene_splits, &h->dn_cell_splits));
+    if (gd > 0) ORIANA_TRY(oriana_plan_dense_splits(n, gd, h->cus, &h->dn_gene_splits, &h->dn_cell_splits));
     // ---- 5. workspace of a call
     const int64_t Kp = h->Kp;
-    RES_TRY(dev_alloc(h, &h->FU, (size_t)(std::max<int64_t>(n, 1) * Kp), true, s));
-    RES_TRY(dev_alloc(h, &h->FV, (size_t)(std::max<int64_t>(m, 1) * Kp), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->FU, (size_t)(std::max<int64_t>(n, 1) * Kp), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->FV, (size_t)(std::max<int64_t>(m, 1) * Kp), true, s));
     // (slabs 1.. of a last-round split hold the rows of the split row blocks only)
-    RES_TRY(dev_alloc(h, &h->R, (size_t)((std::max<int64_t>(n, 1) + (h->nslab - 1) * (n - (int64_t)h->split.nfull * TILE)) * Kp), true, s));
-    RES_TRY(dev_alloc(h, &h->C, (size_t)(std::max<int64_t>(m, 1) * Kp), true, s));
-    RES_TRY(dev_alloc(h, &h->s_cs, (size_t)std::max<int64_t>(h->cslots, 1), true, s));      // (padding slots must stay 0)
-    RES_TRY(dev_alloc(h, &h->prep, (size_t)(oriana_prep_scratch_bytes() / 4), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->R, (size_t)(zq_r_rows(n, &h->split) * Kp), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->C, (size_t)(std::max<int64_t>(m, 1) * Kp), true, s));
+    ORIANA_TRY(dev_alloc(h, &h->s_cs, (size_t)std::max<int64_t>(h->cslots, 1), true, s));      // (padding slots must stay 0)
+    ORIANA_TRY(dev_alloc(h, &h->prep, (size_t)(oriana_prep_scratch_bytes() / 4), true, s));
     if (gd > 0) {
-        RES_TRY(dev_alloc(h, &h->dn_S, (size_t)(nct * ngt * 1024), true, s));
-        RES_TRY(dev_alloc(h, &h->dn_flag, (size_t)std::max<int64_t>(nct * ngt, 1), true, s));
-        RES_TRY(dev_alloc(h, &h->dn_imgV, (size_t)(ngt * oriana_dense_image_pieces(K, 0) * 4), false, s));
-        RES_TRY(dev_alloc(h, &h->dn_imgU, (size_t)(std::max<int64_t>((n + 31) / 32, 1) * oriana_dense_image_pieces(K, 1) * 4), false, s));
+        ORIANA_TRY(dev_alloc(h, &h->dn_S, (size_t)(nct * ngt * 1024), true, s));
+        ORIANA_TRY(dev_alloc(h, &h->dn_flag, (size_t)std::max<int64_t>(nct * ngt, 1), true, s));
+        ORIANA_TRY(dev_alloc(h, &h->dn_imgV, (size_t)(ngt * oriana_dense_image_pieces(K, 0) * 4), false, s));
+        ORIANA_TRY(dev_alloc(h, &h->dn_imgU, (size_t)(std::max<int64_t>((n + 31) / 32, 1) * oriana_dense_image_pieces(K, 1) * 4), false, s));
     }
     ORIANA_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -602,47 +599,26 @@ extern "C" int oriana_counts_info(const oriana_resident *h, int64_t *info, int64
     return 0;
 }
 
+// A view of the handle's buffers for zq_run (zq_nest.h): the two-image kernels and the dynamic den threshold, as engine.zq runs
+// the nests for the model classes; the variant extras are whatever the handle holds at this point.
+static ZqView resident_view(const oriana_resident *h) {
+    ZqView v;
+    v.cm = &h->cm; v.dn = &h->dn; v.n = h->n; v.m = h->m; v.K = h->K; v.Kp = h->Kp; v.gd = h->gd;
+    v.FU = h->FU; v.FV = h->FV; v.R = h->R; v.C = h->C; v.s_cs = h->s_cs; v.prep = h->prep; v.tile_flag = h->tile_flag;
+    v.F2 = h->F2; v.G2 = h->G2; v.C2 = h->C2; v.GQ = h->GQ; v.s_rs = h->s_rs;
+    v.dn_S = h->dn_S; v.dn_flag = h->dn_flag; v.dn_imgV = h->dn_imgV; v.dn_imgU = h->dn_imgU;
+    v.dn_gene_splits = h->dn_gene_splits; v.dn_cell_splits = h->dn_cell_splits;
+    v.split = &h->split; v.col_perm = h->col_perm;
+    v.col_work = h->col_work; v.n_col_work = h->n_col_work; v.col_work1 = h->col_work1; v.n_col_work1 = h->n_col_work1;
+    v.dynamic_den = true; v.clear_outputs = true; v.two_image = true;
+    return v;
+}
+
 // The pCMF nest on the resident layout (sliced or hybrid): what engine.zq_gap runs for the model classes.
 extern "C" int oriana_zq_gap_resident(oriana_resident *h, float *Z_i, float *Z_j, const float *log_U_hat, const float *log_V_hat,
                                       void *stream) {
     if (!h || !Z_i || !Z_j || !log_U_hat || !log_V_hat) return ORIANA_EINVAL;
-    const int64_t n = h->n, m = h->m, K = h->K, Kp = h->Kp, gd = h->gd;
-    const float *den_min = reinterpret_cast<const float *>(reinterpret_cast<const char *>(h->prep) + oriana_prep_den_threshold_offset());
-    oriana_clear_list cl;
-    memset(&cl, 0, sizeof(cl));
-    int e = 0;
-    cl.ptr[e] = Z_i; cl.bytes[e++] = (int64_t)sizeof(float) * n * K;
-    cl.ptr[e] = Z_j; cl.bytes[e++] = (int64_t)sizeof(float) * m * K;
-    cl.ptr[e] = h->C; cl.bytes[e++] = (int64_t)sizeof(float) * m * Kp;
-    cl.ptr[e] = h->tile_flag; cl.bytes[e++] = (int64_t)sizeof(int32_t) * std::max<int64_t>(h->nt, 1);
-    if (h->ms == 0) { cl.ptr[e] = h->R; cl.bytes[e++] = (int64_t)sizeof(float) * (n + (h->nslab - 1) * (n - (int64_t)h->split.nfull * TILE)) * Kp; }
-    RES_TRY(oriana_factor_prep_pair_clear(h->FU, h->FV, log_U_hat, log_V_hat, nullptr, nullptr, h->col_perm, n, m, K, h->prep, &cl, stream));
-    float *FVs = h->FV + gd * Kp, *Cs = h->C + gd * Kp;
-    if (h->ms > 0)
-        RES_TRY(oriana_row_pass_general(&h->cm, h->FU, FVs, nullptr, nullptr, h->R, h->s_cs, nullptr, nullptr, h->tile_flag, K, &h->split,
-                                        den_min, stream));
-    if (gd > 0) {
-        RES_TRY(oriana_dense_images(h->dn_imgV, h->FV, gd, K, 0, stream));
-        int64_t tail_nfull = 0, tail_parts = 1;
-        if (h->split.nfull > 0 && h->split.parts > 1 && h->dn_gene_splits == 1 && h->split.parts <= gd / 32) {
-            tail_nfull = h->split.nfull; tail_parts = h->split.parts;
-        }
-        RES_TRY(oriana_dense_row_pass_tail(&h->dn, h->FU, h->dn_imgV, h->R, h->dn_S, h->dn_flag, K, h->dn_gene_splits, tail_nfull, tail_parts,
-                                           den_min, stream));
-    }
-    if (h->ms > 0)
-        RES_TRY(oriana_fixup(&h->cm, h->tile_flag, h->s_cs, nullptr, nullptr, log_U_hat, log_V_hat, nullptr, nullptr, nullptr, nullptr, Z_i, Z_j,
-                             nullptr, K, 0, stream));
-    if (gd > 0)
-        RES_TRY(oriana_dense_fixup_variant(&h->dn, h->dn_flag, h->dn_S, log_U_hat, log_V_hat, nullptr, h->col_perm, Z_i, Z_j, nullptr, nullptr,
-                                           nullptr, nullptr, K, 0, stream));
-    RES_TRY(oriana_finalize_slabs_from(Z_i, h->FU, h->R, h->nslab, (int64_t)h->split.nfull * TILE, nullptr, n, K, stream));
-    if (h->ms > 0) RES_TRY(oriana_col_pass(&h->cm, h->s_cs, h->FU, Cs, K, h->col_work, h->n_col_work, stream));
-    if (gd > 0) {
-        RES_TRY(oriana_dense_images(h->dn_imgU, h->FU, n, K, 1, stream));
-        RES_TRY(oriana_dense_col_pass(&h->dn, h->dn_imgU, h->dn_S, h->C, K, h->dn_cell_splits, stream));
-    }
-    return oriana_finalize(Z_j, h->FV, h->C, nullptr, h->col_perm, m, K, 1, stream);
+    return zq_run(resident_view(h), Z_i, Z_j, nullptr, log_U_hat, log_V_hat, nullptr, nullptr, nullptr, stream);
 }
 
 // [r6] The ZI / sparse nests WITHOUT per-entry weights -- D_hat == 1 at every stored entry, which is what every D_hat the
@@ -654,104 +630,21 @@ extern "C" int oriana_zq_gap_resident(oriana_resident *h, float *Z_i, float *Z_j
 // reads its third output, zigap.py:105-112): the log sums are then skipped.
 static int zq_unit_resident(oriana_resident *h, float *Zi, float *Zj, float *Zlog, const float *log_U_hat, const float *log_V_hat,
                             const float *S_tilde, const float *S_hat, const float *D_hat, int quirk, void *stream) {
-    const int64_t n = h->n, m = h->m, K = h->K, Kp = h->Kp, gd = h->gd;
+    const int64_t n = h->n, m = h->m, K = h->K, Kp = h->Kp;
     hipStream_t s = (hipStream_t)stream;
-    const bool sparse = S_hat != nullptr, have_sliced = h->ms > 0 || gd == 0;
-    const size_t rs1 = (size_t)std::max<int64_t>(h->rslots, 1);
+    const bool sparse = S_hat != nullptr;
     // (every buffer of a group is tested on its own: a failed allocation must not leave a later call with a NULL sibling)
-    if (sparse && !h->F2) RES_TRY(dev_alloc(h, &h->F2, (size_t)(m * Kp), true, s));
-    if (Zlog && !h->G2) RES_TRY(dev_alloc(h, &h->G2, (size_t)(n * Kp), true, s));
-    if (Zlog && !h->C2) RES_TRY(dev_alloc(h, &h->C2, (size_t)(m * Kp), true, s));
-    if (quirk && !h->dq) RES_TRY(dev_alloc(h, &h->dq, (size_t)(n * K), true, s));
-    if (quirk && !h->GQ) RES_TRY(dev_alloc(h, &h->GQ, (size_t)(n * Kp), true, s));
-    const float *den_min = reinterpret_cast<const float *>(reinterpret_cast<const char *>(h->prep) + oriana_prep_den_threshold_offset());
-    const int64_t r_rows = n + (h->nslab - 1) * (n - (int64_t)h->split.nfull * TILE);
-    oriana_clear_list cl;
-    memset(&cl, 0, sizeof(cl));
-    int e = 0;
-    cl.ptr[e] = Zi; cl.bytes[e++] = (int64_t)sizeof(float) * n * K;
-    cl.ptr[e] = Zj; cl.bytes[e++] = (int64_t)sizeof(float) * m * K;
-    cl.ptr[e] = h->C; cl.bytes[e++] = (int64_t)sizeof(float) * m * Kp;
-    cl.ptr[e] = h->tile_flag; cl.bytes[e++] = (int64_t)sizeof(int32_t) * std::max<int64_t>(h->nt, 1);
-    if (Zlog) { cl.ptr[e] = Zlog; cl.bytes[e++] = (int64_t)sizeof(float) * m * K; cl.ptr[e] = h->C2; cl.bytes[e++] = (int64_t)sizeof(float) * m * Kp; }
-    if (!have_sliced) { cl.ptr[e] = h->R; cl.bytes[e++] = (int64_t)sizeof(float) * r_rows * Kp; }
-    RES_TRY(oriana_factor_prep_pair_clear(h->FU, h->FV, log_U_hat, log_V_hat, S_tilde, nullptr, h->col_perm, n, m, K, h->prep, &cl, stream));
-    float *dq = nullptr;
-    if (quirk) { dq = h->dq; RES_TRY(oriana_take_cols_f32(dq, D_hat, n, m, K, stream)); }
-    if (sparse) RES_TRY(oriana_scale_factor(h->F2, h->FV, S_hat, h->col_perm, m, K, 0, stream));
-    const int64_t goff = gd * Kp;
-    const int variant = (sparse ? 1 : 0) | (dq ? 4 : 0);
-    int64_t nslab = 1;
-    if (have_sliced) {
-        bool fused = false;
-        if (sparse) {
-            const int rc = oriana_row_pass_general(&h->cm, h->FU, h->FV + goff, h->F2 + goff, nullptr, h->R, h->s_cs, nullptr, nullptr,
-                                                   h->tile_flag, K, &h->split, den_min, stream);
-            if (rc != 0 && rc != ORIANA_EKRANGE) return rc;
-            fused = rc == 0;
-        }
-        float *s_rs = nullptr;
-        if (!fused) {
-            if (sparse) { if (!h->s_rs) RES_TRY(dev_alloc(h, &h->s_rs, rs1, true, s)); s_rs = h->s_rs; }
-            RES_TRY(oriana_row_pass_general(&h->cm, h->FU, h->FV + goff, nullptr, nullptr, h->R, h->s_cs, nullptr, s_rs, h->tile_flag, K,
-                                            &h->split, den_min, stream));
-        }
-        if (fused || !sparse) nslab = h->nslab;              // (the second row product of the unfused sparse form writes one slab)
-        RES_TRY(oriana_fixup(&h->cm, h->tile_flag, h->s_cs, nullptr, s_rs, log_U_hat, log_V_hat, S_tilde, S_hat, nullptr, dq, Zi, Zj, Zlog, K,
-                             variant, stream));
-        if (sparse && !fused) RES_TRY(oriana_row_spmm(&h->cm, s_rs, nullptr, h->F2 + goff, h->R, K, stream));
-    }
-    if (gd > 0) {
-        RES_TRY(oriana_dense_images2(h->dn_imgV, h->FV, sparse ? h->F2 : nullptr, gd, K, 0, stream));
-        int64_t tail_nfull = 0, tail_parts = 1;
-        if (h->split.nfull > 0 && 1 < h->split.parts && h->split.parts == nslab && h->dn_gene_splits == 1 && h->split.parts <= gd / 32) {
-            tail_nfull = h->split.nfull; tail_parts = h->split.parts;
-        }
-        RES_TRY(oriana_dense_row_pass_tail(&h->dn, h->FU, h->dn_imgV, h->R, h->dn_S, h->dn_flag, K, h->dn_gene_splits, tail_nfull, tail_parts,
-                                           den_min, stream));
-        RES_TRY(oriana_dense_fixup_variant(&h->dn, h->dn_flag, h->dn_S, log_U_hat, log_V_hat, nullptr, h->col_perm, Zi, Zj, Zlog, dq, S_tilde,
-                                           S_hat, K, 0, stream));
-    }
-    RES_TRY(oriana_finalize_slabs_from(Zi, h->FU, h->R, nslab, (int64_t)h->split.nfull * TILE, nullptr, n, K, stream));
-    double *center = reinterpret_cast<double *>(reinterpret_cast<char *>(h->prep) + oriana_prep_center_offset());
-    if (Zlog) {
-        RES_TRY(oriana_log_center(center, h->FU, log_U_hat, Zi, nullptr, n, K, stream));
-        RES_TRY(oriana_scale_factor_centered(h->G2, h->FU, log_U_hat, center, nullptr, n, K, stream));
-    }
-    // ---- per-gene sums
-    auto dense_cols = [&](const float *G, float *Cm) -> int {
-        RES_TRY(oriana_dense_images(h->dn_imgU, G, n, K, 1, stream));
-        return oriana_dense_col_pass(&h->dn, h->dn_imgU, h->dn_S, Cm, K, h->dn_cell_splits, stream);
-    };
-    auto dual = [&](bool *done) -> int {          // C += s FU and C2 += s G2 from one walk over the stream, where two images fit
-        *done = false;
-        if (!h->col_work1) return 0;
-        const int rc = oriana_col_pass_dual(&h->cm, h->s_cs, h->FU, h->G2, h->C + goff, h->C2 + goff, K, h->col_work1, h->n_col_work1, stream);
-        if (rc != 0 && rc != ORIANA_EKRANGE) return rc;
-        *done = rc == 0;
-        return 0;
-    };
-    const float *G = h->FU;
-    if (dq) { RES_TRY(oriana_scale_factor(h->GQ, h->FU, dq, nullptr, n, K, 0, stream)); G = h->GQ; }
-    bool dual_done = false;
-    if (Zlog && !dq && have_sliced) RES_TRY(dual(&dual_done));
-    if (!dual_done && have_sliced) RES_TRY(oriana_col_pass(&h->cm, h->s_cs, G, h->C + goff, K, h->col_work, h->n_col_work, stream));
-    if (gd > 0) RES_TRY(dense_cols(G, h->C));
-    RES_TRY(oriana_finalize(Zj, h->FV, h->C, nullptr, h->col_perm, m, K, 1, stream));
-    if (Zlog) {
-        if (dq) {                                 // the log sums use the plain column sums (zigap.py:95), Z_j the D_hat[i, k]-weighted ones
-            ORIANA_HIP_CHECK(hipMemsetAsync(h->C, 0, sizeof(float) * m * Kp, s));
-            if (have_sliced) {
-                RES_TRY(dual(&dual_done));
-                if (!dual_done) RES_TRY(oriana_col_pass(&h->cm, h->s_cs, h->FU, h->C + goff, K, h->col_work, h->n_col_work, stream));
-            }
-            if (gd > 0) RES_TRY(dense_cols(h->FU, h->C));
-        }
-        if (!dual_done && have_sliced) RES_TRY(oriana_col_pass(&h->cm, h->s_cs, h->G2, h->C2 + goff, K, h->col_work, h->n_col_work, stream));
-        if (gd > 0) RES_TRY(dense_cols(h->G2, h->C2));
-        RES_TRY(oriana_finalize_zlog(Zlog, h->FV, h->C2, h->C, log_V_hat, center, h->col_perm, m, K, stream));
-    }
-    return 0;
+    if (sparse && !h->F2) ORIANA_TRY(dev_alloc(h, &h->F2, (size_t)(m * Kp), true, s));
+    if (Zlog && !h->G2) ORIANA_TRY(dev_alloc(h, &h->G2, (size_t)(n * Kp), true, s));
+    if (Zlog && !h->C2) ORIANA_TRY(dev_alloc(h, &h->C2, (size_t)(m * Kp), true, s));
+    if (quirk && !h->dq) ORIANA_TRY(dev_alloc(h, &h->dq, (size_t)(n * K), true, s));
+    if (quirk && !h->GQ) ORIANA_TRY(dev_alloc(h, &h->GQ, (size_t)(n * Kp), true, s));
+    // (the row-side copy of s for the second row product: the fused form, Kp <= 64, never needs it)
+    if (sparse && Kp > 64 && (h->ms > 0 || h->gd == 0) && !h->s_rs)
+        ORIANA_TRY(dev_alloc(h, &h->s_rs, (size_t)std::max<int64_t>(h->rslots, 1), true, s));
+    ZqView v = resident_view(h);
+    v.dq = quirk ? h->dq : nullptr;
+    return zq_run(v, Zi, Zj, Zlog, log_U_hat, log_V_hat, S_tilde, S_hat, quirk ? D_hat : nullptr, stream);
 }
 
 // The ZI / sparse nests with a GENERAL D_hat (any weight at the stored entries) on a resident SLICED layout: the kernel sequence
@@ -768,62 +661,25 @@ static int zq_variant_resident(oriana_resident *h, float *Zi, float *Zj, float *
         return zq_unit_resident(h, Zi, Zj, Zlog, log_U_hat, log_V_hat, S_tilde, S_hat, D_hat, quirk, stream);
     if (h->gd > 0) return ORIANA_EUNIT;
     hipStream_t s = (hipStream_t)stream;
-    const bool sparse = S_hat != nullptr, weighted = D_hat != nullptr;
+    const bool sparse = S_hat != nullptr;
     const size_t rs1 = (size_t)std::max<int64_t>(h->rslots, 1), cs1 = (size_t)std::max<int64_t>(h->cslots, 1);
-    if (weighted && !h->w_nz) RES_TRY(dev_alloc(h, &h->w_nz, rs1, true, s));
-    if (weighted && !h->sw_cs) RES_TRY(dev_alloc(h, &h->sw_cs, cs1, true, s));
-    if (sparse && !h->s_rs) RES_TRY(dev_alloc(h, &h->s_rs, rs1, true, s));
-    if (sparse && !h->F2) RES_TRY(dev_alloc(h, &h->F2, (size_t)(m * Kp), true, s));
-    if ((Zlog || quirk) && !h->G2) RES_TRY(dev_alloc(h, &h->G2, (size_t)(n * Kp), true, s));
-    if (Zlog && !h->C2) RES_TRY(dev_alloc(h, &h->C2, (size_t)(m * Kp), true, s));
-    if (quirk && !h->dq) RES_TRY(dev_alloc(h, &h->dq, (size_t)(n * K), true, s));
-    const float *den_min = reinterpret_cast<const float *>(reinterpret_cast<const char *>(h->prep) + oriana_prep_den_threshold_offset());
-    oriana_clear_list cl;
-    memset(&cl, 0, sizeof(cl));
-    int e = 0;
-    cl.ptr[e] = Zi; cl.bytes[e++] = (int64_t)sizeof(float) * n * K;
-    cl.ptr[e] = Zj; cl.bytes[e++] = (int64_t)sizeof(float) * m * K;
-    cl.ptr[e] = h->C; cl.bytes[e++] = (int64_t)sizeof(float) * m * Kp;
-    cl.ptr[e] = h->tile_flag; cl.bytes[e++] = (int64_t)sizeof(int32_t) * std::max<int64_t>(h->nt, 1);
-    if (Zlog) { cl.ptr[e] = Zlog; cl.bytes[e++] = (int64_t)sizeof(float) * m * K; cl.ptr[e] = h->C2; cl.bytes[e++] = (int64_t)sizeof(float) * m * Kp; }
-    RES_TRY(oriana_factor_prep_pair_clear(h->FU, h->FV, log_U_hat, log_V_hat, S_tilde, nullptr, h->col_perm, n, m, K, h->prep, &cl, stream));
-    float *w_nz = weighted ? h->w_nz : nullptr, *sw_cs = weighted ? h->sw_cs : nullptr, *s_rs = sparse ? h->s_rs : nullptr;
-    if (weighted && h->nt > 0) {
-        hipLaunchKernelGGL(k_gather_nz, dim3((unsigned)h->nt), dim3(256), 0, s, h->cm, D_hat, m, w_nz);
+    if (!h->w_nz) ORIANA_TRY(dev_alloc(h, &h->w_nz, rs1, true, s));
+    if (!h->sw_cs) ORIANA_TRY(dev_alloc(h, &h->sw_cs, cs1, true, s));
+    if (sparse && !h->s_rs) ORIANA_TRY(dev_alloc(h, &h->s_rs, rs1, true, s));
+    if (sparse && !h->F2) ORIANA_TRY(dev_alloc(h, &h->F2, (size_t)(m * Kp), true, s));
+    if ((Zlog || quirk) && !h->G2) ORIANA_TRY(dev_alloc(h, &h->G2, (size_t)(n * Kp), true, s));
+    if (Zlog && !h->C2) ORIANA_TRY(dev_alloc(h, &h->C2, (size_t)(m * Kp), true, s));
+    if (quirk && !h->dq) ORIANA_TRY(dev_alloc(h, &h->dq, (size_t)(n * K), true, s));
+    if (h->nt > 0) {
+        hipLaunchKernelGGL(k_gather_nz, dim3((unsigned)h->nt), dim3(256), 0, s, h->cm, D_hat, m, h->w_nz);
         ORIANA_LAUNCH_CHECK();
     }
-    float *dq = nullptr;
-    if (quirk) { dq = h->dq; RES_TRY(oriana_take_cols_f32(dq, D_hat, n, m, K, stream)); }
-    // (the whole-grid kernels take no last-round split: the plan's split applies to the plain pass of the two-lane kernels;
-    //  with s_rs the pass leaves R alone, so one slab serves)
-    oriana_row_split sp = h->split;
-    RES_TRY(oriana_row_pass_general(&h->cm, h->FU, h->FV, nullptr, w_nz, h->R, h->s_cs, sw_cs, s_rs, h->tile_flag, K, &sp, den_min, stream));
-    const int variant = (sparse ? 1 : 0) | (weighted ? 2 : 0) | (dq ? 4 : 0);
-    RES_TRY(oriana_fixup(&h->cm, h->tile_flag, h->s_cs, sw_cs, s_rs, log_U_hat, log_V_hat, S_tilde, S_hat, w_nz, dq, Zi, Zj, Zlog, K, variant, stream));
-    int64_t nslab = h->nslab;
-    if (sparse) {
-        RES_TRY(oriana_scale_factor(h->F2, h->FV, S_hat, h->col_perm, m, K, 0, stream));
-        RES_TRY(oriana_row_spmm(&h->cm, s_rs, w_nz, h->F2, h->R, K, stream));
-        nslab = 1;
-    }
-    RES_TRY(oriana_finalize_slabs_from(Zi, h->FU, h->R, nslab, (int64_t)h->split.nfull * TILE, nullptr, n, K, stream));
-    const float *G = h->FU, *s_for_j = sw_cs ? sw_cs : h->s_cs;
-    if (dq) { RES_TRY(oriana_scale_factor(h->G2, h->FU, dq, nullptr, n, K, 0, stream)); G = h->G2; s_for_j = h->s_cs; }
-    RES_TRY(oriana_col_pass(&h->cm, s_for_j, G, h->C, K, h->col_work, h->n_col_work, stream));
-    RES_TRY(oriana_finalize(Zj, h->FV, h->C, nullptr, h->col_perm, m, K, 1, stream));
-    if (Zlog) {
-        const float *s_log = sw_cs ? sw_cs : h->s_cs;
-        if (dq) {
-            ORIANA_HIP_CHECK(hipMemsetAsync(h->C, 0, sizeof(float) * m * Kp, s));
-            RES_TRY(oriana_col_pass(&h->cm, s_log, h->FU, h->C, K, h->col_work, h->n_col_work, stream));
-        }
-        double *center = reinterpret_cast<double *>(reinterpret_cast<char *>(h->prep) + oriana_prep_center_offset());
-        RES_TRY(oriana_log_center(center, h->FU, log_U_hat, Zi, nullptr, n, K, stream));
-        RES_TRY(oriana_scale_factor_centered(h->G2, h->FU, log_U_hat, center, nullptr, n, K, stream));
-        RES_TRY(oriana_col_pass(&h->cm, s_log, h->G2, h->C2, K, h->col_work, h->n_col_work, stream));
-        RES_TRY(oriana_finalize_zlog(Zlog, h->FV, h->C2, h->C, log_V_hat, center, h->col_perm, m, K, stream));
-    }
-    return 0;
+    // (the weighted kernels have no two-image form: the sequence of the stateless entries, FU * dq and the centred factor
+    //  one after the other in G2)
+    ZqView v = resident_view(h);
+    v.w_nz = h->w_nz; v.sw_cs = h->sw_cs; v.dq = quirk ? h->dq : nullptr; v.GQ = h->G2;
+    v.two_image = false; v.col_work1 = nullptr; v.n_col_work1 = 0;
+    return zq_run(v, Zi, Zj, Zlog, log_U_hat, log_V_hat, S_tilde, S_hat, quirk ? D_hat : nullptr, stream);
 }
 
 extern "C" int oriana_counts_declare_unit_dropout(oriana_resident *h, int on) {

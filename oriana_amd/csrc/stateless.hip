@@ -2,7 +2,7 @@
 // after, dense float32 matrices, callee zero-fills, gap.py:67-80 and twins).  X is repacked on
 // every call, as the reference re-casts X on every call (gap.py:94); the model classes keep the
 // packed layout resident instead and call the passes directly.
-#include "common.h"
+#include "zq_nest.h"
 
 namespace oriana {
 
@@ -100,7 +100,7 @@ extern "C" int64_t oriana_zq_workspace_bytes(int64_t n, int64_t m, int64_t K, in
 }
 
 // The four loop nests on dense inputs.  Zlog / S_tilde / S_hat / D_hat may be NULL (absent in that
-// variant); quirk = zigap.py:94 (per-gene sums weighted by D_hat[i, k]).  Mirrors engine.zq.
+// variant); quirk = zigap.py:94 (per-gene sums weighted by D_hat[i, k]).  Packs X, then runs the nest (zq_nest.h).
 static int zq_dense(float *Zi, float *Zj, float *Zlog, const float *log_U_hat, const float *log_V_hat,
                     const float *S_tilde, const float *S_hat, const float *D_hat, int quirk, const float *X,
                     int64_t n, int64_t m, int64_t K, void *ws, int64_t ws_bytes, void *stream) {
@@ -143,12 +143,10 @@ static int zq_dense(float *Zi, float *Zj, float *Zlog, const float *log_U_hat, c
     const int64_t rs1 = tot[0] > 0 ? tot[0] : 1, cs1 = tot[1] > 0 ? tot[1] : 1;
     oriana_rowrec *rowrec = (oriana_rowrec *)(b + L.rowrec);
     uint8_t *ridx = (uint8_t *)(b + L.ridx);
-    float *s_cs = (float *)(b + L.s_cs), *FU = (float *)(b + L.FU), *FV = (float *)(b + L.FV);
-    float *R = (float *)(b + L.R), *C = (float *)(b + L.C);
+    float *s_cs = (float *)(b + L.s_cs);
     float *w_nz = weighted ? (float *)(b + L.w_nz) : nullptr;
     float *sw_cs = weighted ? (float *)(b + L.sw_cs) : nullptr;
     float *s_rs = sparse ? (float *)(b + L.s_rs) : nullptr;
-    float *F2 = (float *)(b + L.F2), *G2 = (float *)(b + L.G2), *C2 = (float *)(b + L.C2), *dq = nullptr;
     // padding slots: x == 0 records, row index 0, s == 0
     ORIANA_HIP_CHECK(hipMemsetAsync(rowrec, 0, sizeof(oriana_rowrec) * rs1, s));
     ORIANA_HIP_CHECK(hipMemsetAsync(ridx, 0, cs1, s));
@@ -165,50 +163,20 @@ static int zq_dense(float *Zi, float *Zj, float *Zlog, const float *log_U_hat, c
     cm.rslots = tot[0]; cm.cslots = tot[1];
     cm.roff = roff; cm.coff = coff; cm.rslice = rslice; cm.cslice = cslice; cm.rowrec = rowrec; cm.ridx = ridx;
     cm.col_perm = nullptr; cm.row_perm = nullptr;
+    // the nest over the workspace: no dense block, no split, no work lists, no two-image kernels, the fixed den threshold;
+    // the outputs are zeroed above, C / tile_flag / C2 by the preparation's clear list
+    ZqView v;
+    v.cm = &cm; v.n = n; v.m = m; v.K = K; v.Kp = L.Kp;
+    v.FU = (float *)(b + L.FU); v.FV = (float *)(b + L.FV); v.R = (float *)(b + L.R); v.C = (float *)(b + L.C);
+    v.s_cs = s_cs; v.prep = (float *)(b + L.prep); v.tile_flag = tile_flag;
+    v.F2 = (float *)(b + L.F2); v.G2 = v.GQ = (float *)(b + L.G2); v.C2 = (float *)(b + L.C2);
+    v.w_nz = w_nz; v.sw_cs = sw_cs; v.s_rs = s_rs;
     if (quirk) {
-        dq = (float *)(b + L.dq);
-        if ((rc = oriana_take_cols_f32(dq, D_hat, n, m, K, stream))) return rc;
+        v.dq = (float *)(b + L.dq);
+        if ((rc = oriana_take_cols_f32(v.dq, D_hat, n, m, K, stream))) return rc;
     }
-
-    float *prep = (float *)(b + L.prep);
-    ORIANA_HIP_CHECK(hipMemsetAsync(prep, 0, 8 * sizeof(float), s));            // the arrival counter
-    if ((rc = oriana_factor_prep_pair(FU, FV, log_U_hat, log_V_hat, S_tilde, nullptr, nullptr, n, m, K, prep, stream))) return rc;
-    ORIANA_HIP_CHECK(hipMemsetAsync(C, 0, sizeof(float) * m * L.Kp, s));
-    ORIANA_HIP_CHECK(hipMemsetAsync(tile_flag, 0, sizeof(int32_t) * nt, s));
-    if ((rc = oriana_row_pass(&cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, K, stream))) return rc;
-    const int variant = (sparse ? 1 : 0) | (weighted ? 2 : 0) | (dq ? 4 : 0);
-    if ((rc = oriana_fixup(&cm, tile_flag, s_cs, sw_cs, s_rs, log_U_hat, log_V_hat, S_tilde, S_hat, w_nz, dq, Zi, Zj,
-                           Zlog, K, variant, stream))) return rc;
-    if (sparse) {
-        // S_hat-weighted row sums (sparse_gap.py:95): a second row SpMM with FV * S_hat
-        if ((rc = oriana_scale_factor(F2, FV, S_hat, nullptr, m, K, 0, stream))) return rc;
-        if ((rc = oriana_row_spmm(&cm, s_rs, w_nz, F2, R, K, stream))) return rc;
-    }
-    if ((rc = oriana_finalize(Zi, FU, R, nullptr, nullptr, n, K, 1, stream))) return rc;
-    // per-gene sums: weighted by D_hat[i, j] (sw), or -- zigap.py:94 -- by D_hat[i, k] on the plain s
-    const float *G = FU, *s_for_j = sw_cs ? sw_cs : s_cs;
-    if (dq) {
-        if ((rc = oriana_scale_factor(G2, FU, dq, nullptr, n, K, 0, stream))) return rc;
-        G = G2;
-        s_for_j = s_cs;
-    }
-    if ((rc = oriana_col_pass(&cm, s_for_j, G, C, K, nullptr, 0, stream))) return rc;
-    if ((rc = oriana_finalize(Zj, FV, C, nullptr, nullptr, m, K, 1, stream))) return rc;
-    if (Zlog) {
-        // sum_i r_ijk (lu_ik + lv_jk) = FV (sum_i s FU lu) + FV lv (sum_i s FU), D_hat[i, j]-weighted
-        const float *s_log = sw_cs ? sw_cs : s_cs;
-        if (dq) {
-            ORIANA_HIP_CHECK(hipMemsetAsync(C, 0, sizeof(float) * m * L.Kp, s));
-            if ((rc = oriana_col_pass(&cm, s_log, FU, C, K, nullptr, 0, stream))) return rc;
-        }
-        ORIANA_HIP_CHECK(hipMemsetAsync(C2, 0, sizeof(float) * m * L.Kp, s));
-        double *center = (double *)((char *)prep + oriana_prep_center_offset());
-        if ((rc = oriana_log_center(center, FU, log_U_hat, Zi, nullptr, n, K, stream))) return rc;
-        if ((rc = oriana_scale_factor_centered(G2, FU, log_U_hat, center, nullptr, n, K, stream))) return rc;
-        if ((rc = oriana_col_pass(&cm, s_log, G2, C2, K, nullptr, 0, stream))) return rc;
-        if ((rc = oriana_finalize_zlog(Zlog, FV, C2, C, log_V_hat, center, nullptr, m, K, stream))) return rc;
-    }
-    return 0;
+    ORIANA_HIP_CHECK(hipMemsetAsync(v.prep, 0, 8 * sizeof(float), s));            // the arrival counter
+    return zq_run(v, Zi, Zj, Zlog, log_U_hat, log_V_hat, S_tilde, S_hat, nullptr, stream);
 }
 
 extern "C" int oriana_zq_gap_f32(float *Z_hat_i, float *Z_hat_j, const float *log_U_hat, const float *log_V_hat,

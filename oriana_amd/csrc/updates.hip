@@ -6,8 +6,6 @@
 // of oriana/utils.py.  All of it is float64 element-wise work plus column sums: HBM-bound,
 // fused so that each parameter matrix is written once and Z is read once.
 #include "common.h"
-#include <stdlib.h>
-#include <string.h>
 
 namespace oriana {
 
@@ -520,9 +518,24 @@ static bool gu_vec_launch(GuVecArgs a, hipStream_t s) {
 // 2^20 elements on (30,000 x 100: 46 against 60 us), and whenever its PREP outputs are asked for.
 static inline bool gu_small(int64_t r, int64_t K) { return r * K < (int64_t)1 << 20; }
 
-static inline bool gu_scalar_forced() {
-    static const bool f = [] { const char *e = getenv("ORIANA_GU_KERNEL"); return e && !strcmp(e, "r4"); }();   // A/B runs
-    return f;
+// the element-per-lane kernel on the arguments of the vector one
+template <bool FIN>
+static int gu_scalar_launch(const GuVecArgs &a, hipStream_t s) {
+    constexpr int BIG = FIN ? 1024 : 512;            // (the general form needs more than the 128 VGPRs of a 1024-thread group)
+    dim3 block;
+    const bool big = gu_large_groups(a.r);
+    pick_block(a.K, &block, big ? BIG : 256);
+    const int rpb = big ? 4 * (int)block.y : rows_per_block(a.r, (int)block.y);
+    const dim3 grid((unsigned)((a.r + rpb - 1) / rpb));
+    const int Kp = FIN ? a.Kp : 0;
+#define ORIANA_GU(NT) hipLaunchKernelGGL((k_gamma_update<FIN, NT>), grid, block, 0, s, a.a1, a.a2, a.E, a.Elog, a.colsum_E, a.colsum_Elog,    \
+                                         a.prior1, a.prior2, a.Z_in, a.zmul, a.rate_vec, a.rate_mat, a.rmul, a.r, a.K, rpb, a.Zfin, a.F, a.Rs, \
+                                         a.row_index, Kp, a.nslab, a.slab_row0)
+    if (big) ORIANA_GU(BIG);
+    else ORIANA_GU(256);
+#undef ORIANA_GU
+    ORIANA_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace oriana
@@ -531,7 +544,7 @@ using namespace oriana;
 
 extern "C" int64_t oriana_gamma_update_prep_blocks(int64_t r, int64_t K) {
     int vec, lpr;
-    if (r <= 0 || K <= 0 || gu_scalar_forced() || !gu_vec_cfg(K, true, &vec, &lpr)) return 0;
+    if (r <= 0 || K <= 0 || !gu_vec_cfg(K, true, &vec, &lpr)) return 0;
     const int rpb = gu_vec_rpb(r, lpr);
     return (r + rpb - 1) / rpb;
 }
@@ -547,27 +560,11 @@ extern "C" int oriana_gamma_update_prep(double *a1, double *a2, double *E, float
     if (!a1 || !a2 || !E || !Elog) return ORIANA_EINVAL;
     if (Z && (!prior1 || !prior2 || (!rate_vec && !rate_mat))) return ORIANA_EINVAL;
     if (FU_next && (!mu_out || !upart || oriana_kpad(K) == 0)) return ORIANA_EINVAL;
-    if (!gu_scalar_forced() && (FU_next || !gu_small(r, K))) {
-        GuVecArgs a = {a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, zmul, rate_vec, rate_mat, rmul, r, (int)K, 0,
-                       nullptr, nullptr, nullptr, nullptr, (int)oriana_kpad(K), 1, 0, FU_next, mu_out, upart, nullptr};
-        if (gu_vec_launch<false>(a, (hipStream_t)stream)) { ORIANA_LAUNCH_CHECK(); return 0; }
-    }
+    const GuVecArgs a = {a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, zmul, rate_vec, rate_mat, rmul, r, (int)K, 0,
+                         nullptr, nullptr, nullptr, nullptr, (int)oriana_kpad(K), 1, 0, FU_next, mu_out, upart, nullptr};
+    if ((FU_next || !gu_small(r, K)) && gu_vec_launch<false>(a, (hipStream_t)stream)) { ORIANA_LAUNCH_CHECK(); return 0; }
     if (FU_next) return ORIANA_EINVAL;                 // (callers ask oriana_gamma_update_prep_blocks first)
-    dim3 block;
-    const bool big = gu_large_groups(r);
-    pick_block(K, &block, big ? 512 : 256);          // (the general form needs more than the 128 VGPRs of a 1024-thread group)
-    const int rpb = big ? 4 * (int)block.y : rows_per_block(r, (int)block.y);
-    const int64_t nblk = (r + rpb - 1) / rpb;
-    if (big)
-        hipLaunchKernelGGL((k_gamma_update<false, 512>), dim3((unsigned)nblk), block, 0, (hipStream_t)stream, a1, a2, E, Elog,
-                           colsum_E, colsum_Elog, prior1, prior2, Z, zmul, rate_vec, rate_mat, rmul, r, (int)K, rpb,
-                           (float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const int32_t *)nullptr, 0, 1, (int64_t)0);
-    else
-        hipLaunchKernelGGL((k_gamma_update<false, 256>), dim3((unsigned)nblk), block, 0, (hipStream_t)stream, a1, a2, E, Elog,
-                           colsum_E, colsum_Elog, prior1, prior2, Z, zmul, rate_vec, rate_mat, rmul, r, (int)K, rpb,
-                           (float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const int32_t *)nullptr, 0, 1, (int64_t)0);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return gu_scalar_launch<false>(a, (hipStream_t)stream);
 }
 
 extern "C" int oriana_gamma_update(double *a1, double *a2, double *E, float *Elog, double *colsum_E,
@@ -589,27 +586,11 @@ extern "C" int oriana_gamma_update_finalize_prep(double *a1, double *a2, double 
     if (r == 0) return 0;
     if (!a1 || !a2 || !E || !Elog || !Z || !F || !R || !prior1 || !prior2 || !rate_vec) return ORIANA_EINVAL;
     if (FU_next && (!mu_out || !upart)) return ORIANA_EINVAL;
-    if (!gu_scalar_forced() && (FU_next || !gu_small(r, K))) {
-        GuVecArgs a = {a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, nullptr, nullptr, rate_vec, nullptr, nullptr, r, (int)K, 0,
-                       Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0, FU_next, mu_out, upart, nullptr};
-        if (gu_vec_launch<true>(a, (hipStream_t)stream)) { ORIANA_LAUNCH_CHECK(); return 0; }
-    }
+    const GuVecArgs a = {a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, nullptr, nullptr, rate_vec, nullptr, nullptr, r, (int)K, 0,
+                         Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0, FU_next, mu_out, upart, nullptr};
+    if ((FU_next || !gu_small(r, K)) && gu_vec_launch<true>(a, (hipStream_t)stream)) { ORIANA_LAUNCH_CHECK(); return 0; }
     if (FU_next) return ORIANA_EINVAL;
-    dim3 block;
-    const bool big = gu_large_groups(r);
-    pick_block(K, &block, big ? 1024 : 256);
-    const int rpb = big ? 4 * (int)block.y : rows_per_block(r, (int)block.y);
-    const int64_t nblk = (r + rpb - 1) / rpb;
-    if (big)
-        hipLaunchKernelGGL((k_gamma_update<true, 1024>), dim3((unsigned)nblk), block, 0, (hipStream_t)stream, a1, a2, E, Elog,
-                           colsum_E, colsum_Elog, prior1, prior2, (const float *)nullptr, (const float *)nullptr, rate_vec,
-                           (const double *)nullptr, (const float *)nullptr, r, (int)K, rpb, Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0);
-    else
-        hipLaunchKernelGGL((k_gamma_update<true, 256>), dim3((unsigned)nblk), block, 0, (hipStream_t)stream, a1, a2, E, Elog,
-                           colsum_E, colsum_Elog, prior1, prior2, (const float *)nullptr, (const float *)nullptr, rate_vec,
-                           (const double *)nullptr, (const float *)nullptr, r, (int)K, rpb, Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return gu_scalar_launch<true>(a, (hipStream_t)stream);
 }
 
 // [r6] pCMF's cell side without the two matrices nobody reads inside a sweep (gap.py:98, 101): a2 is the same K numbers in
@@ -627,7 +608,7 @@ extern "C" int oriana_gamma_update_finalize_lazy(double *a1, double *a2_row, flo
     if (!a1 || !a2_row || !Elog || !Z || !F || !R || !prior1 || !prior2 || !rate_vec) return ORIANA_EINVAL;
     if (FU_next && (!mu_out || !upart)) return ORIANA_EINVAL;
     if (r == 0) return ORIANA_EKRANGE;                 // (nothing would write a2_row)
-    if (gu_scalar_forced() || (!FU_next && gu_small(r, K))) return ORIANA_EKRANGE;     // (launch-bound sizes: the scalar kernel)
+    if (!FU_next && gu_small(r, K)) return ORIANA_EKRANGE;     // (launch-bound sizes: the scalar kernel)
     GuVecArgs a = {a1, nullptr, nullptr, Elog, colsum_E, colsum_Elog, prior1, prior2, nullptr, nullptr, rate_vec, nullptr, nullptr, r, (int)K, 0,
                    Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0, FU_next, mu_out, upart, a2_row};
     if (!gu_vec_launch<true>(a, (hipStream_t)stream)) return ORIANA_EKRANGE;
@@ -635,20 +616,12 @@ extern "C" int oriana_gamma_update_finalize_lazy(double *a1, double *a2_row, flo
     return 0;
 }
 
-extern "C" int oriana_gamma_update_finalize_from(double *a1, double *a2, double *E, float *Elog, double *colsum_E,
-                                            double *colsum_Elog, const double *prior1, const double *prior2, float *Z,
-                                            const float *F, const float *R, int64_t nslab, int64_t slab_row0, const int32_t *row_index,
-                                            const double *rate_vec, int64_t r, int64_t K, void *stream) {
-    return oriana_gamma_update_finalize_prep(a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, F, R, nslab, slab_row0, row_index,
-                                             rate_vec, r, K, nullptr, nullptr, nullptr, stream);
-}
-
 extern "C" int oriana_gamma_update_finalize(double *a1, double *a2, double *E, float *Elog, double *colsum_E,
                                             double *colsum_Elog, const double *prior1, const double *prior2, float *Z,
                                             const float *F, const float *R, int64_t nslab, const int32_t *row_index,
                                             const double *rate_vec, int64_t r, int64_t K, void *stream) {
-    return oriana_gamma_update_finalize_from(a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, F, R, nslab, 0, row_index,
-                                             rate_vec, r, K, stream);
+    return oriana_gamma_update_finalize_prep(a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, F, R, nslab, 0, row_index,
+                                             rate_vec, r, K, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int oriana_colsum_f64(double *out, const double *A, const float *mul, int64_t r, int64_t K, void *stream) {

@@ -883,7 +883,7 @@ def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=N
         # pass leaves s in row-side slots and a second row product follows.
         fused = False
         F2 = None
-        gs = ws.row_gene_splits                     # gene ranges per row block (slabs of R), see oriana_row_pass_gene_splits
+        gs = ws.row_gene_splits                     # gene ranges per row block (slabs of R), see oriana_row_pass_plan
         nslab = 1
         if sparse:
             F2 = ws.extra('FVS', m)
