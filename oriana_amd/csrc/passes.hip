@@ -20,6 +20,7 @@
 #include "common.h"
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 // (the ablation switches of rounds 1-4 -- no barriers, no scattered s stores, masked padding slots, rotation variants, staging
 //  once, staggered waves -- are archived as tools/experiments/passes_ablation_switches_r4.diff)
@@ -33,9 +34,12 @@
 namespace oriana {
 
 // ------------------------------------------------------------------------------------------
-// dispatch on K:  Kp = 4 * G * T4
+// dispatch on K:  Kp = 4 * G * T4 (+ G * TAIL)
 // ------------------------------------------------------------------------------------------
-struct KCfg { int G, T4, TAIL; };
+struct KCfg {
+    int G, T4, TAIL;
+    constexpr int kp() const { return 4 * G * T4 + G * TAIL; }
+};
 // Kp = 16 t (+4): the smallest padded width that holds K.  The tail (one extra float per lane)
 // keeps K = 20, 50, 100 ... free of padding work.
 static inline bool pick_cfg(int64_t K, KCfg *c) {
@@ -52,52 +56,83 @@ static inline bool pick_cfg(int64_t K, KCfg *c) {
     return false;
 }
 
-#define ORIANA_FOR_CFG(cfg, CALL)                                                       \
-    do {                                                                                \
-        if (cfg.G == 4 && cfg.T4 == 1 && cfg.TAIL == 0) { CALL(4, 1, 0); }              \
-        else if (cfg.G == 4 && cfg.T4 == 1 && cfg.TAIL == 1) { CALL(4, 1, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 2 && cfg.TAIL == 0) { CALL(4, 2, 0); }         \
-        else if (cfg.G == 4 && cfg.T4 == 2 && cfg.TAIL == 1) { CALL(4, 2, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 3 && cfg.TAIL == 0) { CALL(4, 3, 0); }         \
-        else if (cfg.G == 4 && cfg.T4 == 3 && cfg.TAIL == 1) { CALL(4, 3, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 4 && cfg.TAIL == 0) { CALL(4, 4, 0); }         \
-        else if (cfg.G == 4 && cfg.T4 == 4 && cfg.TAIL == 1) { CALL(4, 4, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 5 && cfg.TAIL == 0) { CALL(4, 5, 0); }         \
-        else if (cfg.G == 4 && cfg.T4 == 5 && cfg.TAIL == 1) { CALL(4, 5, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 6 && cfg.TAIL == 0) { CALL(4, 6, 0); }         \
-        else if (cfg.G == 4 && cfg.T4 == 6 && cfg.TAIL == 1) { CALL(4, 6, 1); }         \
-        else if (cfg.G == 4 && cfg.T4 == 7 && cfg.TAIL == 0) { CALL(4, 7, 0); }         \
-        else if (cfg.G == 8 && cfg.T4 == 4) { CALL(8, 4, 0); }                          \
-        else if (cfg.G == 8 && cfg.T4 == 5) { CALL(8, 5, 0); }                          \
-        else if (cfg.G == 8 && cfg.T4 == 6) { CALL(8, 6, 0); }                          \
-        else if (cfg.G == 8 && cfg.T4 == 7) { CALL(8, 7, 0); }                          \
-        else if (cfg.G == 16 && cfg.T4 == 4) { CALL(16, 4, 0); }                        \
-        else return ORIANA_EKRANGE;                                                     \
-    } while (0)
+// run-time configuration -> template arguments: the 18 configurations pick_cfg can return, by Kp / 4
+#define ORIANA_FOR_CFG(cfg, CALL)                                                                                         \
+    switch ((cfg).kp() / 4) {                                                                                             \
+    case 4: CALL(4, 1, 0);   case 5: CALL(4, 1, 1);   case 8: CALL(4, 2, 0);   case 9: CALL(4, 2, 1);                     \
+    case 12: CALL(4, 3, 0);  case 13: CALL(4, 3, 1);  case 16: CALL(4, 4, 0);  case 17: CALL(4, 4, 1);                    \
+    case 20: CALL(4, 5, 0);  case 21: CALL(4, 5, 1);  case 24: CALL(4, 6, 0);  case 25: CALL(4, 6, 1);                    \
+    case 28: CALL(4, 7, 0);  case 32: CALL(8, 4, 0);  case 40: CALL(8, 5, 0);  case 48: CALL(8, 6, 0);                    \
+    case 56: CALL(8, 7, 0);  case 64: CALL(16, 4, 0);                                                                     \
+    default: return ORIANA_EKRANGE;                                                                                       \
+    }
 
-// Which family serves which padded width (one answer per configuration; DESIGN.md section 0 has the table per model):
-//   row pass     Kp <= 32, plain variant ......... narrow  (one lane per row)
-//                Kp = 36, 48, 52, 64 ............. k64     (two lanes per row; every variant)
-//                Kp = 96, 100 ................... k100    (two lanes per row; no second image: two do not fit in LDS)
-//                everything else ................ generic (G lanes per row): Kp <= 32 with weights / row-side s / a second
-//                                                 image, Kp = 68, 80, 84, 112 .. 256
-//   column pass  Kp <= 20 ....................... narrow  (one lane per gene)
-//                Kp = 36 .. 64 .................. k64     (two lanes per gene, two column tiles per image)
-//                other Kp <= 112 (G = 4) ........ k_col_pass2 (four lanes per gene, two column tiles per image)
-//                Kp >= 128 (G = 8, 16) .......... generic
+// run-time variant -> template argument: f(std::integral_constant<int, v>) for the v of the list, ORIANA_EINVAL for any other
+template <int... Vs, typename F>
+static int with_variant(int v, F &&f) {
+    int rc = ORIANA_EINVAL;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Which kernel family serves which configuration.  These functions are the whole rule: the launchers below name a kernel
+// template only under `if constexpr` on their answers (what is compiled is what can be launched), the planning entries
+// (oriana_row_pass_plan_cus, oriana_col_block_tiles) ask them too, and DESIGN.md section 0 shows them as a table per model.
 // (rounds 1-4 selected older generations with ORIANA_PASS_IMPL=r1|r2|r3 for A/B runs: gone; the git history has them)
-static constexpr bool use_narrow(int G, int T4, int TAIL) { return G == 4 && 4 * T4 + TAIL <= 8; }       // row pass: Kp <= 32
-// (column pass: Kp <= 20 -- at Kp = 32 the two-tile kernel measured 26.0 us against 28.3 at 10,000 x 2,000)
-static constexpr bool use_narrow_col(int G, int T4, int TAIL) { return G == 4 && 4 * T4 + TAIL <= 5; }
-static constexpr bool use_k100(int G, int T4) { return G == 4 && T4 == 6; }
-static constexpr bool k64_kernels() { return true; }
+// ------------------------------------------------------------------------------------------
+enum class Fam {
+    none,       // no kernel: the entry answers ORIANA_EKRANGE ("not this form's case") and the caller takes its other form
+    narrow,     // passes_narrow.h: one lane per row / gene
+    k64,        // passes_k64.h: two lanes per row / gene, rows zero-padded to 64 floats
+    k100,       // passes_k100.h, k_row_pass_k100: two lanes per row, duplicated chunk groups
+    col2,       // passes_k100.h, k_col_pass2: four lanes per gene; two column tiles per image, or (DUAL) two images of one tile
+    generic     // passes_generic.h: G lanes per row / gene
+};
+// row-pass variant = the VAR argument of the row kernels (bits 0 and 2 exclude each other: oriana_row_pass_general)
+constexpr int V_SROW = 1, V_WEIGHTS = 2, V_IMAGE2 = 4;
+enum class Col { plain, partials, dual };       // C += s G;  the same into per-item slabs (Cpart);  two products from one walk
+
+// one staged image of 256 factor rows for the generic kernels (rows padded to 256 bytes; column sub-tiles above 160 KB)
+static constexpr size_t lds_bytes(KCfg c) { return (size_t)(TILE / pick_nsub(c.kp())) * lds_stride_floats(c.kp()) * sizeof(float); }
+
+static constexpr Fam row_family(KCfg c, int V) {
+    const int kp = c.kp();
+    if (kp >= 36 && kp <= 64) return Fam::k64;                   // every variant; a second image is a second 64 KB
+    if (V & V_IMAGE2)                                            // two images side by side, whole tiles: Kp <= 32 of what is left
+        return (pick_nsub(kp) == 1 && 2 * lds_bytes(c) <= (size_t)LDS_BUDGET) ? Fam::generic : Fam::none;      // (Kp > 64: one image is 128 KB)
+    if (kp <= 32 && V == 0) return Fam::narrow;                  // the plain variant only
+    if (kp == 96 || kp == 100) return Fam::k100;
+    return Fam::generic;      // Kp <= 32 with weights / row-side s, Kp = 68, 80, 84, 112 .. 256
+}
+// The two-lane families run one 512-thread work-group per work item: a whole row block, or one gene range of a split one
+// (k100::row_item: any oriana_row_split, the last-round form with explicit edges included).  The others take a grid of
+// (work-groups of the row blocks, parts): whole-grid splits only, cut evenly by the kernel.
+static constexpr bool takes_row_items(Fam f) { return f == Fam::k64 || f == Fam::k100; }
+static constexpr int row_groups_per_block(Fam f, int G) { return f == Fam::generic ? TILE / (16 * (64 / G)) : 1; }
+
+static constexpr Fam col_family(KCfg c, Col mode) {
+    const int kp = c.kp();
+    if (mode == Col::dual)                                       // two plain images of a four-lane configuration: Kp <= 64
+        return (c.G == 4 && c.T4 != 6 && 2 * lds_bytes(c) <= (size_t)LDS_BUDGET) ? Fam::col2 : Fam::none;
+    // (33 <= Kp <= 64: the two-lane dual kernel k64::k_col_pass_k64<KP4, true> measured 11.3 ms against 10.9 ms for the four-lane
+    //  one at configs[4] -- with two images per step the walk is bound by the LDS return port either way; it is not dispatched)
+    // (narrow up to Kp = 20 only: at Kp = 32 the two-tile kernel measured 26.0 us against 28.3 at 10,000 x 2,000)
+    if (kp <= 20) return mode == Col::plain ? Fam::narrow : Fam::generic;      // (the narrow kernel writes no partials)
+    if (c.G != 4) return Fam::generic;                           // Kp >= 128
+    return (kp >= 36 && kp <= 64) ? Fam::k64 : Fam::col2;
+}
+// column tiles per work item (and per grid.x index) of the plain and the partials form; a dual item is one tile
+static constexpr int col_tiles_per_item(KCfg c) {
+    const Fam f = col_family(c, Col::plain);
+    return (f == Fam::k64 || f == Fam::col2) ? 2 : 1;
+}
+
 // ORIANA_DEN_THRESHOLD=fixed: the row kernels keep the constant DEN_MIN (round 3's rule; A/B runs)
 static bool den_threshold_dynamic() {
     static const bool fixed = [] { const char *e = getenv("ORIANA_DEN_THRESHOLD"); return e && !strcmp(e, "fixed"); }();
     return !fixed;
 }
-static constexpr bool k64_cfg(int G, int T4, int TAIL) { return G == 4 && 4 * T4 + TAIL >= 9 && 4 * T4 + TAIL <= 16; }
-static constexpr bool use_col2(int G, int T4, int TAIL) { return G == 4 && !use_narrow_col(G, T4, TAIL); }   // column pass, two tiles per image
 
 template <typename KernelT>
 static int set_lds(KernelT kern, size_t bytes) {
@@ -109,227 +144,103 @@ static int set_lds(KernelT kern, size_t bytes) {
     return 0;
 }
 
-static inline size_t lds_bytes(int G, int T4, int TAIL) {
-    const int KP = 4 * G * T4 + G * TAIL;
-    return (size_t)(TILE / pick_nsub(KP)) * lds_stride_floats(KP) * sizeof(float);
-}
-
-template <int G, int T4, int TAIL>
-static int launch_row_pass(const oriana_counts *cm, const float *FU, const float *FV, const float *w_nz, float *R,
-                           float *s_cs, float *sw_cs, float *s_rs, int32_t *tile_flag, hipStream_t s,
-                           const float *FV2, const oriana_row_split &sp, const float *den_min = nullptr) {
-    const int var = (s_rs ? 1 : 0) | (w_nz ? 2 : 0);
-    int rc;
-    // two-lane kernels: one group per full row block, then the parts of the split ones (row_item)
-    const int64_t items = (int64_t)sp.nfull + (cm->nrb - sp.nfull) * sp.parts;
-    if (items > 0x7fffffffLL) return ORIANA_EINVAL;
-    if constexpr (k64_cfg(G, T4, TAIL)) {
-        if (k64_kernels() && !(FV2 && s_rs)) {
-            constexpr int KP4 = 4 * T4 + TAIL;
-            const size_t lb6 = (size_t)k64::IMG4 * 16 * (FV2 ? 2 : 1);
-            const dim3 grid6((unsigned)items);
-#define ORIANA_RP6(V)                                                                                 \
-            rc = set_lds(k64::k_row_pass_k64<KP4, V>, lb6);                                           \
-            if (rc) return rc;                                                                        \
-            hipLaunchKernelGGL((k64::k_row_pass_k64<KP4, V>), grid6, dim3(512), lb6, s, *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, FV2, sp, den_min)
-            const int v6 = var | (FV2 ? 4 : 0);
-            if (v6 == 0) { ORIANA_RP6(0); }
-            else if (v6 == 1) { ORIANA_RP6(1); }
-            else if (v6 == 2) { ORIANA_RP6(2); }
-            else if (v6 == 3) { ORIANA_RP6(3); }
-            else if (v6 == 4) { ORIANA_RP6(4); }
-            else { ORIANA_RP6(6); }
-#undef ORIANA_RP6
-            ORIANA_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    // every other kernel: whole-grid split only, ranges cut evenly by the kernel (gridDim.y)
-    const bool whole_grid = sp.nfull == 0 || sp.parts == 1;
-    const int gene_splits = sp.parts;
-    if (FV2) {
-        // two images of 256 factor rows side by side: only where both fit (and the tile needs no column sub-tiles)
-        constexpr int KP = 4 * G * T4 + G * TAIL;
-        const size_t lb2 = 2 * lds_bytes(G, T4, TAIL);
-        if (use_k100(G, T4) || pick_nsub(KP) != 1 || lb2 > (size_t)LDS_BUDGET) return ORIANA_EKRANGE;
-        if (!whole_grid) return ORIANA_EINVAL;
-        const dim3 grid2((unsigned)(cm->nrb * WaveGeo<G>::SPLIT), (unsigned)gene_splits), block2(1024);
-        if (w_nz) {
-            rc = set_lds(k_row_pass<G, T4, TAIL, 6>, lb2);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_row_pass<G, T4, TAIL, 6>), grid2, block2, lb2, s, *cm, FU, FV, w_nz, R, s_cs, sw_cs, nullptr, tile_flag, FV2, den_min);
-        } else {
-            rc = set_lds(k_row_pass<G, T4, TAIL, 4>, lb2);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_row_pass<G, T4, TAIL, 4>), grid2, block2, lb2, s, *cm, FU, FV, w_nz, R, s_cs, sw_cs, nullptr, tile_flag, FV2, den_min);
-        }
-        ORIANA_LAUNCH_CHECK();
-        return 0;
-    }
-    if (!use_k100(G, T4) && !whole_grid) return ORIANA_EINVAL;
-    if constexpr (G == 4 && 4 * T4 + TAIL <= 8) {
-        if (use_narrow(G, T4, TAIL) && var == 0) {
-            constexpr int KP = 4 * G * T4 + G * TAIL;
-            hipLaunchKernelGGL((narrow::k_row_pass_narrow<KP>), dim3((unsigned)cm->nrb, (unsigned)gene_splits), dim3(256),
-                               narrow::Geo<KP>::bytes(), s, *cm, FU, FV, R, s_cs, tile_flag, den_min);
-            ORIANA_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (use_k100(G, T4)) {
-        constexpr int TL = (G == 4 && T4 == 6) ? TAIL : 0;
-        const size_t lb2 = k100::image_bytes(TL);
-#define ORIANA_RP2(V)                                                                                 \
-        rc = set_lds(k100::k_row_pass_k100<TL, V>, lb2);                                              \
-        if (rc) return rc;                                                                            \
-        hipLaunchKernelGGL((k100::k_row_pass_k100<TL, V>), dim3((unsigned)items), dim3(512), lb2, s, *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, sp, den_min)
-        if (var == 0) { ORIANA_RP2(0); }
-        else if (var == 1) { ORIANA_RP2(1); }
-        else if (var == 2) { ORIANA_RP2(2); }
-        else { ORIANA_RP2(3); }
-#undef ORIANA_RP2
-        ORIANA_LAUNCH_CHECK();
-        return 0;
-    }
-    const dim3 grid((unsigned)(cm->nrb * WaveGeo<G>::SPLIT), (unsigned)gene_splits), block(1024);
-    const size_t lb = lds_bytes(G, T4, TAIL);
-#define ORIANA_RP(V)                                                                                  \
-    rc = set_lds(k_row_pass<G, T4, TAIL, V>, lb);                                                           \
-    if (rc) return rc;                                                                                \
-    hipLaunchKernelGGL((k_row_pass<G, T4, TAIL, V>), grid, block, lb, s, *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, (const float *)nullptr, den_min)
-    if (var == 0) { ORIANA_RP(0); }
-    else if (var == 1) { ORIANA_RP(1); }
-    else if (var == 2) { ORIANA_RP(2); }
-    else { ORIANA_RP(3); }
-#undef ORIANA_RP
+// set_lds, then the launch; the arguments convert to the kernel's parameter types (nullptr, 0)
+template <typename... P, typename... A>
+static int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args) {
+    const int rc = set_lds(kern, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<P>(args)...);
     ORIANA_LAUNCH_CHECK();
     return 0;
+}
+
+template <int G, int T4, int TAIL, int V>
+static int launch_row_pass(const oriana_counts *cm, const float *FU, const float *FV, const float *w_nz, float *R,
+                           float *s_cs, float *sw_cs, float *s_rs, int32_t *tile_flag, hipStream_t s,
+                           const float *FV2, const oriana_row_split &sp, const float *den_min) {
+    constexpr KCfg c{G, T4, TAIL};
+    constexpr Fam F = row_family(c, V);
+    constexpr int KP = c.kp();
+    // one item per full row block, then the parts of the split ones
+    const int64_t items = (int64_t)sp.nfull + (cm->nrb - sp.nfull) * sp.parts;
+    if (items > 0x7fffffffLL) return ORIANA_EINVAL;
+    if constexpr (F == Fam::none) {
+        return ORIANA_EKRANGE;
+    } else if constexpr (F == Fam::k64) {
+        return launch(k64::k_row_pass_k64<KP / 4, V>, dim3((unsigned)items), dim3(512), (size_t)k64::IMG4 * 16 * ((V & V_IMAGE2) ? 2 : 1), s,
+                      *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, FV2, sp, den_min);
+    } else if constexpr (F == Fam::k100) {
+        return launch(k100::k_row_pass_k100<TAIL, V>, dim3((unsigned)items), dim3(512), (size_t)k100::image_bytes(TAIL), s,
+                      *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, sp, den_min);
+    } else {
+        static_assert(!takes_row_items(F) && row_groups_per_block(F, G) == (F == Fam::generic ? WaveGeo<G>::SPLIT : 1), "");
+        if (!(sp.nfull == 0 || sp.parts == 1)) return ORIANA_EINVAL;
+        const dim3 grid((unsigned)(cm->nrb * row_groups_per_block(F, G)), (unsigned)sp.parts);
+        if constexpr (F == Fam::narrow)
+            return launch(narrow::k_row_pass_narrow<KP>, grid, dim3(256), narrow::Geo<KP>::bytes(), s, *cm, FU, FV, R, s_cs, tile_flag, den_min);
+        else
+            return launch(k_row_pass<G, T4, TAIL, V>, grid, dim3(1024), lds_bytes(c) * ((V & V_IMAGE2) ? 2 : 1), s,
+                          *cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, FV2, den_min);
+    }
 }
 
 template <int G, int T4, int TAIL>
 static int launch_row_spmm(const oriana_counts *cm, const float *s_rs, const float *w_nz, const float *FV,
                            float *R, hipStream_t s) {
-    const dim3 grid((unsigned)(cm->nrb * WaveGeo<G>::SPLIT)), block(1024);
-    const size_t lb = lds_bytes(G, T4, TAIL);
-    int rc;
-    if (w_nz) {
-        rc = set_lds(k_row_spmm<G, T4, TAIL, true>, lb); if (rc) return rc;
-        hipLaunchKernelGGL((k_row_spmm<G, T4, TAIL, true>), grid, block, lb, s, *cm, s_rs, w_nz, FV, R);
-    } else {
-        rc = set_lds(k_row_spmm<G, T4, TAIL, false>, lb); if (rc) return rc;
-        hipLaunchKernelGGL((k_row_spmm<G, T4, TAIL, false>), grid, block, lb, s, *cm, s_rs, w_nz, FV, R);
-    }
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return with_variant<0, 1>(w_nz ? 1 : 0, [&](auto HASW) {
+        return launch(k_row_spmm<G, T4, TAIL, decltype(HASW)::value != 0>, dim3((unsigned)(cm->nrb * WaveGeo<G>::SPLIT)), dim3(1024),
+                      lds_bytes(KCfg{G, T4, TAIL}), s, *cm, s_rs, w_nz, FV, R);
+    });
 }
 
-template <int G, int T4, int TAIL>
-static int launch_col_pass(const oriana_counts *cm, const float *s_cs, const float *Gm, float *C,
-                           const int32_t *work, int64_t nwork, float *Cpart, hipStream_t s) {
-    constexpr int SPLIT = WaveGeo<G>::SPLIT;
-    if constexpr (G == 4 && 4 * T4 + TAIL <= 5) {
-        if (use_narrow_col(G, T4, TAIL) && !Cpart) {
-            // one column tile per work item (oriana_col_block_tiles = 1)
-            constexpr int KP = 4 * G * T4 + G * TAIL;
-            auto kern = narrow::k_col_pass_narrow<KP>;
-            const size_t lbn = narrow::Geo<KP>::bytes();
-            if (work) {
-                if (nwork <= 0) return 0;
-                hipLaunchKernelGGL(kern, dim3((unsigned)nwork), dim3(256), lbn, s, *cm, s_cs, Gm, C, work, (int64_t)0);
-            } else {
-                int64_t nb = (2048 + cm->ncb - 1) / cm->ncb;
-                const int64_t maxb = (cm->nrb + 3) / 4;
-                if (nb > maxb) nb = maxb;
-                if (nb < 1) nb = 1;
-                if (nb > 65535) nb = 65535;
-                const int64_t per = (cm->nrb + nb - 1) / nb;
-                nb = (cm->nrb + per - 1) / per;
-                hipLaunchKernelGGL(kern, dim3((unsigned)cm->ncb, (unsigned)nb), dim3(256), lbn, s, *cm, s_cs, Gm, C,
-                                   (const int32_t *)nullptr, per);
-            }
-            ORIANA_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if constexpr (k64_cfg(G, T4, TAIL)) {
-        if (k64_kernels() && use_col2(G, T4, TAIL)) {
-            // work items / grid.x index PAIRS of column tiles, as for k_col_pass2
-            constexpr int KP4 = 4 * T4 + TAIL;
-            const size_t lb6 = (size_t)k64::IMG4 * 16;
-            auto kern6 = k64::k_col_pass_k64<KP4, false>;
-            int rc6 = set_lds(kern6, lb6);
-            if (rc6) return rc6;
-            if (work) {
-                if (nwork <= 0) return 0;
-                hipLaunchKernelGGL(kern6, dim3((unsigned)nwork), dim3(1024), lb6, s, *cm, s_cs, Gm, C, work, (int64_t)0, Cpart,
-                                   (const float *)nullptr, (float *)nullptr);
-            } else {
-                const int64_t ncp = (cm->ncb + 1) / 2;
-                int64_t nb = (1024 + ncp - 1) / ncp;
-                const int64_t maxb = (cm->nrb + 7) / 8;
-                if (nb > maxb) nb = maxb;
-                if (nb < 1) nb = 1;
-                if (nb > 65535) nb = 65535;
-                const int64_t per = (cm->nrb + nb - 1) / nb;
-                nb = (cm->nrb + per - 1) / per;
-                hipLaunchKernelGGL(kern6, dim3((unsigned)ncp, (unsigned)nb), dim3(1024), lb6, s, *cm, s_cs, Gm, C,
-                                   (const int32_t *)nullptr, per, (float *)nullptr, (const float *)nullptr, (float *)nullptr);
-            }
-            ORIANA_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (use_col2(G, T4, TAIL)) {
-        // work items / grid.x index PAIRS of column tiles (oriana_col_block_tiles = 2)
-        constexpr int T4c = (G == 4) ? T4 : 1, TLc = (G == 4) ? TAIL : 0;       // (only instantiated for G = 4)
-        const size_t lb2 = ColImage<T4c, TLc>::bytes();
-        auto kern = k_col_pass2<T4c, TLc, false>;
-        int rc2 = set_lds(kern, lb2);
-        if (rc2) return rc2;
-        if (work) {
-            if (nwork <= 0) return 0;
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwork), dim3(1024), lb2, s, *cm, s_cs, Gm, C, work, (int64_t)0, Cpart,
-                               (const float *)nullptr, (float *)nullptr);
-        } else {
-            const int64_t ncp = (cm->ncb + 1) / 2;
-            int64_t nb = (1024 + ncp - 1) / ncp;
-            const int64_t maxb = (cm->nrb + 7) / 8;
-            if (nb > maxb) nb = maxb;
-            if (nb < 1) nb = 1;
-            if (nb > 65535) nb = 65535;
-            const int64_t per = (cm->nrb + nb - 1) / nb;
-            nb = (cm->nrb + per - 1) / per;
-            hipLaunchKernelGGL(kern, dim3((unsigned)ncp, (unsigned)nb), dim3(1024), lb2, s, *cm, s_cs, Gm, C,
-                               (const int32_t *)nullptr, per, (float *)nullptr, (const float *)nullptr, (float *)nullptr);
-        }
-        ORIANA_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lbw = lds_bytes(G, T4, TAIL);
-    if (work) {
-        if (nwork <= 0) return 0;
-        int rcw = set_lds(k_col_pass<G, T4, TAIL>, lbw);
-        if (rcw) return rcw;
-        hipLaunchKernelGGL((k_col_pass<G, T4, TAIL>), dim3((unsigned)(nwork * SPLIT)), dim3(1024), lbw, s, *cm, s_cs, Gm, C,
-                           work, (int64_t)0, Cpart);
-        ORIANA_LAUNCH_CHECK();
-        return 0;
-    }
-    // enough row bands to fill the chip (>= ~1024 workgroups) without shrinking a band below 8 tiles
-    int64_t nb = (1024 + cm->ncb * SPLIT - 1) / (cm->ncb * SPLIT);
-    int64_t maxb = (cm->nrb + 7) / 8;
+// Grid of the column pass without a work list: (col_groups, row bands), enough bands to fill the chip (~target work-groups)
+// without shrinking a band below min_band row blocks.
+struct Bands { int64_t nb, per; };
+static Bands band_grid(const oriana_counts *cm, int64_t col_groups, int64_t target, int64_t min_band) {
+    int64_t nb = (target + col_groups - 1) / col_groups;
+    const int64_t maxb = (cm->nrb + min_band - 1) / min_band;
     if (nb > maxb) nb = maxb;
     if (nb < 1) nb = 1;
     if (nb > 65535) nb = 65535;
     const int64_t per = (cm->nrb + nb - 1) / nb;
-    nb = (cm->nrb + per - 1) / per;
-    const dim3 grid((unsigned)(cm->ncb * SPLIT), (unsigned)nb), block(1024);
-    const size_t lb = lds_bytes(G, T4, TAIL);
-    int rc = set_lds(k_col_pass<G, T4, TAIL>, lb);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_col_pass<G, T4, TAIL>), grid, block, lb, s, *cm, s_cs, Gm, C, (const int32_t *)nullptr, per, (float *)nullptr);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return {(cm->nrb + per - 1) / per, per};
+}
+
+// work items (work != NULL: nwork triples of width col_tiles_per_item, or width 1 for the dual form) or a band grid
+template <int G, int T4, int TAIL, Col MODE>
+static int launch_col_pass(const oriana_counts *cm, const float *s_cs, const float *Gm, float *C, const int32_t *work,
+                           int64_t nwork, float *Cpart, const float *Gm2, float *C2, hipStream_t s) {
+    constexpr KCfg c{G, T4, TAIL};
+    constexpr Fam F = col_family(c, MODE);
+    if constexpr (F == Fam::none) {
+        return ORIANA_EKRANGE;
+    } else {
+        static_assert(MODE == Col::dual || col_tiles_per_item(c) == ((F == Fam::k64 || F == Fam::col2) ? 2 : 1), "plain and partials share work lists");
+        if (work && nwork <= 0) return 0;
+        constexpr int KP = c.kp();
+        constexpr int SPLIT = F == Fam::generic ? WaveGeo<G>::SPLIT : 1;        // work-groups per item
+        dim3 grid((unsigned)(nwork * SPLIT));
+        int64_t per = 0;
+        if (!work) {
+            const int64_t col_groups = (cm->ncb + col_tiles_per_item(c) - 1) / col_tiles_per_item(c) * SPLIT;
+            const Bands b = F == Fam::narrow ? band_grid(cm, col_groups, 2048, 4) : band_grid(cm, col_groups, 1024, 8);
+            grid = dim3((unsigned)col_groups, (unsigned)b.nb);
+            per = b.per;
+        }
+        if constexpr (F == Fam::narrow) {
+            return launch(narrow::k_col_pass_narrow<KP>, grid, dim3(256), narrow::Geo<KP>::bytes(), s, *cm, s_cs, Gm, C, work, per);
+        } else if constexpr (F == Fam::k64) {
+            return launch(k64::k_col_pass_k64<KP / 4, false>, grid, dim3(1024), (size_t)k64::IMG4 * 16, s,
+                          *cm, s_cs, Gm, C, work, per, Cpart, nullptr, nullptr);
+        } else if constexpr (F == Fam::col2) {
+            constexpr bool DUAL = MODE == Col::dual;
+            static_assert(!DUAL || 2 * ColImage<T4, TAIL>::bytes() <= (size_t)LDS_BUDGET, "");
+            return launch(k_col_pass2<T4, TAIL, DUAL>, grid, dim3(1024), ColImage<T4, TAIL>::bytes() * (DUAL ? 2 : 1), s,
+                          *cm, s_cs, Gm, C, work, per, Cpart, Gm2, C2);
+        } else {
+            return launch(k_col_pass<G, T4, TAIL>, grid, dim3(1024), lds_bytes(c), s, *cm, s_cs, Gm, C, work, per, Cpart);
+        }
+    }
 }
 
 }  // namespace oriana
@@ -339,7 +250,7 @@ using namespace oriana;
 extern "C" int64_t oriana_kpad(int64_t K) {
     KCfg c;
     if (!pick_cfg(K, &c)) return 0;
-    return 4 * c.G * c.T4 + c.G * c.TAIL;
+    return c.kp();
 }
 
 extern "C" const char *oriana_version(void) { return "oriana_hip gfx950 0.5"; }
@@ -347,7 +258,7 @@ extern "C" const char *oriana_version(void) { return "oriana_hip gfx950 0.5"; }
 extern "C" int64_t oriana_col_block_tiles(int64_t K) {
     KCfg c;
     if (!pick_cfg(K, &c)) return 0;
-    return use_col2(c.G, c.T4, c.TAIL) ? 2 : 1;
+    return col_tiles_per_item(c);
 }
 
 static bool counts_ok(const oriana_counts *cm) {
@@ -465,7 +376,7 @@ extern "C" int oriana_row_pass(const oriana_counts *cm, const float *FU, const f
     return oriana_row_pass_general(cm, FU, FV, nullptr, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, K, nullptr, nullptr, stream);
 }
 
-// Gene-tile split of the plain row pass for short matrices: a row block is one work-group (two for K > 116), so a
+// Gene-tile split of the plain row pass for short matrices: a row block is one work-group (two or four for K > 112), so a
 // matrix of 10,000 cells runs the pass on 40 of the 256 CUs; splitting each row block's gene tiles over several groups
 // fills the chip; each group of a row block stores its row sums in its own slab of R, which the consumer adds up
 // (atomics on R cost 1.2 us per split at 10,000 x 20: more than the tile a split saves).
@@ -475,8 +386,9 @@ extern "C" int oriana_row_pass_plan_cus(const oriana_counts *cm, int64_t K, cons
     *out = no_split(cm);
     KCfg cfg;
     if (!pick_cfg(K, &cfg) || cm->nrb <= 0 || cm->ncb <= 1) return 0;
-    const bool two_lane = use_k100(cfg.G, cfg.T4) || (k64_kernels() && k64_cfg(cfg.G, cfg.T4, cfg.TAIL));
-    const int64_t groups = cm->nrb * ((two_lane || use_narrow(cfg.G, cfg.T4, cfg.TAIL)) ? 1 : (TILE / (16 * (64 / cfg.G))));
+    const Fam fam = row_family(cfg, 0);             // (the plan is the plain variant's; the two-lane families serve every variant)
+    const bool two_lane = takes_row_items(fam);
+    const int64_t groups = cm->nrb * row_groups_per_block(fam, cfg.G);
     int64_t nfull = 0, parts = 1;
     if (groups < cus) {
         // short matrices: two work-groups per CU at most, evenly sized ranges (measured at 10,000 x 2,000, K = 20:
@@ -561,10 +473,13 @@ extern "C" int oriana_row_pass_general(const oriana_counts *cm, const float *FU,
     if (!split_ok(cm, sp)) return ORIANA_EINVAL;
     if (cm->m == 0) FV2 = nullptr;
     hipStream_t s = (hipStream_t)stream;
-#define CALL(G, T, L) return launch_row_pass<G, T, L>(cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, s, FV2, sp, den_min)
+    const int var = (s_rs ? V_SROW : 0) | (w_nz ? V_WEIGHTS : 0) | (FV2 ? V_IMAGE2 : 0);
+#define CALL(G, T, L)                                                                                                      \
+    return with_variant<0, 1, 2, 3, 4, 6>(var, [&](auto V) {                                                               \
+        return launch_row_pass<G, T, L, decltype(V)::value>(cm, FU, FV, w_nz, R, s_cs, sw_cs, s_rs, tile_flag, s, FV2, sp, den_min); \
+    })
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
-    return 0;
 }
 
 extern "C" int oriana_row_spmm(const oriana_counts *cm, const float *s_rs, const float *w_nz, const float *FV,
@@ -578,7 +493,6 @@ extern "C" int oriana_row_spmm(const oriana_counts *cm, const float *s_rs, const
 #define CALL(G, T, L) return launch_row_spmm<G, T, L>(cm, s_rs, w_nz, FV, R, s)
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
-    return 0;
 }
 
 extern "C" int oriana_col_pass(const oriana_counts *cm, const float *s_cs, const float *Gm, float *C, int64_t K,
@@ -590,10 +504,9 @@ extern "C" int oriana_col_pass(const oriana_counts *cm, const float *s_cs, const
     if (!Gm || !C || !s_cs) return ORIANA_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (nwork < 0 || (work == nullptr && nwork != 0)) return ORIANA_EINVAL;
-#define CALL(G, T, L) return launch_col_pass<G, T, L>(cm, s_cs, Gm, C, work, nwork, (float *)nullptr, s)
+#define CALL(G, T, L) return launch_col_pass<G, T, L, Col::plain>(cm, s_cs, Gm, C, work, nwork, nullptr, nullptr, nullptr, s)
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
-    return 0;
 }
 
 // [r6] ANALYSIS entry (tools/parity_report.py): the column pass with float64 accumulators in a fixed
@@ -643,26 +556,6 @@ extern "C" int oriana_col_pass_f64acc(const oriana_counts *cm, const float *s_cs
 }
 
 // two images, one column tile per work item (work list of width 1)
-template <int G, int T4, int TAIL>
-static int launch_col_pass_dual(const oriana_counts *cm, const float *s_cs, const float *G1, const float *G2, float *C1,
-                                float *C2, const int32_t *work, int64_t nwork, hipStream_t s) {
-    constexpr int T4c = (G == 4) ? T4 : 1, TLc = (G == 4) ? TAIL : 0;
-    using Im = ColImage<T4c, TLc>;
-    // (33 <= Kp <= 64: the two-lane dual kernel k64::k_col_pass_k64<KP4, true> measured 11.3 ms against 10.9 ms for this four-lane
-    //  one at configs[4] -- with two images per step the walk is bound by the LDS return port either way; it is not dispatched)
-    if (G != 4 || Im::DUP || 2 * Im::bytes() > (size_t)LDS_BUDGET) return ORIANA_EKRANGE;
-    if (nwork <= 0) return 0;
-    constexpr bool OK = (G == 4) && !Im::DUP;
-    auto kern = k_col_pass2<T4c, OK ? TLc : 0, OK>;
-    const size_t lb = 2 * Im::bytes();
-    int rc = set_lds(kern, lb);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwork), dim3(1024), lb, s, *cm, s_cs, G1, C1, work, (int64_t)0, (float *)nullptr,
-                       G2, C2);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int oriana_col_pass_dual(const oriana_counts *cm, const float *s_cs, const float *G1, const float *G2,
                                     float *C1, float *C2, int64_t K, const int32_t *work, int64_t nwork, void *stream) {
     if (!counts_ok(cm) || K <= 0) return ORIANA_EINVAL;
@@ -671,20 +564,18 @@ extern "C" int oriana_col_pass_dual(const oriana_counts *cm, const float *s_cs, 
     if (cm->n == 0 || cm->m == 0) return 0;
     if (!G1 || !G2 || !C1 || !C2 || !s_cs || !work || nwork < 0) return ORIANA_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-#define CALL(G, T, L) return launch_col_pass_dual<G, T, L>(cm, s_cs, G1, G2, C1, C2, work, nwork, s)
+#define CALL(G, T, L) return launch_col_pass<G, T, L, Col::dual>(cm, s_cs, G1, C1, work, nwork, nullptr, G2, C2, s)
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
-    return 0;
 }
 
 static int col_pass_partials(const oriana_counts *cm, const float *s_cs, const float *Gm, float *C, int64_t K,
                              const int32_t *work, int64_t nwork, float *scratch, hipStream_t s) {
     KCfg cfg;
     if (!pick_cfg(K, &cfg)) return ORIANA_EKRANGE;
-#define CALL(G, T, L) return launch_col_pass<G, T, L>(cm, s_cs, Gm, C, work, nwork, scratch, s)
+#define CALL(G, T, L) return launch_col_pass<G, T, L, Col::partials>(cm, s_cs, Gm, C, work, nwork, scratch, nullptr, nullptr, s)
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
-    return 0;
 }
 
 extern "C" int64_t oriana_col_pass_det_scratch_bytes(int64_t K, int64_t nwork) {

@@ -158,7 +158,7 @@ class CountTiles:
     def _build_col_work(self, target_items=None, width=1):
         """Work list of the column pass: (column block, row-block range) items of about equal
         COST, launched band of rows by band of rows.  A column block is `width` adjacent column tiles
-        (oriana_col_block_tiles(K): for K <= 116 the kernel serves two tiles with one image of the row block).
+        (oriana_col_block_tiles(K): for 20 < K <= 112 the kernel serves two tiles with one image of the row block).
         Genes differ widely in density, so uniform bands
         would leave the chip waiting for the densest column block; and the items that run at the same time
         should stage the SAME factor rows (at 1M cells the row-side factor is 400 MB, read once per column

@@ -9,6 +9,15 @@
 the third output, where the entry allows) on a sliced and a hybrid handle and the four stateless entries, at K = 20, 64, 100;
 every call is preceded by a marker launch (oriana_trigamma_f64 over 256 * index elements) that `list` splits the trace at.
 ORIANA_CUS=2 in the environment makes the plans of the small matrix split the last round (row split + dense tail).
+
+    ... -- python tools/nest_trace.py passes LABELS.txt ;  python tools/nest_trace.py list DIR LABELS.txt lds
+
+`passes` is the same for the kernel-level entries csrc/passes.hip dispatches by K: on one small sliced matrix, for one K per
+padded width the library compiles (and K = 1), oriana_row_pass_general in its six variants x {no split, even whole-grid split,
+last-round split with explicit edges}, oriana_row_spmm with and without weights, oriana_col_pass with and without a work list,
+oriana_col_pass_dual and oriana_col_pass_det.  Return codes other than 0 are part of the record (the label ends in rc=...:
+ORIANA_EKRANGE is how an entry says "not this form's K"); `list ... lds` adds the LDS bytes of every launch.  `passes-perf` runs the unsplit forms five times each on a 250,000 x 10,000 matrix,
+for `rocprofv3 --kernel-trace --stats` (the mean duration of each kernel in two builds).
 """
 import csv
 import ctypes
@@ -88,7 +97,74 @@ def run(labels_path):
         f.write('\n'.join(labels) + '\n')
 
 
-def listing(trace_dir, labels_path):
+def passes(labels_path, perf=False):
+    import numpy as np
+    import torch
+    from oriana_amd import _lib, engine
+    from oriana_amd._lib import OrianaRowSplit, ptr, stream_ptr
+    lib = _lib.load()
+    st = stream_ptr()
+    labels = []
+    mark_in = torch.ones(256 * 600, dtype=torch.float64, device='cuda')
+    mark_out = torch.empty_like(mark_in)
+
+    def probe(label, fn, *args):
+        torch.cuda.synchronize()
+        labels.append(label)
+        assert lib.oriana_trigamma_f64(ptr(mark_out), ptr(mark_in), 256 * len(labels), st) == 0
+        labels[-1] += ' rc=%d' % fn(*args)
+        for _ in range(4 if perf else 0):         # (five launches per kernel for `rocprofv3 --stats`)
+            fn(*args)
+        torch.cuda.synchronize()
+
+    if perf:      # kernel durations of two builds: a matrix on which a pass runs for milliseconds, the unsplit forms only
+        n, m = 250000, 10000
+        torch.manual_seed(8)
+        X = torch.poisson(torch.full((n, m), 3.0, device='cuda')) * (torch.rand(n, m, device='cuda') < 0.08)
+    else:
+        n, m = 1700, 1100
+        rng = np.random.default_rng(8)
+        dens = rng.beta(1.0, 3.0, size=m)
+        X = (rng.poisson(3.0, size=(n, m)) * (rng.random((n, m)) < dens[None, :])).astype(np.float32)
+    ct = engine.CountTiles.from_dense(X, device='cuda')
+    cs, nrb, ncb = ct.sparse_struct, ct.nrb, ct.ncb
+    even = OrianaRowSplit(0, 2, (ctypes.c_int32 * 9)(-1))
+    last = OrianaRowSplit(nrb - 2, 2, (ctypes.c_int32 * 9)(0, 3, ncb))
+    splits = (('none', None), ('even', ctypes.byref(even)), ('last-round', ctypes.byref(last)))[:1 if perf else 3]
+    f32 = lambda *shape: torch.rand(*shape, device='cuda') + 0.5
+    Ks = sorted({int(lib.oriana_kpad(K)) for K in range(1, 257)} | {1})
+    for K in Ks:
+        Kp = int(lib.oriana_kpad(K))
+        FU, FV, FV2 = f32(nrb * 256, Kp), f32(ncb * 256, Kp), f32(ncb * 256, Kp)
+        R = torch.zeros(8 * nrb * 256, Kp, device='cuda')
+        C1, C2 = torch.zeros(ncb * 256, Kp, device='cuda'), torch.zeros(ncb * 256, Kp, device='cuda')
+        s_cs, sw_cs = f32(max(ct.cslots, 1)), f32(max(ct.cslots, 1))
+        s_rs, w_nz = f32(max(ct.rslots, 1)), f32(max(ct.rslots, ct.cslots, 1))
+        flag = torch.zeros(nrb * ncb, dtype=torch.int32, device='cuda')
+        variants = (('plain', None, None, None, None), ('s_rs', None, None, None, s_rs), ('w_nz', None, w_nz, sw_cs, None),
+                    ('w_nz+s_rs', None, w_nz, sw_cs, s_rs), ('FV2', FV2, None, None, None), ('FV2+w_nz', FV2, w_nz, sw_cs, None))
+        for vname, f2, w, sw, srow in variants:
+            for sname, sp in splits:
+                probe('K%d row_pass %s split=%s' % (K, vname, sname), lib.oriana_row_pass_general, cs, ptr(FU), ptr(FV), ptr(f2),
+                      ptr(w), ptr(R), ptr(s_cs), ptr(sw), ptr(srow), ptr(flag), K, sp, None, st)
+        for w in (None, w_nz):
+            probe('K%d row_spmm w_nz=%d' % (K, w is not None), lib.oriana_row_spmm, cs, ptr(s_rs), ptr(w), ptr(FV), ptr(R), K, st)
+        work, work1 = ct.col_work_for(K), ct.col_work_width(1)
+        if perf:
+            probe('K%d col_pass work' % K, lib.oriana_col_pass, cs, ptr(s_cs), ptr(FU), ptr(C1), K, ptr(work), work.shape[0], st)
+            continue
+        probe('K%d col_pass bands' % K, lib.oriana_col_pass, cs, ptr(s_cs), ptr(FU), ptr(C1), K, None, 0, st)
+        probe('K%d col_pass work' % K, lib.oriana_col_pass, cs, ptr(s_cs), ptr(FU), ptr(C1), K, ptr(work), work.shape[0], st)
+        probe('K%d col_pass_dual' % K, lib.oriana_col_pass_dual, cs, ptr(s_cs), ptr(FU), ptr(FU), ptr(C1), ptr(C2), K, ptr(work1),
+              work1.shape[0], st)
+        scratch = torch.empty(int(lib.oriana_col_pass_det_scratch_bytes(K, work.shape[0])) // 4 + 1, device='cuda')
+        probe('K%d col_pass_det' % K, lib.oriana_col_pass_det, cs, ptr(s_cs), ptr(FU), ptr(C1), K, ptr(work), work.shape[0], ptr(scratch), st)
+    probe('end', lambda: 0)
+    with open(labels_path, 'w') as f:
+        f.write('\n'.join(labels) + '\n')
+
+
+def listing(trace_dir, labels_path, lds=False):
     """One line per entry: its launches in order as `kernel grid/block` (dimensions of 1 dropped, hipMemsetAsync = memset)."""
     labels = open(labels_path).read().split('\n')
     rows = []
@@ -102,12 +178,14 @@ def listing(trace_dir, labels_path):
         name = name.replace('__amd_rocclr_fillBufferAligned', 'memset')
         block = [int(r['Workgroup_Size_' + a]) for a in 'XYZ']
         grid = [int(r['Grid_Size_' + a]) // max(bl, 1) for a, bl in zip('XYZ', block)]
+        if name.startswith('at::native'):         # (torch's own fills between two entries)
+            continue
         if 'k_map_f64<1>' in name:
-            if labels[grid[0] - 1] == 'end':
+            if labels[grid[0] - 1].startswith('end'):
                 break
             out.append([labels[grid[0] - 1]])
         elif out:
-            out[-1].append('%s %s/%s' % (name, dims(grid), dims(block)))
+            out[-1].append('%s %s/%s' % (name, dims(grid), dims(block)) + (' lds=%s' % r.get('Group_Segment_Size', r.get('LDS_Block_Size')) if lds else ''))
     for e in out:
         print('%s: %s' % (e[0], ' | '.join(e[1:])))
 
@@ -132,7 +210,9 @@ def diff(a_path, b_path):
 if __name__ == '__main__':
     if sys.argv[1] == 'run':
         run(sys.argv[2])
+    elif sys.argv[1] in ('passes', 'passes-perf'):
+        passes(sys.argv[2], perf=sys.argv[1] == 'passes-perf')
     elif sys.argv[1] == 'list':
-        listing(sys.argv[2], sys.argv[3])
+        listing(sys.argv[2], sys.argv[3], lds=sys.argv[4:] == ['lds'])
     else:
         sys.exit(diff(sys.argv[2], sys.argv[3]))
