@@ -3,8 +3,8 @@
 // (stateless.hip).  An entry validates, provides the buffers its variant needs, fills a ZqView and calls zq_run:
 //     preparation (+ clear list) -> row pass -> slow path -> [second row product] -> dense genes -> finalize rows
 //     -> per-gene sums -> finalize genes -> log sums.
-// engine.zq / engine.zq_gap (oriana_amd/engine.py) run the same sequence for the model classes, interleaved with their
-// timers, the sharded exchange and the deterministic mode.
+// engine.zq (oriana_amd/engine.py) is the ONE Python copy of this sequence, in the same order, for the model classes: it
+// interleaves their timers, the cell-side update, the sharded exchange and the deterministic mode.
 #pragma once
 #include "common.h"
 #include <string.h>

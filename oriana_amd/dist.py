@@ -220,7 +220,7 @@ class SweepExchange:
 
     def reduce_rows_async(self, name, lo, hi):
         """Start the all-reduce of rows [lo, hi) of the float32 segment `name` NOW, asynchronously (the segment is written
-        in an order that makes them final early: engine.zq_gap zj_packed).  The next reduce() then sends no float32 buffer
+        in an order that makes them final early: engine.zq zj_packed).  The next reduce() then sends no float32 buffer
         and only waits for them -- plus, should the calls of a sweep not cover every row of every float32 segment, one
         all-reduce per uncovered range."""
         if not self.active or hi <= lo:

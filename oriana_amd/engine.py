@@ -205,7 +205,7 @@ class CountTiles:
         if self.gd and self.col_perm is None:
             raise _lib.OrianaHipError('a hybrid layout needs an explicit gene order')
         # the sliced layout of a hybrid matrix is the sub-matrix of the packed genes [gd, m): its gene order is the
-        # full one advanced by gd entries (so are the FV / C pointers the passes get, see zq_gap)
+        # full one advanced by gd entries (so are the FV / C pointers the passes get, see zq)
         self._struct = OrianaCounts(self.n, self.ms, self.nrb, self.ncb, self.nnz_sparse, self.rslots, self.cslots,
                                     ptr(self.roff), ptr(self.coff), ptr(self.rslice), ptr(self.cslice),
                                     ptr(self.rowrec), ptr(self.ridx),
@@ -697,20 +697,17 @@ def factor_prep_pair(ws, log_U_hat, log_V_hat, mask_v=None, clear=None):
         cl = _clear_list(ws, clear)
     if ws.fu_pending and ws.fu_source != log_U_hat.data_ptr():
         ws.fu_pending = False               # (a caller's own E[log U]: the preparation at hand belongs to another matrix)
+    clp = ctypes.byref(cl) if cl is not None else None
     if ws.fu_pending:
         # the cell side was prepared by the Gamma update that wrote this E[log U] (ZWorkspace.prep_outputs): the buffers swap,
         # this launch combines the statistics, prepares the gene side and overwrites the rejected cell rows
         ws.fu_pending = False
         ws.FU, ws.FU_alt = ws.FU_alt, ws.FU
         call('oriana_factor_prep_pair_fused', ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), ws.prep_blocks, ptr(ws.FV), ptr(log_V_hat),
-             ptr(mask_v), ptr(ct.col_perm), ct.n, ct.m, ws.K, ptr(ws.stats), ctypes.byref(cl) if cl is not None else None, stream_ptr())
+             ptr(mask_v), ptr(ct.col_perm), ct.n, ct.m, ws.K, ptr(ws.stats), clp, stream_ptr())
         return
-    if cl is not None:
-        call('oriana_factor_prep_pair_clear', ptr(ws.FU), ptr(ws.FV), ptr(log_U_hat), ptr(log_V_hat), ptr(mask_v),
-             ptr(ct.row_perm), ptr(ct.col_perm), ct.n, ct.m, ws.K, ptr(ws.stats), ctypes.byref(cl), stream_ptr())
-        return
-    call('oriana_factor_prep_pair', ptr(ws.FU), ptr(ws.FV), ptr(log_U_hat), ptr(log_V_hat), ptr(mask_v), ptr(ct.row_perm),
-         ptr(ct.col_perm), ct.n, ct.m, ws.K, ptr(ws.stats), stream_ptr())
+    call('oriana_factor_prep_pair_clear', ptr(ws.FU), ptr(ws.FV), ptr(log_U_hat), ptr(log_V_hat), ptr(mask_v),
+         ptr(ct.row_perm), ptr(ct.col_perm), ct.n, ct.m, ws.K, ptr(ws.stats), clp, stream_ptr())
 
 
 # analysis runs (tools/parity_report.py): float64 accumulators and one rounding for the per-gene sums -- '1': all of them, 'log': the
@@ -754,190 +751,161 @@ def col_pass_dual(ct, s_cs, G1, G2, C1, C2, K, goff=0):
     return rc == 0
 
 
-def zq_gap(ws, Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, phase='all', finalize_rows=True, finalize_cols=True, clear=(),
-           zj_packed=False, on_segment=None):
-    """GaP.compute_Z_q_expectations (reference gap.py:67-80) on the resident tiles: outputs first,
-    zero-filled by the callee, returns None.  `phase`: 'rows' stops once Z_hat_i is final (factor
-    preparation, row pass, slow path, row-side finalize), 'cols' does the rest (column pass, gene-side finalize):
-    the cell-side Gamma update only needs Z_hat_i, so a sharded sweep runs it between the two and has every
-    partial of its single exchange ready when the column pass ends.
-    finalize_rows / finalize_cols = False: the caller completes Z_hat_i / Z_hat_j itself (the pCMF sweep folds
-    Z += F * R into its Gamma updates, oriana_gamma_update_finalize); until then they hold the slow path's additions
-    only.  `clear`: further buffers (at most 3) zero-filled by the factor preparation's launch.
-    zj_packed (the row-sharded pCMF sweep): Z_hat_j is kept in the PACKED gene order -- the slow paths index it by the packed
-    gene, the gene-side finalize writes it without the permutation -- so that the dense genes [0, gd) and the sliced genes
-    [gd, m) are two contiguous segments of the exchange buffer; `on_segment(lo, hi)` is called as soon as the rows
-    [lo, hi) of Z_hat_j are final (the sliced segment after the sliced column pass, i.e. BEFORE the dense gene-side
-    kernel runs: its all-reduce travels under that kernel)."""
-    ct, K = ws.ct, ws.K
-    st = stream_ptr()
-    dn = ct.dense
-    gd = ct.gd
-    # hybrid layout: the sliced layout covers the packed genes [gd, m) -- its FV / C rows start gd rows in
-    FVs, Cs = ptr(ws.FV) + 4 * gd * ws.Kp, ptr(ws.C) + 4 * gd * ws.Kp
-    if phase in ('all', 'rows'):
-        _check_f32(Z_hat_i, (ct.n, K)); _check_f32(Z_hat_j, (ct.m, K))
-        _check_f32(log_U_hat, (ct.n, K)); _check_f32(log_V_hat, (ct.m, K))
-        # short matrices: the gene tiles of a row block are split over several work-groups, which add into R
-        gs = ws.row_gene_splits
-        zero_R = ws.R if ct.ms == 0 else None              # (no sliced part: the dense row pass adds into it)
-        factor_prep_pair(ws, log_U_hat, log_V_hat, clear=(Z_hat_i, Z_hat_j, ws.C, ws.tile_flag, zero_R) + tuple(clear))
-        if ct.ms > 0:
-            with _span(ws, 'row_pass'):
-                call('oriana_row_pass_general', ct.sparse_struct, ptr(ws.FU), FVs, None, None, ptr(ws.R), ptr(ws.s_cs), None, None,
-                     ptr(ws.tile_flag), K, ctypes.byref(ws.row_split), ws.den_min_ptr, st)
-        if dn is not None:
-            with _span(ws, 'dense_images'):
-                call('oriana_dense_images', ptr(ws.dn_imgV), ptr(ws.FV), gd, K, 0, st)
-            with _span(ws, 'dense_row'):
-                # (the blocks of the chip's last round split as the sliced row pass split them: same rows, same slabs of R)
-                tail = ws.dense_tail(gs)
-                call('oriana_dense_row_pass_tail', dn.c_struct, ptr(ws.FU), ptr(ws.dn_imgV), ptr(ws.R), ptr(ws.dn_S),
-                     ptr(ws.dn_flag), K, ws.dn_gene_splits, tail[0], tail[1], ws.den_min_ptr, st)
-        with _span(ws, 'fixup'):
-            if ct.ms > 0:
-                # (packed Z_hat_j: the sliced part's packed gene 0 is row gd of the buffer)
-                call('oriana_fixup', ct.sparse_struct, ptr(ws.tile_flag), ptr(ws.s_cs), None, None, ptr(log_U_hat),
-                     ptr(log_V_hat), None, None, None, None, ptr(Z_hat_i), ptr(Z_hat_j) + (4 * gd * K if zj_packed else 0), None, K,
-                     8 if zj_packed else 0, st)
-            if dn is not None:
-                call('oriana_dense_fixup_variant', dn.c_struct, ptr(ws.dn_flag), ptr(ws.dn_S), ptr(log_U_hat), ptr(log_V_hat),
-                     ptr(ct.row_perm), ptr(ct.col_perm), ptr(Z_hat_i), ptr(Z_hat_j), None, None, None, None, K,
-                     1 if zj_packed else 0, st)
-        if finalize_rows:
-            call('oriana_finalize_slabs_from', ptr(Z_hat_i), ptr(ws.FU), ptr(ws.R), gs, ws.row_slab_row0, ptr(ct.row_perm), ct.n, K, st)
-    if phase in ('all', 'cols'):
-        if ct.ms > 0:
-            with _span(ws, 'col_pass'):
-                col_pass(ct, ws.s_cs, ws.FU, ws.C, K, C_ptr=Cs)
-            if zj_packed:                   # the sliced genes' rows of Z_hat_j are final: hand them to the exchange
-                call('oriana_finalize', ptr(Z_hat_j) + 4 * gd * K, FVs, Cs, None, None, ct.ms, K, 1, st)
-                if on_segment is not None:
-                    on_segment(gd, ct.m)
-        if dn is not None:
-            with _span(ws, 'dense_images'):
-                call('oriana_dense_images', ptr(ws.dn_imgU), ptr(ws.FU), ct.n, K, 1, st)
-            with _span(ws, 'dense_col'):
-                call('oriana_dense_col_pass', dn.c_struct, ptr(ws.dn_imgU), ptr(ws.dn_S), ptr(ws.C), K,
-                     ws.dn_cell_splits, st)
-            if zj_packed:
-                call('oriana_finalize', ptr(Z_hat_j), ptr(ws.FV), ptr(ws.C), None, None, gd, K, 1, st)
-                if on_segment is not None:
-                    on_segment(0, gd)
-        if finalize_cols and not zj_packed:
-            call('oriana_finalize', ptr(Z_hat_j), ptr(ws.FV), ptr(ws.C), None, ptr(ct.col_perm), ct.m, K, 1, st)
-
-
-def zq_gap_stateless(Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, X):
-    """oriana_zq_gap_f32: the reference signature on dense device tensors (packs X per call)."""
-    for t in (Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, X):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
-            raise TypeError('expected 2-D C-contiguous float32 device tensors')
-    n, K = log_U_hat.shape
-    m = log_V_hat.shape[0]
-    _check_f32(Z_hat_i, (n, K)); _check_f32(Z_hat_j, (m, K)); _check_f32(log_V_hat, (m, K)); _check_f32(X, (n, m))
-    ws, base, nbytes = _stateless_ws(n, m, K, X)
-    call('oriana_zq_gap_f32', ptr(Z_hat_i), ptr(Z_hat_j), ptr(log_U_hat), ptr(log_V_hat), ptr(X), n, m, K,
-         base, nbytes, stream_ptr())
-
-
 # (module switches for tests: the two-kernel forms of the sparse row / column phase, which every Kp > 64 takes anyway)
 _FUSE_SPARSE_ROWS = True
 _FUSE_SPARSE_COLS = True
 
 
-def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=None, w_nz=None, phase='all'):
-    """The four loop nests on the resident tiles.  `w_nz` = D_hat at the stored entries (row-side
-    slots, CountTiles.side_nz); None means 1, which is always the case inside the models
-    (zigap.py:135 sets the dropout posterior of every non-zero count to 1 in float32):
+def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=None, w_nz=None, phase='all',
+       finalize_rows=True, finalize_cols=True, clear=(), zj_packed=False, on_segment=None):
+    """The four loop nests on the resident tiles: THE launch sequence of the model classes (csrc/zq_nest.h is its C twin).
+    `w_nz` = D_hat at the stored entries (row-side slots, CountTiles.side_nz); None means 1, which is always the case
+    inside the models (zigap.py:135 sets the dropout posterior of every non-zero count to 1 in float32):
       Z_i[i,k]   = sum_j [S_hat[j,k]] r_ijk                    (gap.py:79, sparse_gap.py:95)
       Z_j[j,k]   = sum_i [dq[i,k]] r_ijk                       (gap.py:80; dq = D_hat[:, :K], zigap.py:94)
       Z_log[j,k] = sum_i r_ijk (lu_ik + lv_jk)                 (zigap.py:95) -- skipped when Z_log is None
     with r_ijk = x_ij e_k / sum_k e_k, e_k = exp(lu_ik + lv_jk) [S_tilde[j,k]].  Outputs first,
-    zero-filled here, float32 device tensors.  `phase` as in zq_gap ('rows': everything Z_i needs; 'cols': the
-    per-gene sums; both phases must get the same arguments).
+    zero-filled here, float32 device tensors; returns None.
+    `phase`: 'rows' stops once Z_i is final (factor preparation, row pass, slow path, row-side finalize), 'cols' does the
+    rest (column pass, gene-side finalize); both phases must get the same arguments.  The cell-side Gamma update only needs
+    Z_i, so a sweep runs it between the two and has every partial of its single exchange ready when the column pass ends
+    (SURVEY 8e).
     HYBRID layouts (every nest without per-entry weights): the sliced kernels cover the packed genes [gd, m) -- their
     gene-side pointers start gd rows in --, the dense-gene kernels the first gd: den against the (masked) FV image, the
     accumulation against FV * S_hat (oriana_dense_images2), one gene-side pass per per-gene sum (FU [* dq], and the
-    centred E[log U]-weighted factor of the log sums)."""
+    centred E[log U]-weighted factor of the log sums).
+    The plain nest (pCMF: no S_hat, dq, w_nz, Z_log; ValueError otherwise) also takes:
+    finalize_rows / finalize_cols = False: the caller completes Z_i / Z_j itself (the pCMF sweep folds Z += F * R into its
+    Gamma updates, oriana_gamma_update_finalize); until then they hold the slow path's additions only.
+    `clear`: further buffers (at most 3: the launch takes 8) zero-filled by the factor preparation's launch.
+    zj_packed (the row-sharded pCMF sweep): Z_j is kept in the PACKED gene order -- the slow paths index it by the packed
+    gene, the gene-side finalize writes it without the permutation -- so that the dense genes [0, gd) and the sliced genes
+    [gd, m) are two contiguous segments of the exchange buffer; `on_segment(lo, hi)` is called as soon as the rows
+    [lo, hi) of Z_j are final (the sliced segment after the sliced column pass, i.e. BEFORE the dense gene-side
+    kernel runs: its all-reduce travels under that kernel)."""
+    if ws.ct.dense is not None and w_nz is not None:
+        raise _lib.OrianaHipError('a hybrid (dense-gene) layout carries no per-entry weights: pack without dense_density for this use')
+    if (zj_packed or on_segment is not None or clear or not (finalize_rows and finalize_cols)) and not (
+            S_hat is None and dq is None and w_nz is None and Z_log is None):
+        raise ValueError('zj_packed, on_segment, clear and finalize_rows / finalize_cols = False belong to the plain nest only')
+    if phase in ('all', 'rows'):
+        _zq_rows(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde, S_hat, dq, w_nz, finalize_rows, clear, zj_packed)
+    if phase in ('all', 'cols'):
+        _zq_cols(ws, Z_j, Z_log, log_V_hat, dq, w_nz, finalize_cols, zj_packed, on_segment)
+
+
+def zq_gap(ws, Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, **kw):
+    """GaP.compute_Z_q_expectations (reference gap.py:67-80) on the resident tiles: the plain nest of zq (its keywords)."""
+    zq(ws, Z_hat_i, Z_hat_j, None, log_U_hat, log_V_hat, **kw)
+
+
+def _have_sliced(ct):
+    """Do the sliced kernels run?  Not on a hybrid layout whose genes are all dense."""
+    return ct.ms > 0 or ct.dense is None
+
+
+def _zq_rows(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde, S_hat, dq, w_nz, finalize, clear, zj_packed):
+    """Everything Z_i needs: preparation, row pass, slow path, [second row product], dense genes, finalize rows."""
     ct, K = ws.ct, ws.K
     n, m = ct.n, ct.m
     sparse = S_hat is not None
     st = stream_ptr()
     dn, gd = ct.dense, ct.gd
-    if dn is not None and w_nz is not None:
-        raise _lib.OrianaHipError('a hybrid (dense-gene) layout carries no per-entry weights: pack without dense_density for this use')
     cst = ct.sparse_struct                       # (== the whole layout when there are no dense genes)
     goff = 4 * gd * ws.Kp                        # byte offset of the sliced part's first gene row in FV, C, ...
-    have_sliced = ct.ms > 0 or dn is None
-    if phase in ('all', 'rows'):
-        _check_f32(Z_i, (n, K)); _check_f32(Z_j, (m, K)); _check_f32(log_U_hat, (n, K)); _check_f32(log_V_hat, (m, K))
-        if w_nz is not None and ws.sw_cs is None:
-            ws.sw_cs = torch.zeros(max(ct.cslots, 1), dtype=torch.float32, device=ct.device)
+    have_sliced = _have_sliced(ct)
+    _check_f32(Z_i, (n, K)); _check_f32(Z_j, (m, K)); _check_f32(log_U_hat, (n, K)); _check_f32(log_V_hat, (m, K))
+    if w_nz is not None and ws.sw_cs is None:
+        ws.sw_cs = torch.zeros(max(ct.cslots, 1), dtype=torch.float32, device=ct.device)
     sw_cs = ws.sw_cs if w_nz is not None else None
-    if phase in ('all', 'rows'):
-        zero_R = ws.R if not have_sliced else None          # (no sliced part: the dense row pass adds into it)
-        factor_prep_pair(ws, log_U_hat, log_V_hat, mask_v=S_tilde, clear=(Z_i, Z_j, ws.C, ws.tile_flag, Z_log, zero_R))
-        # sparse models: the S_hat-weighted row sums (sparse_gap.py:95).  Where two factor images fit in LDS (Kp <= 64)
-        # they come out of the row pass itself (dot product against FV, accumulation against FV * S_hat); otherwise the
-        # pass leaves s in row-side slots and a second row product follows.
-        fused = False
-        F2 = None
-        gs = ws.row_gene_splits                     # gene ranges per row block (slabs of R), see oriana_row_pass_plan
-        nslab = 1
-        if sparse:
-            F2 = ws.extra('FVS', m)
-            call('oriana_scale_factor', ptr(F2), ptr(ws.FV), ptr(S_hat), ptr(ct.col_perm), m, K, 0, st)
-        if have_sliced:
-            if sparse and _FUSE_SPARSE_ROWS:
-                with _span(ws, 'row_pass'):
-                    rc = _lib.load().oriana_row_pass_general(cst, ptr(ws.FU), ptr(ws.FV) + goff, ptr(F2) + goff, ptr(w_nz), ptr(ws.R),
-                                                             ptr(ws.s_cs), ptr(sw_cs), None, ptr(ws.tile_flag), K, ctypes.byref(ws.row_split), ws.den_min_ptr, st)
-                if rc not in (0, -2):
-                    raise _lib.OrianaHipError('oriana_row_pass_general failed with code %d' % rc)
-                fused = rc == 0
-            if not fused:
-                if sparse and ws.s_rs is None:   # row-side copy of s for the second row product (lazy: the fused form never needs it)
-                    ws.s_rs = torch.zeros(max(ct.rslots, 1), dtype=torch.float32, device=ct.device)
-                with _span(ws, 'row_pass'):
-                    call('oriana_row_pass_general', cst, ptr(ws.FU), ptr(ws.FV) + goff, None, ptr(w_nz), ptr(ws.R), ptr(ws.s_cs),
-                         ptr(sw_cs), ptr(ws.s_rs) if sparse else None, ptr(ws.tile_flag), K, ctypes.byref(ws.row_split), ws.den_min_ptr, st)
-            if fused or not sparse:
-                nslab = gs                       # (the second row product of the unfused sparse form writes one slab)
-            with _span(ws, 'fixup'):
-                call('oriana_fixup', cst, ptr(ws.tile_flag), ptr(ws.s_cs), ptr(sw_cs),
-                     ptr(ws.s_rs) if (sparse and not fused) else None,
-                     ptr(log_U_hat), ptr(log_V_hat), ptr(S_tilde), ptr(S_hat), ptr(w_nz), ptr(dq), ptr(Z_i), ptr(Z_j), ptr(Z_log),
-                     K, (1 if sparse else 0) | (2 if w_nz is not None else 0) | (4 if dq is not None else 0), st)
-            if sparse and not fused:
-                with _span(ws, 'row_spmm'):
-                    call('oriana_row_spmm', cst, ptr(ws.s_rs), ptr(w_nz), ptr(F2) + goff, ptr(ws.R), K, st)
-        if dn is not None:
-            # (after the sliced kernels: the dense row kernel ADDS its sums into R)
-            with _span(ws, 'dense_images'):
-                call('oriana_dense_images2', ptr(ws.dn_imgV), ptr(ws.FV), ptr(F2), gd, K, 0, st)
-            with _span(ws, 'dense_row'):
-                tail = ws.dense_tail(nslab)
-                call('oriana_dense_row_pass_tail', dn.c_struct, ptr(ws.FU), ptr(ws.dn_imgV), ptr(ws.R), ptr(ws.dn_S), ptr(ws.dn_flag), K,
-                     ws.dn_gene_splits, tail[0], tail[1], ws.den_min_ptr, st)
-            with _span(ws, 'fixup'):
-                call('oriana_dense_fixup_variant', dn.c_struct, ptr(ws.dn_flag), ptr(ws.dn_S), ptr(log_U_hat), ptr(log_V_hat),
-                     ptr(ct.row_perm), ptr(ct.col_perm), ptr(Z_i), ptr(Z_j), ptr(Z_log), ptr(dq), ptr(S_tilde), ptr(S_hat), K, 0, st)
-        call('oriana_finalize_slabs_from', ptr(Z_i), ptr(ws.FU), ptr(ws.R), nslab, ws.row_slab_row0, ptr(ct.row_perm), n, K, st)
-        if Z_log is not None:
-            # E[log U]-weighted row factor of the log sums: built NOW, from the pre-update E[log U] (the caller
-            # may run the cell-side update between the two phases)
-            call('oriana_log_center', ws.center_ptr, ptr(ws.FU), ptr(log_U_hat), ptr(Z_i), ptr(ct.row_perm), n, K, st)
-            call('oriana_scale_factor_centered', ptr(ws.extra('GL', n)), ptr(ws.FU), ptr(log_U_hat), ws.center_ptr, ptr(ct.row_perm), n, K, st)
-    if phase == 'rows':
-        return
-
-    def dense_cols(Gmat, Cmat):
-        """The dense genes' share of  Cmat += s Gmat  (gene-side kernel over the cell images of Gmat)."""
+    zero_R = ws.R if not have_sliced else None          # (no sliced part: the dense row pass adds into it)
+    factor_prep_pair(ws, log_U_hat, log_V_hat, mask_v=S_tilde, clear=(Z_i, Z_j, ws.C, ws.tile_flag, Z_log, zero_R) + tuple(clear))
+    # sparse models: the S_hat-weighted row sums (sparse_gap.py:95).  Where two factor images fit in LDS (Kp <= 64)
+    # they come out of the row pass itself (dot product against FV, accumulation against FV * S_hat); otherwise the
+    # pass leaves s in row-side slots and a second row product follows.
+    fused = False
+    F2 = None
+    gs = ws.row_gene_splits                     # gene ranges per row block (slabs of R), see oriana_row_pass_plan
+    nslab = 1
+    if sparse:
+        F2 = ws.extra('FVS', m)
+        call('oriana_scale_factor', ptr(F2), ptr(ws.FV), ptr(S_hat), ptr(ct.col_perm), m, K, 0, st)
+    if have_sliced:
+        if sparse and _FUSE_SPARSE_ROWS:
+            with _span(ws, 'row_pass'):
+                rc = _lib.load().oriana_row_pass_general(cst, ptr(ws.FU), ptr(ws.FV) + goff, ptr(F2) + goff, ptr(w_nz), ptr(ws.R),
+                                                         ptr(ws.s_cs), ptr(sw_cs), None, ptr(ws.tile_flag), K, ctypes.byref(ws.row_split), ws.den_min_ptr, st)
+            if rc not in (0, -2):
+                raise _lib.OrianaHipError('oriana_row_pass_general failed with code %d' % rc)
+            fused = rc == 0
+        if not fused:
+            if sparse and ws.s_rs is None:   # row-side copy of s for the second row product (lazy: the fused form never needs it)
+                ws.s_rs = torch.zeros(max(ct.rslots, 1), dtype=torch.float32, device=ct.device)
+            with _span(ws, 'row_pass'):
+                call('oriana_row_pass_general', cst, ptr(ws.FU), ptr(ws.FV) + goff, None, ptr(w_nz), ptr(ws.R), ptr(ws.s_cs),
+                     ptr(sw_cs), ptr(ws.s_rs) if sparse else None, ptr(ws.tile_flag), K, ctypes.byref(ws.row_split), ws.den_min_ptr, st)
+        if fused or not sparse:
+            nslab = gs                       # (the second row product of the unfused sparse form writes one slab)
+        with _span(ws, 'fixup'):
+            # (packed Z_j, variant bit 8: indexed by the packed gene -- the sliced part's gene 0 is row gd of the buffer)
+            call('oriana_fixup', cst, ptr(ws.tile_flag), ptr(ws.s_cs), ptr(sw_cs),
+                 ptr(ws.s_rs) if (sparse and not fused) else None,
+                 ptr(log_U_hat), ptr(log_V_hat), ptr(S_tilde), ptr(S_hat), ptr(w_nz), ptr(dq), ptr(Z_i),
+                 ptr(Z_j) + (4 * gd * K if zj_packed else 0), ptr(Z_log), K,
+                 (1 if sparse else 0) | (2 if w_nz is not None else 0) | (4 if dq is not None else 0) | (8 if zj_packed else 0), st)
+        if sparse and not fused:
+            with _span(ws, 'row_spmm'):
+                call('oriana_row_spmm', cst, ptr(ws.s_rs), ptr(w_nz), ptr(F2) + goff, ptr(ws.R), K, st)
+    if dn is not None:
+        # (after the sliced kernels: the dense row kernel ADDS its sums into R; the sliced slow path and the dense row kernel
+        #  touch disjoint buffers)
         with _span(ws, 'dense_images'):
-            call('oriana_dense_images', ptr(ws.dn_imgU), ptr(Gmat), n, K, 1, st)
-        with _span(ws, 'dense_col'):
-            call('oriana_dense_col_pass', dn.c_struct, ptr(ws.dn_imgU), ptr(ws.dn_S), ptr(Cmat), K, ws.dn_cell_splits, st)
+            call('oriana_dense_images2', ptr(ws.dn_imgV), ptr(ws.FV), ptr(F2), gd, K, 0, st)
+        with _span(ws, 'dense_row'):
+            # (the blocks of the chip's last round split as the sliced row pass split them: same rows, same slabs of R)
+            tail = ws.dense_tail(nslab)
+            call('oriana_dense_row_pass_tail', dn.c_struct, ptr(ws.FU), ptr(ws.dn_imgV), ptr(ws.R), ptr(ws.dn_S), ptr(ws.dn_flag), K,
+                 ws.dn_gene_splits, tail[0], tail[1], ws.den_min_ptr, st)
+        with _span(ws, 'fixup'):
+            call('oriana_dense_fixup_variant', dn.c_struct, ptr(ws.dn_flag), ptr(ws.dn_S), ptr(log_U_hat), ptr(log_V_hat),
+                 ptr(ct.row_perm), ptr(ct.col_perm), ptr(Z_i), ptr(Z_j), ptr(Z_log), ptr(dq), ptr(S_tilde), ptr(S_hat), K,
+                 1 if zj_packed else 0, st)
+    if finalize:
+        call('oriana_finalize_slabs_from', ptr(Z_i), ptr(ws.FU), ptr(ws.R), nslab, ws.row_slab_row0, ptr(ct.row_perm), n, K, st)
+    if Z_log is not None:
+        # E[log U]-weighted row factor of the log sums: built NOW, from the pre-update E[log U] (the caller
+        # may run the cell-side update between the two phases)
+        call('oriana_log_center', ws.center_ptr, ptr(ws.FU), ptr(log_U_hat), ptr(Z_i), ptr(ct.row_perm), n, K, st)
+        call('oriana_scale_factor_centered', ptr(ws.extra('GL', n)), ptr(ws.FU), ptr(log_U_hat), ws.center_ptr, ptr(ct.row_perm), n, K, st)
+
+
+def _dense_cols(ws, G, C, st):
+    """The dense genes' share of  C += s G  (gene-side kernel over the cell images of G)."""
+    with _span(ws, 'dense_images'):
+        call('oriana_dense_images', ptr(ws.dn_imgU), ptr(G), ws.ct.n, ws.K, 1, st)
+    with _span(ws, 'dense_col'):
+        call('oriana_dense_col_pass', ws.ct.dense.c_struct, ptr(ws.dn_imgU), ptr(ws.dn_S), ptr(C), ws.K, ws.dn_cell_splits, st)
+
+
+def _finalize_packed(ws, Z_j, lo, hi, on_segment, st):
+    """The rows [lo, hi) of a Z_j kept in the packed gene order have their sums: complete them in place (no permutation)
+    and hand them to the exchange."""
+    if hi > lo:
+        call('oriana_finalize', ptr(Z_j) + 4 * lo * ws.K, ptr(ws.FV) + 4 * lo * ws.Kp, ptr(ws.C) + 4 * lo * ws.Kp, None, None,
+             hi - lo, ws.K, 1, st)
+        if on_segment is not None:
+            on_segment(lo, hi)
+
+
+def _zq_cols(ws, Z_j, Z_log, log_V_hat, dq, w_nz, finalize, zj_packed, on_segment):
+    """The per-gene sums: column pass, dense genes, finalize genes, log sums."""
+    ct, K = ws.ct, ws.K
+    n, m = ct.n, ct.m
+    st = stream_ptr()
+    dn, gd = ct.dense, ct.gd
+    goff = 4 * gd * ws.Kp                        # byte offset of the sliced part's first gene row in FV, C, ...
+    have_sliced = _have_sliced(ct)
+    sw_cs = ws.sw_cs if w_nz is not None else None
     # per-gene sums: weighted by D_hat[i, j] (sw), or -- zigap.py:94 -- by D_hat[i, k] on the plain s
     G, s_for_j = ws.FU, (sw_cs if sw_cs is not None else ws.s_cs)
     if dq is not None:
@@ -958,9 +926,14 @@ def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=N
     if not dual_done and have_sliced:
         with _span(ws, 'col_pass'):
             col_pass(ct, s_for_j, G, ws.C, K, C_ptr=ptr(ws.C) + goff)
+    if zj_packed and have_sliced:               # (before the dense genes: this segment's all-reduce travels under their kernel)
+        _finalize_packed(ws, Z_j, gd, m, on_segment, st)
     if dn is not None:
-        dense_cols(G, ws.C)
-    call('oriana_finalize', ptr(Z_j), ptr(ws.FV), ptr(ws.C), None, ptr(ct.col_perm), m, K, 1, st)
+        _dense_cols(ws, G, ws.C, st)
+        if zj_packed:
+            _finalize_packed(ws, Z_j, 0, gd, on_segment, st)
+    if finalize and not zj_packed:
+        call('oriana_finalize', ptr(Z_j), ptr(ws.FV), ptr(ws.C), None, ptr(ct.col_perm), m, K, 1, st)
     if Z_log is not None:
         if dq is not None:                      # the log sums use the D_hat[i, j]-weighted column sums
             ws.C.zero_()
@@ -970,13 +943,18 @@ def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=N
                     if not dual_done:
                         col_pass(ct, s_log, ws.FU, ws.C, K, C_ptr=ptr(ws.C) + goff)
             if dn is not None:
-                dense_cols(ws.FU, ws.C)
+                _dense_cols(ws, ws.FU, ws.C, st)
         if not dual_done and have_sliced:
             with _span(ws, 'col_pass_log'):
                 col_pass(ct, s_log, G2, C2, K, C_ptr=ptr(C2) + goff, what='log')
         if dn is not None:
-            dense_cols(G2, C2)
+            _dense_cols(ws, G2, C2, st)
         call('oriana_finalize_zlog', ptr(Z_log), ptr(ws.FV), ptr(C2), ptr(ws.C), ptr(log_V_hat), ws.center_ptr, ptr(ct.col_perm), m, K, st)
+
+
+def zq_gap_stateless(Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, X):
+    """oriana_zq_gap_f32: the reference signature on dense device tensors (packs X per call)."""
+    zq_dense(Z_hat_i, Z_hat_j, None, log_U_hat, log_V_hat, X)
 
 
 def _stateless_ws(n, m, K, X):

@@ -323,6 +323,32 @@ def test_zq_gap_rejects_wrong_dtype(eng):
         eng.zq_gap(ws, z, z.clone(), z.double(), z.clone())
 
 
+@pytest.mark.parametrize('option', [dict(zj_packed=True), dict(on_segment=lambda lo, hi: None), dict(finalize_rows=False),
+                                    dict(finalize_cols=False), dict(clear=True)])
+@pytest.mark.parametrize('nest', ['S_hat', 'dq', 'w_nz', 'Z_log'])
+def test_plain_nest_options_are_refused_on_the_other_nests(eng, option, nest):
+    """zj_packed / on_segment / clear / finalize_* = False are options of the plain nest: with S_hat, dq, w_nz or Z_log engine.zq
+    raises ValueError before anything is launched (the outputs keep their contents) instead of half-honouring them."""
+    extra = torch.ones(8, device='cuda')
+    if 'clear' in option:
+        option = dict(clear=(extra,))
+    X = np.ones((4, 4), np.float32)
+    ct = eng.CountTiles.from_dense(X, 'cuda', side=torch.ones(4, 4, device='cuda'))
+    ws = eng.ZWorkspace(ct, 2)
+    z = lambda: torch.full((4, 2), 7.0, device='cuda')
+    Zi, Zj = z(), z()
+    kw = {'S_hat': dict(S_tilde=z(), S_hat=z()), 'dq': dict(dq=z()), 'w_nz': dict(w_nz=ct.side_nz), 'Z_log': {}}[nest]
+    for phase in ('all', 'rows', 'cols'):
+        with pytest.raises(ValueError):
+            eng.zq(ws, Zi, Zj, z() if nest == 'Z_log' else None, z(), z(), phase=phase, **kw, **option)
+    torch.cuda.synchronize()
+    assert float(Zi.min()) == 7.0 and float(Zj.min()) == 7.0
+    assert float(extra.min()) == 1.0
+    eng.zq_gap(ws, Zi, Zj, z(), z(), **option)             # (the plain nest takes each of them)
+    torch.cuda.synchronize()
+    assert float(extra.max()) == (0.0 if 'clear' in option else 1.0)
+
+
 def test_stateless_dropin_signature(eng):
     """GaP.compute_Z_q_expectations(Z_i, Z_j, log_U, log_V, X): the reference's own calling
     convention (gap.py:89-94) on device tensors, through oriana_zq_gap_f32."""

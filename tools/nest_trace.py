@@ -18,6 +18,17 @@ last-round split with explicit edges}, oriana_row_spmm with and without weights,
 oriana_col_pass_dual and oriana_col_pass_det.  Return codes other than 0 are part of the record (the label ends in rc=...:
 ORIANA_EKRANGE is how an entry says "not this form's K"); `list ... lds` adds the LDS bytes of every launch.  `passes-perf` runs the unsplit forms five times each on a 250,000 x 10,000 matrix,
 for `rocprofv3 --kernel-trace --stats` (the mean duration of each kernel in two builds).
+
+    ... -- python tools/nest_trace.py models LABELS.txt ;  python tools/nest_trace.py list DIR LABELS.txt
+
+`models` is `run` for the Python sequencer (oriana_amd/engine.py): behind the same markers engine.zq_gap (whole, phase='rows' then
+'cols', finalize_rows / finalize_cols = False, zj_packed with a recording on_segment -- the segments end up in the label) and
+engine.zq (plain, dq, sparse, and sparse + w_nz on the sliced layout; with and without Z_log; whole and in two phases) on the
+sliced and the hybrid layout of the same matrix at K = 20, 64, 100, then two step()s of each of the four model classes per layout.
+ORIANA_CUS=2, ORIANA_DETERMINISTIC=1 and ORIANA_FORCE_SHARDED=1 (a one-rank gloo group: the packed-Z_j path of models/gap.py) in the
+environment select the other forms of the sequence.  `list ... nocopy` drops the runtime's buffer copies (__amd_rocclr_copyBuffer):
+under ORIANA_FORCE_SHARDED=1 the exchange issues them from its own threads, beside the sweep's stream, and their place in the
+time-ordered listing changes from run to run.
 """
 import csv
 import ctypes
@@ -164,7 +175,78 @@ def passes(labels_path, perf=False):
         f.write('\n'.join(labels) + '\n')
 
 
-def listing(trace_dir, labels_path, lds=False):
+def models(labels_path):
+    import tempfile
+    import numpy as np
+    import torch
+    import oriana_amd.models as M
+    from oriana_amd import _lib, engine
+    from oriana_amd._lib import ptr, stream_ptr
+    lib = _lib.load()
+    st = stream_ptr()
+    labels = []
+    mark_in = torch.ones(256 * 400, dtype=torch.float64, device='cuda')
+    mark_out = torch.empty_like(mark_in)
+    pg = None
+    if os.environ.get('ORIANA_FORCE_SHARDED') == '1':
+        import torch.distributed as dist
+        dist.init_process_group('gloo', init_method='file://' + os.path.join(tempfile.mkdtemp(prefix='nest_trace_pg_'), 'rendezvous'), rank=0, world_size=1)
+        pg = dist.group.WORLD
+
+    def entry(label, *calls):
+        torch.cuda.synchronize()
+        labels.append(label)
+        assert lib.oriana_trigamma_f64(ptr(mark_out), ptr(mark_in), 256 * len(labels), st) == 0
+        for fn in calls:
+            fn()
+        torch.cuda.synchronize()
+
+    n, m = 1700, 1100
+    for K in (20, 64, 100):
+        rng = np.random.default_rng(K)
+        dens = rng.beta(1.0, 3.0, size=m)
+        X = (rng.poisson(3.0, size=(n, m)) * (rng.random((n, m)) < dens[None, :])).astype(np.float32)
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+        Dg = d(rng.random((n, m)))
+        lu, lv = d(rng.normal(size=(n, K))), d(rng.normal(size=(m, K)))
+        St, Sh, dq = d(rng.random((m, K)) < 0.7), d(rng.random((m, K))), d(rng.random((n, K)))
+        a1, b1 = rng.gamma(1.0, size=(n, K)), rng.gamma(1.0, size=(m, K))
+        Zi, Zj, Zl = (torch.empty(r, K, device='cuda') for r in (n, m, m))
+        for layout, dd in (('sliced', None), ('hybrid', 0.2)):
+            if dd and not engine.dense_supported(K):
+                continue
+            ct = engine.CountTiles.from_dense(X, 'cuda', side=None if dd else Dg, dense_density=dd)
+            assert (ct.gd > 0) == bool(dd) and ct.ms > 0
+            ws = engine.ZWorkspace(ct, K)
+            tag = 'K%d %s ' % (K, layout)
+            gap = lambda **kw: engine.zq_gap(ws, Zi, Zj, lu, lv, **kw)
+            entry(tag + 'zq_gap', gap)
+            entry(tag + 'zq_gap rows+cols', lambda: gap(phase='rows'), lambda: gap(phase='cols'))
+            entry(tag + 'zq_gap finalize_rows=finalize_cols=False', lambda: gap(finalize_rows=False, finalize_cols=False))
+            segments = []
+            entry(tag + 'zq_gap zj_packed', lambda: gap(zj_packed=True, on_segment=lambda lo, hi: segments.append((lo, hi))))
+            labels[-1] += ' segments=%s' % (segments,)
+            nests = [('plain', {}), ('dq', dict(dq=dq)), ('sparse', dict(S_tilde=St, S_hat=Sh))]
+            if not dd:                                   # (a hybrid layout carries no per-entry weights)
+                nests.append(('sparse+w_nz', dict(S_tilde=St, S_hat=Sh, w_nz=ct.side_nz)))
+            for name, kw in nests:
+                for zl in (Zl, None):
+                    nest = lambda kw=kw, zl=zl, **ph: engine.zq(ws, Zi, Zj, zl, lu, lv, **kw, **ph)
+                    entry(tag + 'zq %s zlog=%d' % (name, zl is not None), nest)
+                    entry(tag + 'zq %s zlog=%d rows+cols' % (name, zl is not None), lambda: nest(phase='rows'),
+                          lambda: nest(phase='cols'))
+            for name in ('GaP', 'ZIGaP', 'SparseGaP', 'SparseZIGaP'):
+                model = getattr(M, name)(X, k=K, init=(a1, b1), dense_density=dd or 0, process_group=pg)
+                assert (model.counts.gd > 0) == bool(dd)
+                entry(tag + name + '.step x2', model.step, model.step)
+    entry('end')
+    if pg is not None:
+        torch.distributed.destroy_process_group()
+    with open(labels_path, 'w') as f:
+        f.write('\n'.join(labels) + '\n')
+
+
+def listing(trace_dir, labels_path, lds=False, nocopy=False):
     """One line per entry: its launches in order as `kernel grid/block` (dimensions of 1 dropped, hipMemsetAsync = memset)."""
     labels = open(labels_path).read().split('\n')
     rows = []
@@ -179,6 +261,8 @@ def listing(trace_dir, labels_path, lds=False):
         block = [int(r['Workgroup_Size_' + a]) for a in 'XYZ']
         grid = [int(r['Grid_Size_' + a]) // max(bl, 1) for a, bl in zip('XYZ', block)]
         if name.startswith('at::native'):         # (torch's own fills between two entries)
+            continue
+        if nocopy and name.startswith('__amd_rocclr_copyBuffer'):
             continue
         if 'k_map_f64<1>' in name:
             if labels[grid[0] - 1].startswith('end'):
@@ -212,7 +296,9 @@ if __name__ == '__main__':
         run(sys.argv[2])
     elif sys.argv[1] in ('passes', 'passes-perf'):
         passes(sys.argv[2], perf=sys.argv[1] == 'passes-perf')
+    elif sys.argv[1] == 'models':
+        models(sys.argv[2])
     elif sys.argv[1] == 'list':
-        listing(sys.argv[2], sys.argv[3], lds=sys.argv[4:] == ['lds'])
+        listing(sys.argv[2], sys.argv[3], lds='lds' in sys.argv[4:], nocopy='nocopy' in sys.argv[4:])
     else:
         sys.exit(diff(sys.argv[2], sys.argv[3]))
