@@ -21,8 +21,7 @@
 //
 // Fragment map of v_mfma_f32_32x32x2_f32: A[m = lane & 31][k = lane >> 5], B[k = lane >> 5][n = lane & 31],
 // D reg v: [m = 8 (v / 4) + 4 (lane >> 5) + v % 4][n = lane & 31].
-#include "common.h"
-#include <type_traits>
+#include "dense_tiles.h"
 // (the ablation switches behind the measurements of DESIGN_HISTORY.md -- ORIANA_ABL32_NOSTORE / _NOSIG / _NOTRANS -- are
 // archived as a patch: tools/experiments/dense_f32_mfma_ablation_switches_r2.diff)
 
@@ -845,13 +844,8 @@ static int launch_sweep(float *D_hat, const double *U, const double *V, const fl
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
     if (splits > 65535 || rb > 0x7fffffffLL) return ORIANA_EINVAL;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_dropout_sweep<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    hipLaunchKernelGGL(k_dropout_sweep<NT>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, V, pi_d,
-                       nzmask, colsum, Vn, DV, n, m, K, KP2, jps);
-    return 0;
+    return launch(k_dropout_sweep<NT>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, V, pi_d, nzmask, colsum,
+                  Vn, DV, n, m, K, KP2, jps);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -989,17 +983,17 @@ __global__ __launch_bounds__(256, 2) void k_dt_times_factor_b16(double *__restri
 template <int NT>
 static int launch_dt_b16(double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K,
                          hipStream_t st) {
+    if (!scratch || !dn::aligned16(scratch)) return ORIANA_EINVAL;
     u4v *img = reinterpret_cast<u4v *>(scratch);
-    hipLaunchKernelGGL(k_split_rows<NT>, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, img, W, n, K);
     const int64_t jb = (m + 127) / 128;
     const int64_t splits0 = pick_splits(jb, (n + 255) / 256);
     int64_t ips = (n + splits0 - 1) / splits0;
     ips = (ips + 63) / 64 * 64;                                  // whole staged groups
     const int64_t splits = (n + ips - 1) / ips;
     if (splits > 65535 || jb > 0x7fffffffLL || (n + 15) / 16 > 0x7fffffffLL) return ORIANA_EINVAL;
-    hipLaunchKernelGGL(k_dt_times_factor_b16<NT>, dim3((unsigned)jb, (unsigned)splits), dim3(256), 0, st, out, D,
-                       (const u4v *)img, n, m, K, ips);
-    return 0;
+    const int rc = launch(k_split_rows<NT>, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, img, W, n, K);
+    if (rc) return rc;
+    return launch(k_dt_times_factor_b16<NT>, dim3((unsigned)jb, (unsigned)splits), dim3(256), 0, st, out, D, img, n, m, K, ips);
 }
 
 // scratch of oriana_dropout_sweep_fused (floats): logit(pi_d) [m rounded up to 64] | first images | second images
@@ -1013,20 +1007,16 @@ static int launch_sweep_b16(float *D_hat, const double *U, const double *V, cons
     const size_t lds = (size_t)L.total;
     u4v *img1 = reinterpret_cast<u4v *>(img_scratch);
     u4v *img2 = Vn ? reinterpret_cast<u4v *>(img_scratch + b16_img_floats(m, KC * 3 * 64)) : nullptr;
-    hipLaunchKernelGGL((k_split_images<NT, KC>), dim3((unsigned)((m + 31) / 32)), dim3(256), 0, st, img1, img2, V, Vn, m, K);
+    const int rc = launch(k_split_images<NT, KC>, dim3((unsigned)((m + 31) / 32)), dim3(256), 0, st, img1, img2, V, Vn, m, K);
+    if (rc) return rc;
     const int64_t rb = (n + 127) / 128;
     const int64_t splits0 = pick_splits(rb, (m + 255) / 256);
     int64_t jps = (m + splits0 - 1) / splits0;
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
     if (splits > 65535 || rb > 0x7fffffffLL) return ORIANA_EINVAL;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_dropout_sweep_b16<NT, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    hipLaunchKernelGGL((k_dropout_sweep_b16<NT, KC>), dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U,
-                       (const u4v *)img1, lg, nzmask, colsum, (const u4v *)img2, DV, n, m, K, jps);
-    return 0;
+    return launch(k_dropout_sweep_b16<NT, KC>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, img1, lg, nzmask,
+                  colsum, img2, DV, n, m, K, jps);
 }
 
 template <int NT, int GQ>
@@ -1037,23 +1027,8 @@ static int launch_dt(double *out, const float *D, const double *W, int64_t n, in
     ips = (ips + 63) / 64 * 64;                                  // whole staged chunks
     const int64_t splits = (n + ips - 1) / ips;
     if (splits > 65535 || jb > 0x7fffffffLL) return ORIANA_EINVAL;
-    hipLaunchKernelGGL((k_dt_times_factor_f32<NT, GQ>), dim3((unsigned)jb, (unsigned)splits), dim3(256), 0, st, out, D, W,
-                       n, m, K, ips);
-    return 0;
+    return launch(k_dt_times_factor_f32<NT, GQ>, dim3((unsigned)jb, (unsigned)splits), dim3(256), 0, st, out, D, W, n, m, K, ips);
 }
-
-// 32 < K <= 100 (gene count a multiple of 4): csrc/dense_zi.hip
-namespace dn {
-bool zi_supported(int64_t m, int64_t K);
-bool zi_dt_supported(int64_t m, int64_t K);
-int64_t zi_sweep_image_floats(int64_t m);
-int64_t zi_dt_image_floats(int64_t n);
-int zi_sweep(float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
-             double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st);
-int64_t zi_tiles_words(int64_t n, int64_t m);
-int zi_tiles(uint32_t *out, const uint32_t *nzmask, int64_t n, int64_t m, hipStream_t st);
-int zi_dt(double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st);
-}  // namespace dn
 
 }  // namespace oriana
 
@@ -1061,10 +1036,9 @@ using namespace oriana;
 
 extern "C" int64_t oriana_dropout_sweep_scratch_floats(int64_t m, int64_t K) {
     if (m < 0 || K < 0) return 0;
-    // logit(pi_d) + the two operand images of the bf16 path at their largest (K <= 64: 4 k chunks, 2 n tiles; or the
-    // images of csrc/dense_zi.hip for 64 < K <= 100)
+    // logit(pi_d) + the two operand images of the b16 family at their largest (4 k chunks, 2 n tiles), or those of the tiles family
     const int64_t a = b16_img_floats(m, 4 * 3 * 64) + b16_img_floats(m, 2 * 2 * 3 * 64);
-    const int64_t b = (K > 32 && K <= 100) ? dn::zi_sweep_image_floats(m) : 0;
+    const int64_t b = dn::zi_may_use_tiles(oriana_kpad(K)) ? dn::zi_sweep_image_floats(m) : 0;
     return 3 * ((m + 63) / 64 * 64) + (a > b ? a : b);       // logits, scaled logits + floors (dense_zi.hip), images
 }
 
@@ -1095,39 +1069,29 @@ extern "C" int oriana_dropout_sweep_fused_tiles(float *D_hat, const double *U, c
     if (arithmetic != ORIANA_MATRIX_F32 && arithmetic != ORIANA_MATRIX_BF16X3) return ORIANA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int64_t mpad = (m + 63) / 64 * 64;
+    // scratch: logits | scaled logits | floors (tiles) | operand images
+    const float *pi_d = scratch, *lgs = scratch + mpad;
+    float *img = scratch + 3 * mpad;
     hipLaunchKernelGGL(k_logit_f32, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, scratch, scratch + mpad, scratch + 2 * mpad,
                        pi_d64, m);
-    const float *pi_d = scratch;
-    scratch += mpad;                                   // (the scaled logits and the floors; the operand images follow them)
-    int rc = ORIANA_EKRANGE;
-    if (arithmetic == ORIANA_MATRIX_BF16X3 && V_next && nztiles && dn::zi_supported(m, K))
-        rc = dn::zi_sweep(D_hat, U, V, scratch, mpad, nztiles, colsum, V_next, DV_next, scratch + 2 * mpad, n, m, (int)K, st);
-    scratch += mpad;
-    if (rc != ORIANA_EKRANGE) {
-        // (done, or failed for good; ORIANA_EKRANGE = not this kernel's case, e.g. a D_hat that is not 16-byte aligned)
-    } else if (arithmetic == ORIANA_MATRIX_BF16X3 && K <= 64) {
-        float *img = scratch + mpad;
-        switch ((int)((K + 15) / 16)) {
-            case 1: rc = launch_sweep_b16<1, 1>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st); break;
-            case 2: rc = launch_sweep_b16<1, 2>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st); break;
-            case 3: rc = launch_sweep_b16<2, 3>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st); break;
-            default: rc = launch_sweep_b16<2, 4>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st); break;
-        }
-    } else {
-        switch ((int)((K + 31) / 32)) {
-            case 1: rc = launch_sweep<1>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st); break;
-            case 2: rc = launch_sweep<2>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st); break;
-            case 3: rc = launch_sweep<3>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st); break;
-            default: rc = launch_sweep<4>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st); break;
-        }
-    }
-    if (rc) return rc;
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return with_variant<ORIANA_MATRIX_F32, ORIANA_MATRIX_BF16X3>(arithmetic, [&](auto A) {
+        return dn::with_cfg<1, dn::ZI_KP_MAX / 16>(dn::kc_tail(oriana_kpad(K)), [&](auto c) {
+            return dn::zi_first<dn::ZiOp::update, decltype(c)::KP, decltype(A)::value>(
+                [&](dn::ZiFam f) { return dn::zi_update_ok(f, D_hat, lgs, nztiles, V_next, DV_next, m); },
+                [&](auto p) {
+                    using P = decltype(p);
+                    if constexpr (P::fam == dn::ZiFam::tiles)
+                        return dn::zi_sweep({P::a, P::b}, D_hat, U, V, lgs, mpad, nztiles, colsum, V_next, DV_next, img, n, m, (int)K, st);
+                    else if constexpr (P::fam == dn::ZiFam::b16)
+                        return launch_sweep_b16<P::a, P::b>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st);
+                    else
+                        return launch_sweep<P::a>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st);
+                });
+        });
+    });
 }
 
-// the round-2 entry: without the per-lane flags (oriana_nzmask_tiles) the K = 33 .. 100 kernel of csrc/dense_zi.hip does not apply (K <= 64 takes
-// the bf16 kernels of this file, the rest the float32 matrix instruction)
+// the round-2 entry: without the per-lane flags (oriana_nzmask_tiles) the tiles family does not apply (dn::zi_update_ok)
 extern "C" int oriana_dropout_sweep_fused(float *D_hat, const double *U, const double *V, const double *pi_d64,
                                           const uint32_t *nzmask, double *colsum, const double *V_next, double *DV_next,
                                           float *scratch, int arithmetic, int64_t n, int64_t m, int64_t K, void *stream) {
@@ -1137,8 +1101,8 @@ extern "C" int oriana_dropout_sweep_fused(float *D_hat, const double *U, const d
 
 extern "C" int64_t oriana_dense_t_scratch_floats(int64_t n, int64_t K) {
     if (n < 0 || K < 0) return 0;
-    const int64_t a = ((n + 15) / 16 + 4) * (int64_t)(2 * 3 * 64) * 4;       // operand images of W at their largest (K <= 64)
-    const int64_t b = (K > 32 && K <= 100) ? dn::zi_dt_image_floats(n) : 0;   // csrc/dense_zi.hip
+    const int64_t a = ((n + 15) / 16 + 4) * (int64_t)(2 * 3 * 64) * 4;       // operand images of W at the b16 family's largest
+    const int64_t b = dn::zi_may_use_tiles(oriana_kpad(K)) ? dn::zi_dt_image_floats(n) : 0;
     return a > b ? a : b;
 }
 
@@ -1148,25 +1112,17 @@ extern "C" int oriana_dense_t_times_factor_f32(double *out, const float *D, cons
     if (K > 128) return ORIANA_EKRANGE;
     if (n == 0 || m == 0) return 0;
     if (!out || !D || !W) return ORIANA_EINVAL;
-    if (arithmetic != ORIANA_MATRIX_F32 && arithmetic != ORIANA_MATRIX_BF16X3) return ORIANA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = ORIANA_EKRANGE;
-    if (arithmetic == ORIANA_MATRIX_BF16X3 && scratch && ((uintptr_t)scratch & 15) == 0 && dn::zi_dt_supported(m, K))
-        rc = dn::zi_dt(out, D, W, scratch, n, m, (int)K, st);
-    if (rc != ORIANA_EKRANGE) {
-    } else if (arithmetic == ORIANA_MATRIX_BF16X3 && K <= 64) {
-        if (!scratch || ((uintptr_t)scratch & 15) != 0) return ORIANA_EINVAL;
-        if (K <= 32) rc = launch_dt_b16<1>(out, D, W, scratch, n, m, (int)K, st);
-        else rc = launch_dt_b16<2>(out, D, W, scratch, n, m, (int)K, st);
-    } else {
-        switch ((int)((K + 31) / 32)) {
-            case 1: rc = launch_dt<1, 4>(out, D, W, n, m, (int)K, st); break;
-            case 2: rc = launch_dt<2, 2>(out, D, W, n, m, (int)K, st); break;
-            case 3: rc = launch_dt<3, 1>(out, D, W, n, m, (int)K, st); break;
-            default: rc = launch_dt<4, 1>(out, D, W, n, m, (int)K, st); break;
-        }
-    }
-    if (rc) return rc;
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return with_variant<ORIANA_MATRIX_F32, ORIANA_MATRIX_BF16X3>(arithmetic, [&](auto A) {
+        return dn::with_cfg<1, dn::ZI_KP_MAX / 16>(dn::kc_tail(oriana_kpad(K)), [&](auto c) {
+            return dn::zi_first<dn::ZiOp::dt, decltype(c)::KP, decltype(A)::value>(
+                [&](dn::ZiFam f) { return dn::zi_dt_ok(f, D, scratch, m); },
+                [&](auto p) {
+                    using P = decltype(p);
+                    if constexpr (P::fam == dn::ZiFam::tiles) return dn::zi_dt({P::a, P::b}, out, D, W, scratch, n, m, (int)K, st);
+                    else if constexpr (P::fam == dn::ZiFam::b16) return launch_dt_b16<P::a>(out, D, W, scratch, n, m, (int)K, st);
+                    else return launch_dt<P::a, P::b>(out, D, W, n, m, (int)K, st);
+                });
+        });
+    });
 }

@@ -10,7 +10,7 @@
 // Fragment maps of v_mfma_f64_16x16x4_f64 (one f64 per lane for A and B, four for C/D):
 //   A[row = lane & 15][k = lane >> 4],  B[k = lane >> 4][col = lane & 15],
 //   D reg r: [row = (lane >> 4) + 4 r][col = lane & 15].
-#include "common.h"
+#include "launch.h"
 // (the ablation switches behind the round-1 measurements -- ORIANA_ABL_NOMFMA / _NOSIG / _NOSTORE / _NOMASK -- are archived as
 // a patch: tools/experiments/dense_f32_mfma_ablation_switches_r2.diff)
 
@@ -335,15 +335,12 @@ static int launch_dtf(double *out, const float *D, const double *W, int64_t P, i
     qps = (qps + QC - 1) / QC * QC;
     splits = (Q + qps - 1) / qps;
     const size_t lds = (size_t)2 * QC * (NT * 16 + 2) * sizeof(double);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_dense_times_factor<NT, T, TRANS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    hipLaunchKernelGGL((k_dense_times_factor<NT, T, TRANS>), dim3((unsigned)pb, (unsigned)splits), dim3(256), lds, st,
-                       out, D, W, P, Q, K, qps, splits > 1 ? 1 : 0);
-    return 0;
+    return launch(k_dense_times_factor<NT, T, TRANS>, dim3((unsigned)pb, (unsigned)splits), dim3(256), lds, st, out, D, W, P, Q, K, qps,
+                  splits > 1 ? 1 : 0);
 }
+
+// NT = ceil(K / 16) tiles of factors (9 .. 16 run as 16) -> T tiles of p per wave, T * NT <= 16 accumulator tiles
+constexpr int dtf_tiles(int nt) { return nt <= 4 ? 4 : nt == 5 ? 3 : nt <= 8 ? 2 : 1; }
 
 }  // namespace oriana
 
@@ -358,28 +355,11 @@ extern "C" int oriana_dense_times_factor(double *out, const float *D, const doub
     if ((P + 63) / 64 > 0x7fffffffLL) return ORIANA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int nt = (int)((K + 15) / 16);
-    int rc = 0;
-#define ORIANA_DTF(NT_, T_)                                                                      \
-    do {                                                                                         \
-        if (trans) rc = launch_dtf<NT_, T_, 1>(out, D, W, P, Q, (int)K, st);                      \
-        else rc = launch_dtf<NT_, T_, 0>(out, D, W, P, Q, (int)K, st);                            \
-    } while (0)
-    // NT = ceil(K / 16) tiles of factors, T tiles of p per wave with T * NT <= 16 accumulator tiles
-    switch (nt) {
-        case 1: ORIANA_DTF(1, 4); break;
-        case 2: ORIANA_DTF(2, 4); break;
-        case 3: ORIANA_DTF(3, 4); break;
-        case 4: ORIANA_DTF(4, 4); break;
-        case 5: ORIANA_DTF(5, 3); break;
-        case 6: ORIANA_DTF(6, 2); break;
-        case 7: ORIANA_DTF(7, 2); break;
-        case 8: ORIANA_DTF(8, 2); break;
-        default: ORIANA_DTF(16, 1); break;
-    }
-#undef ORIANA_DTF
-    if (rc) return rc;
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return with_variant<1, 2, 3, 4, 5, 6, 7, 8, 16>(nt <= 8 ? nt : 16, [&](auto NT) {
+        return with_variant<0, 1>(trans ? 1 : 0, [&](auto TRANS) {
+            return launch_dtf<decltype(NT)::value, dtf_tiles(decltype(NT)::value), decltype(TRANS)::value>(out, D, W, P, Q, (int)K, st);
+        });
+    });
 }
 
 template <int MODE>
@@ -391,17 +371,13 @@ static int launch_dropout_fused(double *p_d, float *D_hat, const double *U, cons
     const size_t lds = (size_t)64 * us * sizeof(double);
     const int64_t ncb = (m + 255) / 256;
     const int64_t slab = 65535LL * 256;                  // row blocks in slabs of 65535 * 256 rows
-    if (lds > 64 * 1024)
-        ORIANA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dropout_fused<MODE>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (int64_t r0 = 0; r0 < n; r0 += slab) {
         const int64_t rows = (n - r0 < slab) ? n - r0 : slab;
-        hipLaunchKernelGGL(k_dropout_fused<MODE>, dim3((unsigned)ncb, (unsigned)((rows + 255) / 256)), dim3(256), lds,
-                           (hipStream_t)stream, p_d ? p_d + r0 * m : nullptr, D_hat ? D_hat + r0 * m : nullptr,
-                           U + r0 * K, V, pi_d, nzmask ? nzmask + (r0 / 32) * m : nullptr, colsum, rows, m, (int)K, KS,
-                           us);
+        const int rc = launch(k_dropout_fused<MODE>, dim3((unsigned)ncb, (unsigned)((rows + 255) / 256)), dim3(256), lds,
+                              (hipStream_t)stream, p_d ? p_d + r0 * m : nullptr, D_hat ? D_hat + r0 * m : nullptr, U + r0 * K, V,
+                              pi_d, nzmask ? nzmask + (r0 / 32) * m : nullptr, colsum, rows, m, (int)K, KS, us);
+        if (rc) return rc;
     }
-    ORIANA_LAUNCH_CHECK();
     return 0;
 }
 

@@ -708,59 +708,24 @@ __global__ __launch_bounds__(256) void k_dn_metric(const uint16_t *__restrict__ 
 template <int KC, int TAIL> constexpr int row_lds_bytes() { return 3 * Cfg<KC, TAIL>::PV * 16 + NW * 32 * TS * 4; }
 template <int KC, int TAIL> constexpr int col_lds_bytes() { return 3 * Cfg<KC, TAIL>::PU * 16 + 2 * NW * 256 * 16; }
 
-template <typename Fn>
-static int set_lds(Fn fn, int bytes) {
-    if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    return 0;
-}
-
 }  // namespace dn
 }  // namespace oriana
 
 using namespace oriana;
 using namespace oriana::dn;
 
-// compiled (KC, TAIL) pairs: Kp = 16 KC + 4 TAIL, i.e. every K <= 100
-#define ORIANA_DN_FOR_CFG(KC_, TL_, CALL)                                     \
-    do {                                                                      \
-        if (KC_ == 6 && TL_ == 1) { CALL(6, 1); }                             \
-        else if (KC_ == 6 && TL_ == 0) { CALL(6, 0); }                        \
-        else if (KC_ == 5 && TL_ == 1) { CALL(5, 1); }                        \
-        else if (KC_ == 5 && TL_ == 0) { CALL(5, 0); }                        \
-        else if (KC_ == 4 && TL_ == 1) { CALL(4, 1); }                        \
-        else if (KC_ == 4 && TL_ == 0) { CALL(4, 0); }                        \
-        else if (KC_ == 3 && TL_ == 1) { CALL(3, 1); }                        \
-        else if (KC_ == 3 && TL_ == 0) { CALL(3, 0); }                        \
-        else if (KC_ == 2 && TL_ == 1) { CALL(2, 1); }                        \
-        else if (KC_ == 2 && TL_ == 0) { CALL(2, 0); }                        \
-        else if (KC_ == 1 && TL_ == 1) { CALL(1, 1); }                        \
-        else if (KC_ == 1 && TL_ == 0) { CALL(1, 0); }                        \
-        else return ORIANA_EKRANGE;                                           \
-    } while (0)
-
-static bool dn_cfg(int64_t K, int *kc, int *tl, int *kp) {
-    const int64_t Kp = oriana_kpad(K);
-    if (Kp == 0 || Kp > 100 || (Kp % 16 != 0 && Kp % 16 != 4)) return false;   // (Kp = 112: three image buffers exceed LDS)
-    *kc = (int)(Kp / 16); *tl = (Kp % 16 == 4) ? 1 : 0; *kp = (int)Kp;
-    return *kc >= 1 && *kc <= 6;
-}
+// the (KC, TAIL) of K for the kernels of this file: f(Cfg<KC, TAIL>{}), ORIANA_EKRANGE for a width they do not serve
+template <typename F>
+static int for_cfg(int64_t K, F &&f) { return with_cfg<DN_KC_MIN, DN_KC_MAX>(kc_tail(oriana_kpad(K)), f); }
 
 extern "C" int oriana_dense_supported(int64_t K) {
-    int kc, tl, kp;
-    return dn_cfg(K, &kc, &tl, &kp) ? 1 : 0;
+    return for_cfg(K, [](auto) { return 0; }) == 0 ? 1 : 0;
 }
 
 // 16-byte pieces of one tile's operand image: side 0 = gene side (both images), 1 = cell side
 extern "C" int64_t oriana_dense_image_pieces(int64_t K, int side) {
-    int kc, tl, kp;
-    if (!dn_cfg(K, &kc, &tl, &kp)) return 0;
     int64_t out = 0;
-#define ORIANA_DN_CALL(KC, TL) out = side ? Cfg<KC, TL>::PU : Cfg<KC, TL>::PV
-    ORIANA_DN_FOR_CFG(kc, tl, ORIANA_DN_CALL);
-#undef ORIANA_DN_CALL
+    for_cfg(K, [&](auto c) { out = side ? decltype(c)::PU : decltype(c)::PV; return 0; });
     return out;
 }
 
@@ -789,23 +754,19 @@ extern "C" int oriana_dense_pack(const void *X, int xdtype, int64_t rows, int64_
 
 extern "C" int oriana_dense_images2(void *img, const float *F, const float *F2, int64_t rows, int64_t K, int side,
                                     void *stream) {
-    int kc, tl, kp;
     if (rows < 0 || K <= 0) return ORIANA_EINVAL;
-    if (!dn_cfg(K, &kc, &tl, &kp)) return ORIANA_EKRANGE;
+    if (!oriana_dense_supported(K)) return ORIANA_EKRANGE;
     if (rows == 0) return 0;
     if (!img || !F) return ORIANA_EINVAL;
     if (!F2) F2 = F;
     const unsigned tiles = (unsigned)((rows + 31) / 32);
     hipStream_t s = (hipStream_t)stream;
-#define ORIANA_DN_CALL(KC, TL)                                                                                              \
-    do {                                                                                                                    \
-        if (side) hipLaunchKernelGGL((k_dn_images<KC, TL, false>), dim3(tiles), dim3(512), 0, s, (u4v *)img, F, F2, rows, kp); \
-        else hipLaunchKernelGGL((k_dn_images<KC, TL, true>), dim3(tiles), dim3(512), 0, s, (u4v *)img, F, F2, rows, kp);     \
-    } while (0)
-    ORIANA_DN_FOR_CFG(kc, tl, ORIANA_DN_CALL);
-#undef ORIANA_DN_CALL
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return for_cfg(K, [&](auto c) {
+        using C = decltype(c);
+        return with_variant<0, 1>(side ? 1 : 0, [&](auto CELL) {
+            return launch(k_dn_images<C::kc, C::tl, decltype(CELL)::value == 0>, dim3(tiles), dim3(512), 0, s, (u4v *)img, F, F2, rows, C::KP);
+        });
+    });
 }
 
 extern "C" int oriana_dense_images(void *img, const float *F, int64_t rows, int64_t K, int side, void *stream) {
@@ -815,9 +776,8 @@ extern "C" int oriana_dense_images(void *img, const float *F, int64_t rows, int6
 extern "C" int oriana_dense_row_pass_tail(const oriana_dense *d, const float *FU, const void *imgV, float *R, float *S,
                                           int32_t *flag, int64_t K, int64_t gene_splits, int64_t tail_nfull, int64_t tail_parts,
                                           const float *den_min, void *stream) {
-    int kc, tl, kp;
     if (!dense_ok(d) || K <= 0 || gene_splits < 1) return ORIANA_EINVAL;
-    if (!dn_cfg(K, &kc, &tl, &kp)) return ORIANA_EKRANGE;
+    if (!oriana_dense_supported(K)) return ORIANA_EKRANGE;
     if (d->gd == 0 || d->n == 0) return 0;
     if (!FU || !imgV || !R || !S || !flag) return ORIANA_EINVAL;
     const int ngt = (int)(d->gd / 32);
@@ -836,25 +796,17 @@ extern "C" int oriana_dense_row_pass_tail(const oriana_dense *d, const float *FU
         tail_nfull = nblk; tail_parts = 1;
     }
     hipStream_t s = (hipStream_t)stream;
-#define ORIANA_DN_CALL(KC, TL)                                                                                              \
-    do {                                                                                                                    \
-        constexpr int lb = row_lds_bytes<KC, TL>();                                                                         \
-        const int rc = set_lds(k_dn_row<KC, TL>, lb);                                                                       \
-        if (rc) return rc;                                                                                                  \
-        hipLaunchKernelGGL((k_dn_row<KC, TL>), grid, dim3(512), lb, s, d->x, S, FU, (const u4v *)imgV, R, flag, d->n, ngt,  \
-                           kp, per, splits > 1 ? 1 : 0, (int)tail_nfull, (int)tail_parts, den_min);                         \
-    } while (0)
-    ORIANA_DN_FOR_CFG(kc, tl, ORIANA_DN_CALL);
-#undef ORIANA_DN_CALL
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return for_cfg(K, [&](auto c) {
+        using C = decltype(c);
+        return launch(k_dn_row<C::kc, C::tl>, grid, dim3(512), (size_t)row_lds_bytes<C::kc, C::tl>(), s, d->x, S, FU, (const u4v *)imgV, R,
+                      flag, d->n, ngt, C::KP, per, splits > 1 ? 1 : 0, (int)tail_nfull, (int)tail_parts, den_min);
+    });
 }
 
 extern "C" int oriana_dense_col_pass(const oriana_dense *d, const void *imgU, const float *S, float *C, int64_t K,
                                      int64_t cell_splits, void *stream) {
-    int kc, tl, kp;
     if (!dense_ok(d) || K <= 0 || cell_splits < 1) return ORIANA_EINVAL;
-    if (!dn_cfg(K, &kc, &tl, &kp)) return ORIANA_EKRANGE;
+    if (!oriana_dense_supported(K)) return ORIANA_EKRANGE;
     if (d->gd == 0 || d->n == 0) return 0;
     if (!imgU || !S || !C) return ORIANA_EINVAL;
     const int ngt = (int)(d->gd / 32);
@@ -865,18 +817,11 @@ extern "C" int oriana_dense_col_pass(const oriana_dense *d, const void *imgU, co
     const int64_t groups = (ngt + NW - 1) / NW;
     if (splits * groups > 0x7fffffffLL) return ORIANA_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-#define ORIANA_DN_CALL(KC, TL)                                                                                              \
-    do {                                                                                                                    \
-        constexpr int lb = col_lds_bytes<KC, TL>();                                                                         \
-        const int rc = set_lds(k_dn_col<KC, TL>, lb);                                                                       \
-        if (rc) return rc;                                                                                                  \
-        hipLaunchKernelGGL((k_dn_col<KC, TL>), dim3((unsigned)(splits * groups)), dim3(512), lb, s, S, (const u4v *)imgU,   \
-                           C, nct, ngt, kp, per, (int)splits);                                                              \
-    } while (0)
-    ORIANA_DN_FOR_CFG(kc, tl, ORIANA_DN_CALL);
-#undef ORIANA_DN_CALL
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return for_cfg(K, [&](auto c) {
+        using Cf = decltype(c);
+        return launch(k_dn_col<Cf::kc, Cf::tl>, dim3((unsigned)(splits * groups)), dim3(512), (size_t)col_lds_bytes<Cf::kc, Cf::tl>(), s, S,
+                      (const u4v *)imgU, C, nct, ngt, Cf::KP, per, (int)splits);
+    });
 }
 
 extern "C" int oriana_dense_fixup_variant(const oriana_dense *d, const int32_t *flag, float *S, const float *logU,
@@ -913,12 +858,6 @@ extern "C" int oriana_dense_metric(const oriana_dense *d, const double *U, const
     if ((U == nullptr) != (V == nullptr) || (U && !out4) || (colsum && !colnnz)) return ORIANA_EINVAL;
     const int ngt = (int)(d->gd / 32);
     const size_t lb = U ? (size_t)64 * K * sizeof(double) : 0;
-    if (lb > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_dn_metric, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    hipLaunchKernelGGL(k_dn_metric, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), lb, (hipStream_t)stream, d->x, U,
-                       V, row_perm, col_perm, colsum, colnnz, out2, out4, d->n, ngt, (int)K);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
+    return launch(k_dn_metric, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), lb, (hipStream_t)stream, d->x, U, V,
+                  row_perm, col_perm, colsum, colnnz, out2, out4, d->n, ngt, (int)K);
 }

@@ -1,8 +1,10 @@
 // dense_tiles.h -- pieces shared by the matrix-core kernels over dense 32 x 32 tiles (dense_pass.hip: the dense genes of
-// pCMF's responsibility pass; dense_zi.hip: the D update and D_hat^T U_hat of the ZI models for 64 < K <= 100): bf16 x 3
-// splits, the six-product macro, accumulator geometry, operand image layout, LDS-DMA copies.
+// pCMF's responsibility pass, Kp <= 100; dense_zi.hip: the D update and D_hat^T U_hat of the ZI models for the widths
+// zi_candidate below gives them): bf16 x 3 splits, the six-product macro, accumulator geometry, operand image layout, LDS-DMA
+// copies; and, host side, the (KC, TAIL) dispatcher and the rule that says which kernel family serves which ZI product.
 #pragma once
-#include "common.h"
+#include "launch.h"
+#include <utility>
 
 namespace oriana {
 namespace dn {
@@ -72,6 +74,7 @@ struct Cfg {
     static constexpr int PVZ = (PV_RAW + 2 * 64 + NW * 64 - 1) / (NW * 64) * (NW * 64);
     static constexpr int PU = (PU_RAW + NW * 64 - 1) / (NW * 64) * (NW * 64);
     static constexpr int KM = 16 * KC;                                    // factors on the matrix core
+    static constexpr int kc = KC, tl = TAIL, KP = 16 * KC + 4 * TAIL;
 };
 
 // LDS-DMA copy of one image (P pieces, a multiple of 8 x 64) by the 8 waves of a work-group
@@ -84,6 +87,135 @@ __device__ __forceinline__ void image_dma(const u4v *__restrict__ src, u4v *dst_
                                          (__attribute__((address_space(3))) void *)(dst_lds + piece), 16, 0, 0);
     }
 }
+
+
+// ------------------------------------------------------------------------------------------
+// host side: padded width -> (KC, TAIL) -> template arguments
+// ------------------------------------------------------------------------------------------
+// Kp = 16 KC + 4 TAIL (oriana_kpad: 16 t, or 16 t + 4 up to 100); {0, 0} for a width that has no such form
+struct KcTl { int kc, tl; };
+constexpr KcTl kc_tail(int64_t Kp) {
+    return (Kp > 0 && (Kp % 16 == 0 || Kp % 16 == 4)) ? KcTl{(int)(Kp / 16), Kp % 16 == 4 ? 1 : 0} : KcTl{0, 0};
+}
+
+// run-time (kc, tl) -> f(Cfg<KC, TAIL>{}) for KC_MIN <= KC <= KC_MAX, ORIANA_EKRANGE outside (with_variant's form)
+template <int KC_MIN, typename F, int... I>
+static int with_cfg_seq(KcTl c, F &&f, std::integer_sequence<int, I...>) {
+    int rc = ORIANA_EKRANGE;
+    (void)((c.kc == KC_MIN + I / 2 && c.tl == I % 2 && ((rc = f(Cfg<KC_MIN + I / 2, I % 2>{})), true)) || ...);
+    return rc;
+}
+template <int KC_MIN, int KC_MAX, typename F>
+static int with_cfg(KcTl c, F &&f) {
+    return with_cfg_seq<KC_MIN>(c, f, std::make_integer_sequence<int, 2 * (KC_MAX - KC_MIN + 1)>{});
+}
+
+// the dense genes (dense_pass.hip): every Kp <= 100  (Kp = 112: three image buffers exceed LDS)
+constexpr int DN_KC_MIN = 1, DN_KC_MAX = 6;
+
+// ------------------------------------------------------------------------------------------
+// Which kernel family serves which dense product of a ZI sweep.  zi_candidate is the whole rule: the two C entries
+// (dense_f32.hip) run the first candidate whose run-time preconditions hold, the launchers name a kernel template only under
+// `if constexpr` on its answers (what is compiled is what can be launched), the scratch-size entries ask it too, and DESIGN.md
+// section 0 shows it as a table.
+// ------------------------------------------------------------------------------------------
+enum class ZiOp { update, dt };     // the D update with the next sweep's D_hat V_hat;  out += D_hat^T W
+enum class ZiFam {
+    none,       // no kernel: ORIANA_EKRANGE
+    tiles,      // dense_zi.hip: k_zi_row / k_zi_col<KC = a, TAIL = b>, bf16 x 3 over 32 x 32 tiles with LDS-DMA
+    b16,        // dense_f32.hip: k_dropout_sweep_b16<NT = a, KC = b> / k_dt_times_factor_b16<NT = a>
+    f32         // dense_f32.hip: k_dropout_sweep<NT = a> / k_dt_times_factor_f32<NT = a, GQ = b>, the float32 matrix instruction
+};
+struct ZiCand { ZiFam fam; int a, b; };
+constexpr int ZI_MAX_CAND = 3;
+constexpr int ZI_KP_MAX = 128;      // the widest product of either entry; ZI_KC_* = the (KC, TAIL) range dense_zi.hip compiles from
+constexpr int ZI_KC_MIN = 3, ZI_KC_MAX = 6;
+
+// candidate i (in the order they are tried) for the padded width kp under `arithmetic`; none from the end of the list on
+constexpr ZiCand zi_candidate(ZiOp op, int kp, int arithmetic, int i) {
+    ZiCand list[ZI_MAX_CAND + 1] = {};
+    int n = 0;
+    const KcTl t = kc_tail(kp);
+    if (t.kc == 0 || kp > ZI_KP_MAX || i < 0 || i >= ZI_MAX_CAND) return ZiCand{ZiFam::none, 0, 0};
+    if (arithmetic == ORIANA_MATRIX_BF16X3) {
+        // tiles from K = 33 (Kp = 36) to Kp = 100.  Measured at 100k x 20k against the b16 kernels (tools/perf_zi_per_k.py, round 6's
+        // build): D update 3.37 against 4.11 ms at K = 48, 3.65 against 4.00 ms at K = 50, 3.72 against 4.11 ms at K = 64; D^T U 1.82
+        // against 2.00 ms at K = 48 but 2.06 against 1.98 ms at K = 50 WITH the tail factors' 4 x 4 x 1 instructions: below 65 the
+        // transposed product takes the next whole chunk instead.
+        if (kp >= 36 && kp <= 100) {
+            if (op == ZiOp::update) {
+                // Kp = 48 .. 100 (k_zi_row has no KC = 2: Kp = 36 goes on to b16).  [r6] Kp = 64 (K = 53 .. 64) too: with room for the
+                // flag / logit pieces behind the images (Cfg::PVZ) and the copies issued at the top of the tile, k_zi_row<4, 0> takes
+                // 3.68 ms where the b16 kernel takes 4.11 (K = 49 .. 52 stays on <3, 1> with the tail riding in the last factor tile:
+                // 3.65 against 3.72 ms zero-padded to four chunks)
+                if (t.kc >= ZI_KC_MIN) list[n++] = ZiCand{ZiFam::tiles, t.kc, t.tl};
+            } else if (t.tl && t.kc <= 3) {
+                // [r6] D_hat^T W below K = 65: Kp = 36 and 52 (K = 50: configs[2]) take the NEXT whole chunk of 16 with zero-padded
+                // factors instead of the tail of four -- k_zi_col<4, 0> 1.50 ms against 1.67 ms for k_dt_times_factor_b16 inside the
+                // configs[2] sweep (the D update itself is faster WITH the tail: 3.49 against 3.94 ms; profiles/r06_zi_k52_ab.txt)
+                list[n++] = ZiCand{ZiFam::tiles, t.kc + 1, 0};
+            } else {
+                list[n++] = ZiCand{ZiFam::tiles, t.kc, t.tl};
+            }
+        }
+        if (kp <= 64) {             // three-way splits on v_mfma_f32_32x32x16_bf16: KC chunks of 16 factors, NT tiles of 32
+            const int kc = (kp + 15) / 16;
+            list[n++] = op == ZiOp::update ? ZiCand{ZiFam::b16, (kc + 1) / 2, kc} : ZiCand{ZiFam::b16, kp <= 32 ? 1 : 2, 0};
+        }
+    }
+    {                               // ORIANA_MATRIX_F32, and what bf16 x 3 leaves: NT tiles of 32 factors; GQ gene quads per wave
+        const int nt = (kp + 31) / 32;
+        list[n++] = op == ZiOp::update ? ZiCand{ZiFam::f32, nt, 0} : ZiCand{ZiFam::f32, nt, nt == 1 ? 4 : nt == 2 ? 2 : 1};
+    }
+    return list[i];
+}
+// some product of this width may run on the tiles family: the scratch entries leave room for its images
+constexpr bool zi_may_use_tiles(int64_t kp) {
+    if (kp <= 0 || kp > ZI_KP_MAX) return false;
+    return zi_candidate(ZiOp::update, (int)kp, ORIANA_MATRIX_BF16X3, 0).fam == ZiFam::tiles ||
+           zi_candidate(ZiOp::dt, (int)kp, ORIANA_MATRIX_BF16X3, 0).fam == ZiFam::tiles;
+}
+// the rule can answer tiles<KC, TAIL> for this product at some width: the instantiations dense_zi.hip holds
+constexpr bool zi_tiles_reachable(ZiOp op, int kc, int tl) {
+    for (int kp = 16; kp <= ZI_KP_MAX; kp += 4) {
+        const ZiCand c = zi_candidate(op, kp, ORIANA_MATRIX_BF16X3, 0);
+        if (c.fam == ZiFam::tiles && c.a == kc && c.b == tl) return true;
+    }
+    return false;
+}
+
+// Run-time preconditions of a family; a candidate that fails them is passed over.  tiles moves 16-byte pieces of D_hat rows,
+// logits, flags and images (gene count a multiple of 4, aligned pointers); the D update is the fused form only (per-lane flags
+// of oriana_nzmask_tiles, V_next and DV_next given) and keeps its tile offsets in 32 bits.  b16 and f32 take everything the
+// entries admit.
+static inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+static inline bool zi_update_ok(ZiFam f, const float *D_hat, const float *lgit, const uint32_t *nztiles, const double *Vn,
+                                const double *DV, int64_t m) {
+    return f != ZiFam::tiles || (Vn && DV && nztiles && m % 4 == 0 && m <= 16000000 && aligned16(D_hat, lgit, nztiles));
+}
+static inline bool zi_dt_ok(ZiFam f, const float *D, const float *scratch, int64_t m) {
+    return f != ZiFam::tiles || (scratch && m % 4 == 0 && aligned16(D, scratch));
+}
+
+// run(ZiPick) for the first candidate of <OP, KP, ARITH> whose preconditions hold (ok(family)); ORIANA_EKRANGE if there is none
+template <ZiFam F, int A, int B> struct ZiPick { static constexpr ZiFam fam = F; static constexpr int a = A, b = B; };
+template <ZiOp OP, int KP, int ARITH, int I = 0, typename Ok, typename Run>
+static int zi_first(Ok &&ok, Run &&run) {
+    constexpr ZiCand c = zi_candidate(OP, KP, ARITH, I);
+    if constexpr (c.fam == ZiFam::none) return ORIANA_EKRANGE;
+    else return ok(c.fam) ? run(ZiPick<c.fam, c.a, c.b>{}) : zi_first<OP, KP, ARITH, I + 1>(ok, run);
+}
+
+// dense_zi.hip, called from the entries of dense_f32.hip
+int64_t zi_sweep_image_floats(int64_t m);
+int64_t zi_dt_image_floats(int64_t n);
+int64_t zi_tiles_words(int64_t n, int64_t m);
+int zi_tiles(uint32_t *out, const uint32_t *nzmask, int64_t n, int64_t m, hipStream_t st);
+int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
+             double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st);
+int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st);
 
 }  // namespace dn
 }  // namespace oriana

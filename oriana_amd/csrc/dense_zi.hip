@@ -9,8 +9,9 @@
 //              dn::k_dn_row (S(t) beside the matrix instructions of Lambda(t + 1), then the product of tile t).
 //   k_zi_col   out[gene, k] += sum_i D_hat[i, gene] W[i, k]  (zigap.py:124): dn::k_dn_col reading D_hat row-major.
 //
-// Serves 33 <= K <= 100 (zi_cfg / zi_cfg_dt below: measured assignment); dense_f32.hip keeps K <= 32 and the float32 matrix
-// instruction for K > 100 or a gene count that is not a multiple of 4 (16-byte row pieces).
+// Which (KC, TAIL) serves which K, and what runs instead: zi_candidate in dense_tiles.h (measured assignment); the entries are in
+// dense_f32.hip, which keeps K <= 32, the float32 matrix instruction for K > 100, and a gene count that is not a multiple of 4
+// (16-byte row pieces).
 #include "dense_tiles.h"
 #include <stdlib.h>
 #include <string.h>
@@ -571,16 +572,6 @@ __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, con
     }
 }
 
-template <typename KernelT>
-static int zi_set_lds(KernelT kern, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)bytes);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    return 0;
-}
-
 // work-groups of 512 threads, one per CU: the split count that leaves the last round of the chip fullest (fewer on ties)
 static int64_t zi_pick_splits(int64_t blocks, int64_t max_splits) {
     const int64_t cus = oriana_device_cus();                 // (256 on MI355X)
@@ -594,56 +585,6 @@ static int64_t zi_pick_splits(int64_t blocks, int64_t max_splits) {
         if (eff > best_eff + 0.03) { best_eff = eff; best = sp; }
     }
     return best;
-}
-
-#define ORIANA_ZI_FOR_CFG(KC_, TL_, CALL)                                     \
-    do {                                                                      \
-        if (KC_ == 6 && TL_ == 1) { CALL(6, 1); }                             \
-        else if (KC_ == 6 && TL_ == 0) { CALL(6, 0); }                        \
-        else if (KC_ == 5 && TL_ == 1) { CALL(5, 1); }                        \
-        else if (KC_ == 5 && TL_ == 0) { CALL(5, 0); }                        \
-        else if (KC_ == 4 && TL_ == 1) { CALL(4, 1); }                        \
-        else if (KC_ == 4 && TL_ == 0) { CALL(4, 0); }                        \
-        else if (KC_ == 3 && TL_ == 1) { CALL(3, 1); }                        \
-        else if (KC_ == 3 && TL_ == 0) { CALL(3, 0); }                        \
-        else return ORIANA_EKRANGE;                                           \
-    } while (0)
-
-// Smallest K served here: 33.  Measured at 100k x 20k against dense_f32.hip's bf16 kernels (tools/perf_zi_per_k.py, round 6's
-// build): D update 3.37 against 4.11 ms at K = 48, 3.65 against 4.00 ms at K = 50, 3.72 against 4.11 ms at K = 64; D^T U 1.82
-// against 2.00 ms at K = 48 but 2.06 against 1.98 ms at K = 50 WITH the tail factors' 4 x 4 x 1 instructions: below 65 the
-// transposed product takes the next whole chunk instead (zi_cfg_dt).
-static int64_t zi_min_k() { return 33; }
-
-static bool zi_cfg(int64_t K, int *kc, int *tl) {
-    const int64_t Kp = oriana_kpad(K);
-    if (K < zi_min_k() || Kp == 0 || Kp > 100 || (Kp % 16 != 0 && Kp % 16 != 4)) return false;
-    *kc = (int)(Kp / 16); *tl = (Kp % 16 == 4) ? 1 : 0;
-    // Kp = 48 .. 100.  [r6] Kp = 64 (K = 53 .. 64) too: with room for the flag / logit pieces behind the images (Cfg::PVZ) and the
-    // copies issued at the top of the tile, k_zi_row<4, 0> takes 3.68 ms where dense_f32.hip's bf16 kernel takes 4.11
-    // (K = 49 .. 52 stays on <3, 1> with the tail riding in the last factor tile: 3.65 against 3.72 ms zero-padded to four chunks)
-    return *kc >= 3 && *kc <= 6;
-}
-
-bool zi_supported(int64_t m, int64_t K) {                                  // the D update
-    int kc, tl;
-    return (m % 4) == 0 && zi_cfg(K, &kc, &tl);
-}
-
-// [r6] D_hat^T W below K = 65: Kp = 36 and 52 (K = 50: configs[2]) take the NEXT whole chunk of 16 with zero-padded factors instead
-// of the tail of four -- k_zi_col<4, 0> 1.50 ms against 1.67 ms for k_dt_times_factor_b16 inside the configs[2] sweep (the D update
-// itself is faster WITH the tail: 3.49 against 3.94 ms; profiles/r06_zi_k52_ab.txt)
-static bool zi_cfg_dt(int64_t K, int *kc, int *tl) {
-    const int64_t Kp = oriana_kpad(K);
-    if (K < zi_min_k() || Kp == 0 || Kp > 100 || (Kp % 16 != 0 && Kp % 16 != 4)) return false;
-    *kc = (int)(Kp / 16); *tl = (Kp % 16 == 4) ? 1 : 0;
-    if (*tl && *kc <= 3) { *kc += 1; *tl = 0; }
-    return *kc >= 3 && *kc <= 6;
-}
-
-bool zi_dt_supported(int64_t m, int64_t K) {                               // D_hat^T W
-    int kc, tl;
-    return (m % 4) == 0 && zi_cfg_dt(K, &kc, &tl) && (K > 64 || tl == 0);
 }
 
 // floats of scratch for the gene-side images of m genes / the cell-side images of n cells (largest configuration)
@@ -689,10 +630,8 @@ int zi_tiles(uint32_t *out, const uint32_t *nzmask, int64_t n, int64_t m, hipStr
 }
 
 // lgit: [0, mpad) the scaled logits -logit(pi_d) log2(e), [mpad, 2 mpad) the floors (k_logit_f32)
-int zi_sweep(float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
+int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
              double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
-    int kc, tl;
-    if (!zi_cfg(K, &kc, &tl) || (m % 4) != 0 || m > 16000000 || !Vn || !DV || !nztiles) return ORIANA_EKRANGE;
     const int ngt = (int)((m + 31) / 32);
     const int64_t blocks = ((n + 31) / 32 + NW - 1) / NW;
     int64_t splits = zi_pick_splits(blocks, (ngt + 7) / 8);
@@ -700,27 +639,20 @@ int zi_sweep(float *D_hat, const double *U, const double *V, const float *lgit, 
     splits = (ngt + per - 1) / per;
     if (blocks > 0x7fffffffLL || splits > 65535) return ORIANA_EINVAL;
     u4v *img = reinterpret_cast<u4v *>(img_scratch);
-    if (((reinterpret_cast<uintptr_t>(D_hat) | reinterpret_cast<uintptr_t>(lgit) | (uintptr_t)(mpad * 4) |
-          reinterpret_cast<uintptr_t>(nztiles)) & 15) != 0 || (int64_t)ngt * 8 * 128 > 0x7fffffffLL)
-        return ORIANA_EKRANGE;                                             // 16-byte pieces: the caller falls back
-#define ORIANA_ZI_CALL(KC, TL)                                                                                              \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL((k_zi_images<KC, TL, true>), dim3((unsigned)ngt), dim3(512), 0, st, img, V, Vn, m, K);           \
-        constexpr int lb = zi_row_lds_bytes<KC, TL>();                                                                      \
-        const int rc = zi_set_lds(k_zi_row<KC, TL>, lb);                                                                    \
-        if (rc) return rc;                                                                                                  \
-        hipLaunchKernelGGL((k_zi_row<KC, TL>), dim3((unsigned)blocks, (unsigned)splits), dim3(512), lb, st, D_hat, U,       \
-                           (const u4v *)img, lgit, mpad, nztiles, colsum, DV, n, m, K, ngt, per);                           \
-    } while (0)
-    ORIANA_ZI_FOR_CFG(kc, tl, ORIANA_ZI_CALL);
-#undef ORIANA_ZI_CALL
-    return 0;
+    return with_cfg<ZI_KC_MIN, ZI_KC_MAX>(cfg, [&](auto c) {
+        constexpr int KC = decltype(c)::kc, TL = decltype(c)::tl;
+        if constexpr (!zi_tiles_reachable(ZiOp::update, KC, TL)) {
+            return ORIANA_EKRANGE;
+        } else {
+            const int rc = launch(k_zi_images<KC, TL, true>, dim3((unsigned)ngt), dim3(512), 0, st, img, V, Vn, m, K);
+            if (rc) return rc;
+            return launch(k_zi_row<KC, TL>, dim3((unsigned)blocks, (unsigned)splits), dim3(512), (size_t)zi_row_lds_bytes<KC, TL>(), st,
+                          D_hat, U, img, lgit, mpad, nztiles, colsum, DV, n, m, K, ngt, per);
+        }
+    });
 }
 
-int zi_dt(double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st) {
-    int kc, tl;
-    if (!zi_dt_supported(m, K) || !zi_cfg_dt(K, &kc, &tl)) return ORIANA_EKRANGE;
-    if ((reinterpret_cast<uintptr_t>(D) & 15) != 0) return ORIANA_EKRANGE;   // 16-byte row pieces: the caller falls back
+int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st) {
     const int ngt = (int)((m + 31) / 32);
     const int64_t nct = (n + 31) / 32;
     const int64_t groups = (ngt + NW - 1) / NW;
@@ -729,19 +661,17 @@ int zi_dt(double *out, const float *D, const double *W, float *scratch, int64_t 
     splits = (nct + per - 1) / per;
     if (splits * groups > 0x7fffffffLL) return ORIANA_EINVAL;
     u4v *img = reinterpret_cast<u4v *>(scratch);
-#define ORIANA_ZI_CALL(KC, TL)                                                                                              \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL((k_zi_images<KC, TL, false>), dim3((unsigned)nct), dim3(512), 0, st, img, (const double *)nullptr, \
-                           W, n, K);                                                                                        \
-        constexpr int lb = zi_col_lds_bytes<KC, TL>();                                                                      \
-        const int rc = zi_set_lds(k_zi_col<KC, TL>, lb);                                                                    \
-        if (rc) return rc;                                                                                                  \
-        hipLaunchKernelGGL((k_zi_col<KC, TL>), dim3((unsigned)(splits * groups)), dim3(512), lb, st, D, (const u4v *)img,   \
-                           out, n, m, K, nct, ngt, per, (int)splits);                                                       \
-    } while (0)
-    ORIANA_ZI_FOR_CFG(kc, tl, ORIANA_ZI_CALL);
-#undef ORIANA_ZI_CALL
-    return 0;
+    return with_cfg<ZI_KC_MIN, ZI_KC_MAX>(cfg, [&](auto c) {
+        constexpr int KC = decltype(c)::kc, TL = decltype(c)::tl;
+        if constexpr (!zi_tiles_reachable(ZiOp::dt, KC, TL)) {
+            return ORIANA_EKRANGE;
+        } else {
+            const int rc = launch(k_zi_images<KC, TL, false>, dim3((unsigned)nct), dim3(512), 0, st, img, nullptr, W, n, K);
+            if (rc) return rc;
+            return launch(k_zi_col<KC, TL>, dim3((unsigned)(splits * groups)), dim3(512), (size_t)zi_col_lds_bytes<KC, TL>(), st,
+                          D, img, out, n, m, K, nct, ngt, per, (int)splits);
+        }
+    });
 }
 
 }  // namespace dn

@@ -17,10 +17,9 @@
 // iteration and walks the four records of each quad with DPP broadcasts; the inner loops have no
 // data-dependent branch.  No MFMA: the work is a sampled dot product per non-zero plus two scaled
 // vector adds over the sparse support of X, not a dense contraction.
-#include "common.h"
+#include "launch.h"
 #include <string.h>
 #include <stdlib.h>
-#include <type_traits>
 
 // (the ablation switches of rounds 1-4 -- no barriers, no scattered s stores, masked padding slots, rotation variants, staging
 //  once, staggered waves -- are archived as tools/experiments/passes_ablation_switches_r4.diff)
@@ -66,14 +65,6 @@ static inline bool pick_cfg(int64_t K, KCfg *c) {
     case 56: CALL(8, 7, 0);  case 64: CALL(16, 4, 0);                                                                     \
     default: return ORIANA_EKRANGE;                                                                                       \
     }
-
-// run-time variant -> template argument: f(std::integral_constant<int, v>) for the v of the list, ORIANA_EINVAL for any other
-template <int... Vs, typename F>
-static int with_variant(int v, F &&f) {
-    int rc = ORIANA_EINVAL;
-    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
-    return rc;
-}
 
 // ------------------------------------------------------------------------------------------
 // Which kernel family serves which configuration.  These functions are the whole rule: the launchers below name a kernel
@@ -132,26 +123,6 @@ static constexpr int col_tiles_per_item(KCfg c) {
 static bool den_threshold_dynamic() {
     static const bool fixed = [] { const char *e = getenv("ORIANA_DEN_THRESHOLD"); return e && !strcmp(e, "fixed"); }();
     return !fixed;
-}
-
-template <typename KernelT>
-static int set_lds(KernelT kern, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return -1000 - (int)e;
-    }
-    return 0;
-}
-
-// set_lds, then the launch; the arguments convert to the kernel's parameter types (nullptr, 0)
-template <typename... P, typename... A>
-static int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args) {
-    const int rc = set_lds(kern, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<P>(args)...);
-    ORIANA_LAUNCH_CHECK();
-    return 0;
 }
 
 template <int G, int T4, int TAIL, int V>

@@ -6,7 +6,8 @@ The responsibility sums run on the resident non-zero tiles (engine.zq); the drop
 exactly 1 (in float32) at every non-zero count -- zigap.py:135 sets p_d[X != 0] = 1 - 1e-10 and
 Bernoulli.mean casts to float32 (bernoulli.py:45) -- so the loop nests never need D_hat[i, j] at
 the non-zeros.  The three dense contractions of the ZI models (D_hat V_hat, D_hat^T U_hat,
-U_hat V_hat^T: zigap.py:116, 124, 132) run on the matrix cores.  Inside a sweep (csrc/dense_f32.hip, K <= 128):
+U_hat V_hat^T: zigap.py:116, 124, 132) run on the matrix cores.  Inside a sweep (the entries of csrc/dense_f32.hip, K <= 128; which
+kernel family serves which K -- csrc/dense_zi.hip, or the bf16 / float32 kernels of dense_f32.hip -- is zi_candidate in csrc/dense_tiles.h):
 float32 products whose long sums end in float64; U_hat V_hat^T is fused with the sigmoid / override / column-sum
 epilogue so that Lambda is never materialised, and the same kernel forms D_hat V_hat for the NEXT sweep from the
 tile of D_hat it is about to store -- a sweep reads D_hat once (D_hat^T U_hat) and writes it once.  The float64
@@ -54,7 +55,7 @@ class _ZIMixin:
         # bit mask of X != 0 (constant): lets the D update apply p_d[X != 0] = 1 - 1e-10 in its own pass
         self._nzmask = torch.zeros(((n + 31) // 32) * max(mp, 1), dtype=torch.int32, device=dev)
         call('oriana_nzmask_f32', ptr(self._nzmask), ptr(self._Dp), n, mp, stream_ptr())
-        # [r6] the same mask as per-lane flags for the K = 33 .. 100 D-update kernel (csrc/dense_zi.hip)
+        # [r6] the same mask as per-lane flags for the D-update kernel of csrc/dense_zi.hip (which K it serves: zi_candidate in csrc/dense_tiles.h)
         from .. import _lib
         self._nztiles = torch.zeros(max(int(_lib.load().oriana_nzmask_tiles_words(n, mp)), 4), dtype=torch.int32, device=dev)
         call('oriana_nzmask_tiles', ptr(self._nztiles), ptr(self._nzmask), n, mp, stream_ptr())
@@ -73,7 +74,7 @@ class _ZIMixin:
         self._lg_scratch = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(mp, self.k)), dtype=torch.float32, device=dev)
         self._dt_scratch = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, self.k)), dtype=torch.float32, device=dev)
         # how the float32 products are evaluated (include/oriana_hip.h): 1 = three-way bf16 splits on the bf16 matrix
-        # cores (K <= 100), 0 = the float32 matrix instruction
+        # cores (up to Kp = 100; the float32 instruction above), 0 = the float32 matrix instruction
         self._matrix_arith = {'f32': 0, 'bf16x3': 1}[os.environ.get('ORIANA_ZI_MATRIX', 'bf16x3')]
 
     def _padG(self, T, key):

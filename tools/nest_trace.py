@@ -29,6 +29,20 @@ ORIANA_CUS=2, ORIANA_DETERMINISTIC=1 and ORIANA_FORCE_SHARDED=1 (a one-rank gloo
 environment select the other forms of the sequence.  `list ... nocopy` drops the runtime's buffer copies (__amd_rocclr_copyBuffer):
 under ORIANA_FORCE_SHARDED=1 the exchange issues them from its own threads, beside the sweep's stream, and their place in the
 time-ordered listing changes from run to run.
+
+    ... -- python tools/nest_trace.py dense LABELS.txt ;  python tools/nest_trace.py list DIR LABELS.txt lds
+
+`dense` is `passes` for the dense matrix-core entries (csrc/dense_f32.hip, dense_zi.hip, dense_pass.hip, dense_mfma.hip), on one small
+matrix.  oriana_dropout_sweep_fused_tiles and oriana_dense_t_times_factor_f32 for K = 1, one K per padded width up to 128 and K = 129,
+with both `arithmetic` values, each in its full form and with one precondition of the first kernel family taken away at a time (no
+per-lane flags, no V_next / DV_next, a gene count with m % 4 == 2, D_hat or the scratch 4 bytes off a 16-byte boundary, no scratch);
+the forwarding entry oriana_dropout_sweep_fused; the values of the size entries (oriana_dropout_sweep_scratch_floats,
+oriana_dense_t_scratch_floats, oriana_nzmask_tiles_words, oriana_dense_supported, oriana_dense_image_pieces) in the label;
+oriana_dense_images2 (both sides), oriana_dense_row_pass_tail (unsplit, gene_splits > 1, tail_parts > 1) and oriana_dense_col_pass
+(1 and several cell_splits) on the dense block of a hybrid layout for one K per padded width up to 100 and K = 112 (rc=-2);
+oriana_dense_times_factor in both orientations for one K per NT case up to 256; oriana_dropout_update_fused and
+oriana_dropout_metric at three K; oriana_dense_metric on the same dense block.  Every call is valid for its entry: a refusal is a return code of host-side validation.  ORIANA_CUS=2
+in the environment moves the split pickers (both read oriana_device_cus()).
 """
 import csv
 import ctypes
@@ -246,6 +260,119 @@ def models(labels_path):
         f.write('\n'.join(labels) + '\n')
 
 
+def dense(labels_path):
+    import numpy as np
+    import torch
+    from oriana_amd import _lib, engine
+    from oriana_amd._lib import ptr, stream_ptr
+    lib = _lib.load()
+    st = stream_ptr()
+    labels = []
+    mark_in = torch.ones(256 * 1200, dtype=torch.float64, device='cuda')
+    mark_out = torch.empty_like(mark_in)
+
+    def probe(label, fn, *args):
+        torch.cuda.synchronize()
+        labels.append(label)
+        assert lib.oriana_trigamma_f64(ptr(mark_out), ptr(mark_in), 256 * len(labels), st) == 0
+        labels[-1] += ' rc=%d' % fn(*args)
+        torch.cuda.synchronize()
+
+    n = 1700
+    rng = np.random.default_rng(10)
+    f64 = lambda *shape: torch.rand(*shape, dtype=torch.float64, device='cuda') + 0.25
+    f32 = lambda *shape: torch.rand(*shape, device='cuda') + 0.5
+    off4 = lambda t: t.data_ptr() + 4              # (every buffer handed over this way has room for it)
+    widths = sorted({int(lib.oriana_kpad(K)) for K in range(1, 129)})
+    assert widths == [16, 20, 32, 36, 48, 52, 64, 68, 80, 84, 96, 100, 112, 128]
+    Ks = sorted([1, 50, 129] + widths)
+
+    # ---- the two dense products of a ZI sweep
+    for m in (1098, 1100):                            # m % 4 == 2: no 16-byte row pieces; then m % 4 == 0
+        X = (rng.poisson(3.0, size=(n, m)) * (rng.random((n, m)) < 0.3)).astype(np.float32)
+        Dbuf = torch.zeros(n * m + 4, device='cuda')
+        Dbuf[:n * m] = torch.from_numpy(X).cuda().reshape(-1)
+        mask = torch.zeros(((n + 31) // 32) * m, dtype=torch.int32, device='cuda')
+        assert lib.oriana_nzmask_f32(ptr(mask), ptr(Dbuf), n, m, st) == 0
+        words = int(lib.oriana_nzmask_tiles_words(n, m))
+        tiles = torch.zeros(max(words, 4), dtype=torch.int32, device='cuda')
+        assert lib.oriana_nzmask_tiles(ptr(tiles), ptr(mask), n, m, st) == 0
+        pi, colsum = torch.rand(m, dtype=torch.float64, device='cuda') * 0.8 + 0.1, torch.zeros(m, dtype=torch.float64, device='cuda')
+        probe('m%d nzmask_tiles_words=%d nzmask_tiles' % (m, words), lib.oriana_nzmask_tiles, ptr(tiles), ptr(mask), n, m, st)
+        for K in Ks:
+            U, V, Vn, DV, out = f64(n, K), f64(m, K), f64(m, K), torch.zeros(n, K, dtype=torch.float64, device='cuda'), torch.zeros(m, K, dtype=torch.float64, device='cuda')
+            ssz, tsz = int(lib.oriana_dropout_sweep_scratch_floats(m, K)), int(lib.oriana_dense_t_scratch_floats(n, K))
+            ss, ts = torch.zeros(ssz + 8, device='cuda'), torch.zeros(tsz + 8, device='cuda')
+            assert ss.data_ptr() % 16 == 0 and ts.data_ptr() % 16 == 0 and Dbuf.data_ptr() % 16 == 0
+            tag = 'm%d K%d ' % (m, K)
+            probe(tag + 'sweep_scratch_floats=%d dense_t_scratch_floats=%d' % (ssz, tsz), lambda: 0)
+            for arith in (0, 1):
+                forms = [('full', {})]
+                if m % 4 == 0:
+                    forms += [('no-nztiles', dict(tiles=None)), ('no-V_next', dict(Vn=None, DV=None)), ('D_hat+4', dict(D=off4(Dbuf))),
+                              ('scratch+4', dict(scratch=off4(ss))), ('scratch=NULL', dict(scratch=None))]
+                for name, kw in forms:
+                    a = dict(D=ptr(Dbuf), tiles=ptr(tiles), Vn=ptr(Vn), DV=ptr(DV), scratch=ptr(ss))
+                    a.update(kw)
+                    probe(tag + 'arith=%d sweep_fused_tiles %s' % (arith, name), lib.oriana_dropout_sweep_fused_tiles, a['D'], ptr(U), ptr(V),
+                          ptr(pi), ptr(mask), a['tiles'], ptr(colsum), a['Vn'], a['DV'], a['scratch'], arith, n, m, K, st)
+                probe(tag + 'arith=%d sweep_fused' % arith, lib.oriana_dropout_sweep_fused, ptr(Dbuf), ptr(U), ptr(V), ptr(pi), ptr(mask),
+                      ptr(colsum), ptr(Vn), ptr(DV), ptr(ss), arith, n, m, K, st)
+                forms = [('full', {})]
+                if m % 4 == 0:
+                    forms += [('D_hat+4', dict(D=off4(Dbuf))), ('scratch+4', dict(scratch=off4(ts))), ('scratch=NULL', dict(scratch=None))]
+                for name, kw in forms:
+                    a = dict(D=ptr(Dbuf), scratch=ptr(ts))
+                    a.update(kw)
+                    probe(tag + 'arith=%d dense_t_times_factor_f32 %s' % (arith, name), lib.oriana_dense_t_times_factor_f32, ptr(out), a['D'],
+                          ptr(U), a['scratch'], arith, n, m, K, st)
+
+    # ---- the float64 products and the exact D update / metric (dense_mfma.hip)
+    D = Dbuf[:n * m]
+    pi, colsum = torch.rand(m, dtype=torch.float64, device='cuda') * 0.8 + 0.1, torch.zeros(m, dtype=torch.float64, device='cuda')
+    for K in (1, 16, 32, 48, 64, 80, 96, 112, 128, 129, 200, 256):
+        U, V = f64(n, K), f64(m, K)
+        for trans, W, rows in ((0, V, n), (1, U, m)):
+            out = torch.zeros(rows, K, dtype=torch.float64, device='cuda')
+            probe('K%d dense_times_factor trans=%d' % (K, trans), lib.oriana_dense_times_factor, ptr(out), ptr(D), ptr(W), n, m, K, trans, st)
+    for K in (20, 100, 128):                          # (128: more than 64 KB of LDS)
+        U, V = f64(n, K), f64(m, K)
+        pd, out2 = torch.zeros(n, m, dtype=torch.float64, device='cuda'), torch.zeros(2, dtype=torch.float64, device='cuda')
+        probe('K%d dropout_update_fused' % K, lib.oriana_dropout_update_fused, ptr(pd), ptr(D), ptr(U), ptr(V), ptr(pi), ptr(mask),
+              ptr(colsum), n, m, K, st)
+        probe('K%d dropout_metric' % K, lib.oriana_dropout_metric, ptr(out2), ptr(D), ptr(U), ptr(V), ptr(pi), ptr(mask), n, m, K, st)
+
+    # ---- the dense genes of a hybrid layout (dense_pass.hip)
+    dens = rng.beta(1.0, 3.0, size=m)
+    X = (rng.poisson(3.0, size=(n, m)) * (rng.random((n, m)) < dens[None, :])).astype(np.float32)
+    ct = engine.CountTiles.from_dense(X, 'cuda', dense_density=0.2)
+    d = ct.dense
+    assert d is not None and d.ngt >= 4
+    nrows = d.nct * 32
+    for K in [w for w in widths if w <= 100] + [112]:
+        Kp = int(lib.oriana_kpad(K))
+        pv, pu = int(lib.oriana_dense_image_pieces(K, 0)), int(lib.oriana_dense_image_pieces(K, 1))
+        tag = 'K%d dense ' % K
+        probe(tag + 'supported=%d image_pieces=%d,%d' % (lib.oriana_dense_supported(K), pv, pu), lambda: 0)
+        FU, FV = f32(nrows, Kp), f32(d.gd, Kp)
+        imgV, imgU = torch.zeros(max(d.ngt * pv * 4, 4), device='cuda'), torch.zeros(max((nrows // 32) * pu * 4, 4), device='cuda')
+        S, flag = torch.zeros(d.nct * d.ngt * 1024, device='cuda'), torch.zeros(d.nct * d.ngt, dtype=torch.int32, device='cuda')
+        R, C = torch.zeros(4 * nrows, Kp, device='cuda'), torch.zeros(d.gd, Kp, device='cuda')
+        probe(tag + 'images2 side=0', lib.oriana_dense_images2, ptr(imgV), ptr(FV), None, d.gd, K, 0, st)
+        probe(tag + 'images2 side=1', lib.oriana_dense_images2, ptr(imgU), ptr(FU), None, n, K, 1, st)
+        for name, gsp, nfull, parts in (('unsplit', 1, 0, 1), ('gene_splits=3', 3, 0, 1), ('tail_parts=2', 1, 1, 2)):
+            probe(tag + 'row_pass_tail ' + name, lib.oriana_dense_row_pass_tail, d.c_struct, ptr(FU), ptr(imgV), ptr(R), ptr(S), ptr(flag),
+                  K, gsp, nfull, parts, None, st)
+        for csp in (1, 5):
+            probe(tag + 'col_pass cell_splits=%d' % csp, lib.oriana_dense_col_pass, d.c_struct, ptr(imgU), ptr(S), ptr(C), K, csp, st)
+        sums = torch.zeros(2 * m + 6, dtype=torch.float64, device='cuda')      # colsum | colnnz | out2 | out4
+        probe(tag + 'metric', lib.oriana_dense_metric, d.c_struct, ptr(f64(n, K)), ptr(f64(m, K)), None, None, ptr(sums), ptr(sums) + 8 * m,
+              ptr(sums) + 16 * m, ptr(sums) + 16 * m + 16, K, st)
+    probe('end', lambda: 0)
+    with open(labels_path, 'w') as f:
+        f.write('\n'.join(labels) + '\n')
+
+
 def listing(trace_dir, labels_path, lds=False, nocopy=False):
     """One line per entry: its launches in order as `kernel grid/block` (dimensions of 1 dropped, hipMemsetAsync = memset)."""
     labels = open(labels_path).read().split('\n')
@@ -298,6 +425,8 @@ if __name__ == '__main__':
         passes(sys.argv[2], perf=sys.argv[1] == 'passes-perf')
     elif sys.argv[1] == 'models':
         models(sys.argv[2])
+    elif sys.argv[1] == 'dense':
+        dense(sys.argv[2])
     elif sys.argv[1] == 'list':
         listing(sys.argv[2], sys.argv[3], lds='lds' in sys.argv[4:], nocopy='nocopy' in sys.argv[4:])
     else:
