@@ -182,16 +182,6 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
         stg.store(lds, tid);
         __syncthreads();
         }
-        for (int it = 0; it < niter; ++it) {
-            const bool live = it < nit;
-            uint4 cur = rawq[0];
-            const f2 wcur = wq[0];
-            #pragma unroll
-            for (int d = 0; d + 1 < PD; ++d) { rawq[d] = rawq[d + 1]; wq[d] = wq[d + 1]; }
-            const int nx = (it + PD < nit) ? it + PD : nit - 1;
-            if (nit > 0) { rawq[PD - 1] = recp[(int64_t)nx * 32]; if (HASW) wq[PD - 1] = *reinterpret_cast<const f2 *>(w_nz + rbase + (int64_t)nx * 64); }
-            if (!live) { cur.x = 0u; cur.z = 0u; }               // past the end of the shorter slice: padding
-            f2 sbuf = {0.f, 0.f};
 #define ORIANA_ROW_STEP2(U)                                                                           \
             {                                                                                         \
                 const uint32_t bm = pb_u32<U>((U & 1) ? cur.w : cur.y);                               \
@@ -235,13 +225,41 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
                 _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) asm volatile("" : "+v"(acc[tt]));  \
                 asm volatile("" : "+v"(cur.x), "+v"(cur.y), "+v"(cur.z), "+v"(cur.w));                \
             }
-            ORIANA_ROW_STEP2(0)
-            ORIANA_ROW_STEP2(1)
-            ORIANA_ROW_STEP2(2)
-            ORIANA_ROW_STEP2(3)
-#undef ORIANA_ROW_STEP2
-            if (SROW && live) *reinterpret_cast<f2 *>(s_rs + rbase + (int64_t)it * 64) = sbuf;
+        // One iteration = record U of each row at step U.  TRIM (the wave's final iteration): a row's records are packed
+        // front-first inside its slice -- k_pack_fill puts the entry of rank k in the row at iteration k >> 2, record k & 3,
+        // and every other slot of the zero-filled stream stays x == 0 -- so "record U holds an entry in some row" is
+        // monotone in U, and the steps from rem = 1 + (last U with an entry in any row of the live half waves) on hold
+        // padding in every lane.  They would add fma(+0, v, acc) to accumulators that are never -0, store 0 to the
+        // write-only dummy slots and leave sbuf at its zeros: they are not issued.  rem is wave-uniform (two ballots).
+#define ORIANA_ROW_ITER(TRIM)                                                                         \
+        {                                                                                             \
+            const bool live = it < nit;                                                               \
+            uint4 cur = rawq[0];                                                                      \
+            const f2 wcur = wq[0];                                                                    \
+            if (!(TRIM)) {                                                                            \
+                _Pragma("unroll") for (int d = 0; d + 1 < PD; ++d) { rawq[d] = rawq[d + 1]; wq[d] = wq[d + 1]; }  \
+                const int nx = (it + PD < nit) ? it + PD : nit - 1;                                   \
+                if (nit > 0) { rawq[PD - 1] = recp[(int64_t)nx * 32]; if (HASW) wq[PD - 1] = *reinterpret_cast<const f2 *>(w_nz + rbase + (int64_t)nx * 64); }  \
+            }                                                                                         \
+            if (!live) { cur.x = 0u; cur.z = 0u; }               /* past the end of the shorter slice: padding */ \
+            int rem = 4;                                                                              \
+            if (TRIM) {                          /* lane q of a pair holds records 2q (x) and 2q + 1 (z) */ \
+                const unsigned long long bx = __ballot(__uint_as_float(cur.x) != 0.f);                \
+                const unsigned long long bz = __ballot(__uint_as_float(cur.z) != 0.f);                \
+                const unsigned long long odd = 0xAAAAAAAAAAAAAAAAull;                                 \
+                rem = (bz & odd) ? 4 : (bx & odd) ? 3 : bz ? 2 : bx ? 1 : 0;                          \
+            }                                                                                         \
+            f2 sbuf = {0.f, 0.f};                                                                     \
+            if (rem > 0) ORIANA_ROW_STEP2(0)                                                          \
+            if (rem > 1) ORIANA_ROW_STEP2(1)                                                          \
+            if (rem > 2) ORIANA_ROW_STEP2(2)                                                          \
+            if (rem > 3) ORIANA_ROW_STEP2(3)                                                          \
+            if (SROW && live) *reinterpret_cast<f2 *>(s_rs + rbase + (int64_t)it * 64) = sbuf;        \
         }
+        for (int it = 0; it + 1 < niter; ++it) ORIANA_ROW_ITER(false)
+        if (niter > 0) { const int it = niter - 1; ORIANA_ROW_ITER(true) }
+#undef ORIANA_ROW_ITER
+#undef ORIANA_ROW_STEP2
         if (__any(bad) && lane == 0) tile_flag[t] = 1;
     }
     if (row < cm.n && !SROW) {
@@ -393,10 +411,21 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
                     _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) asm volatile("" : "+v"(accA[tt]), "+v"(accB[tt]));  \
                     asm volatile("" : "+v"(svc), "+v"(rvc));                                          \
                 }
+    // The slice's final iteration is peeled and trimmed: lane 4 c + U holds record U of column c, and a step whose 16
+    // slots all hold s == 0 only adds fma(0, v, acc) to accumulators that are never -0 (they start at +0), so the steps
+    // from rem = 1 + (last U with s != 0 in any column) on are not issued.  That rule needs no knowledge of the layout to
+    // be exact; it FINDS the padding because k_pack_fill gives the entry of rank k in its column the slot of iteration
+    // k >> 2, record k & 3 (front-first), the row kernels and k_fixup write s only at a record's cdst or at the 64 dummy
+    // slots behind cslice[16], and every allocator of s_cs / sw_cs zero-fills it once (Workspace, stateless.hip,
+    // resident.hip): a padding slot reads +0 for the lifetime of the counts.  A NaN ("evaluate me exactly") is != 0.
+#define ORIANA_COL_REM(SVC)                                                                           \
+                    const unsigned long long nzm = __ballot((SVC) != 0.f);                            \
+                    const int rem = (nzm & 0x8888888888888888ull) ? 4 : (nzm & 0x4444444444444444ull) ? 3 : \
+                                    (nzm & 0x2222222222222222ull) ? 2 : nzm ? 1 : 0;
 #define ORIANA_COL_RUN4D(ST)                                                                          \
             {                                                                                         \
                 const int last = (ST.nit > 0) ? ST.nit - 1 : 0;                                       \
-                for (int it = 0; it < ST.nit; ++it) {                                                 \
+                for (int it = 0; it < last; ++it) {                                                   \
                     float svc = ST.sv[0]; uint32_t rvc = ST.rv[0];                                    \
                     _Pragma("unroll") for (int d = 0; d + 1 < CPD; ++d) { ST.sv[d] = ST.sv[d + 1]; ST.rv[d] = ST.rv[d + 1]; } \
                     const int nx = (it + CPD < last) ? it + CPD : last;                               \
@@ -407,11 +436,19 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
                     ORIANA_COL_STEP4D(2)                                                              \
                     ORIANA_COL_STEP4D(3)                                                              \
                 }                                                                                     \
+                if (ST.nit > 0) {                                                                     \
+                    float svc = ST.sv[0]; uint32_t rvc = ST.rv[0];                                    \
+                    ORIANA_COL_REM(svc)                                                               \
+                    if (rem > 0) ORIANA_COL_STEP4D(0)                                                 \
+                    if (rem > 1) ORIANA_COL_STEP4D(1)                                                 \
+                    if (rem > 2) ORIANA_COL_STEP4D(2)                                                 \
+                    if (rem > 3) ORIANA_COL_STEP4D(3)                                                 \
+                }                                                                                     \
             }
 #define ORIANA_COL_RUN4(ST, ACC, ACT)                                                                 \
             {                                                                                         \
                 const int last = (ST.nit > 0) ? ST.nit - 1 : 0;                                       \
-                for (int it = 0; it < ST.nit; ++it) {                                                 \
+                for (int it = 0; it < last; ++it) {                                                   \
                     float svc = ST.sv[0]; uint32_t rvc = ST.rv[0];                                    \
                     _Pragma("unroll") for (int d = 0; d + 1 < CPD; ++d) { ST.sv[d] = ST.sv[d + 1]; ST.rv[d] = ST.rv[d + 1]; } \
                     const int nx = (it + CPD < last) ? it + CPD : last;                               \
@@ -421,6 +458,14 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
                     ORIANA_COL_STEP4(ACC, ACT, 1)                                                     \
                     ORIANA_COL_STEP4(ACC, ACT, 2)                                                     \
                     ORIANA_COL_STEP4(ACC, ACT, 3)                                                     \
+                }                                                                                     \
+                if (ST.nit > 0) {                                                                     \
+                    float svc = ST.sv[0]; uint32_t rvc = ST.rv[0];                                    \
+                    ORIANA_COL_REM(svc)                                                               \
+                    if (rem > 0) ORIANA_COL_STEP4(ACC, ACT, 0)                                        \
+                    if (rem > 1) ORIANA_COL_STEP4(ACC, ACT, 1)                                        \
+                    if (rem > 2) ORIANA_COL_STEP4(ACC, ACT, 2)                                        \
+                    if (rem > 3) ORIANA_COL_STEP4(ACC, ACT, 3)                                        \
                 }                                                                                     \
             }
     Stream stA, stB, stN;
@@ -459,6 +504,7 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
         stA = stN;
     }
 #undef ORIANA_COL_RUN4D
+#undef ORIANA_COL_REM
 #undef ORIANA_COL_STEP4D
 #undef ORIANA_COL_RUN4
 #undef ORIANA_COL_STEP4
