@@ -377,6 +377,30 @@ int oriana_count_stats(const oriana_counts *cm, double *colsum, double *colnnz, 
 int oriana_dropout_metric(double *out2, const float *D_hat, const double *U, const double *V, const double *pi_d,
                           const uint32_t *nzmask, int64_t n, int64_t m, int64_t K, void *stream);
 
+/* ---- the variational bound of pCMF (oriana_amd/models/gap.py: elbo; no counterpart in the reference) --------
+ * With q(Z) at its optimum for the current q(U) q(V), Gamma(shape, rate) throughout:
+ *   ELBO = sum_{x != 0} [x log den - lgamma(x + 1)] - sum_k (sum_i U_hat_ik)(sum_j V_hat_jk) - KL_U - KL_V,
+ *   log den_ij = log sum_k exp(E[log U]_ik + E[log V]_jk)   (the float32 expectations the next sweep reads).
+ *   oriana_elbo_nnz   : out2 += { sum x log den, sum lgamma(x + 1) } over the stored entries of the sliced layout.
+ *                       log den = mu_u[i] + mu_v[j] + log(x / s): s_rs from oriana_row_pass over the shifted factors
+ *                       F = exp(l - mu) of oriana_factor_prep, mu_u [n], mu_v [m] its row maxima (packed order, NaN for a
+ *                       rejected row).  An entry whose s is the NaN sentinel or 0 is a float64 log-sum-exp over the K
+ *                       factors from logU (n, K), logV (m, K) (caller's order, float32) inside the kernel -- NOT the
+ *                       exp-of-the-sum arithmetic of oriana_fixup: the bound stays finite where den underflows.
+ *   oriana_dense_elbo : the same two sums over the non-zero counts of the dense genes of a hybrid layout, every
+ *                       log den a float64 log-sum-exp (K <= 256).
+ *   oriana_gamma_kl   : out[0] += sum_{i,k} KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)) over an (r, K) side, float64:
+ *                       (s1 - p1) psi(s1) - lgamma(s1) + lgamma(p1) + p1 (log s2 - log p2) + s1 (p2 - s2) / s2.
+ *                       s2_is_row != 0: s2 is a K-vector broadcast over the rows (pCMF's cell-side rate,
+ *                       oriana_gamma_update_finalize_lazy); else dense (r, K).  Shapes at the clamp (1e-15) give finite values.
+ */
+int oriana_elbo_nnz(const oriana_counts *cm, const float *s_rs, const float *mu_u, const float *mu_v,
+                    const float *logU, const float *logV, int64_t K, double *out2, void *stream);
+int oriana_dense_elbo(const oriana_dense *d, const float *logU, const float *logV, const int32_t *row_perm,
+                      const int32_t *col_perm, double *out2, int64_t K, void *stream);
+int oriana_gamma_kl(double *out, const double *s1, const double *s2, int s2_is_row, const double *p1, const double *p2,
+                    int64_t r, int64_t K, void *stream);
+
 /* ---- stateless drop-ins with the reference's exact signatures (outputs first) ------------------
  * One entry per loop nest, arguments in the reference's order, all matrices dense C-contiguous f32
  * on the device: X, D_hat (n, m); log_U_hat and the row-side output (n, K); log_V_hat, S_tilde, S_hat

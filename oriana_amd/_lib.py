@@ -120,6 +120,9 @@ _SIGS = {
     'oriana_factor_cast_f32': (c_int, [_P, _P, _P, _P, _I, _I, _P]),
     'oriana_metric_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _I, _P, _P]),
     'oriana_count_stats': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P]),
+    'oriana_elbo_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _I, _P, _P]),
+    'oriana_dense_elbo': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _I, _P]),
+    'oriana_gamma_kl': (c_int, [_P, _P, _P, c_int, _P, _P, _I, _I, _P]),
     'oriana_dropout_metric': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'oriana_nzmask_f32': (c_int, [_P, _P, _I, _I, _P]),
     'oriana_dropout_fix_nz_ld': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, c_double, _I, _P]),

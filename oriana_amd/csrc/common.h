@@ -215,6 +215,17 @@ __device__ __forceinline__ double nan_to_num(double v) {
 }
 __device__ __forceinline__ double clamp_eps(double v) { return fmax(1e-15, nan_to_num(v)); }
 
+// log sum_k exp(a[k] + b[k]) in float64 (the log of the softmax denominator of gap.py:74-78, never leaving the log domain:
+// finite wherever one sum a[k] + b[k] is, however negative)
+__device__ __forceinline__ double logsumexp_f64(const float *__restrict__ a, const float *__restrict__ b, int K) {
+    double mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmax(mx, (double)a[k] + (double)b[k]);
+    if (!(fabs(mx) < INFINITY)) return mx;
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp((double)a[k] + (double)b[k] - mx);
+    return mx + log(s);
+}
+
 // oriana/utils.py:9-15
 __device__ __forceinline__ double sigmoid_f64(double x) { return 1.0 / (1.0 + exp(-x)); }
 __device__ __forceinline__ double logit_f64(double x) {

@@ -705,6 +705,50 @@ __global__ __launch_bounds__(256) void k_dn_metric(const uint16_t *__restrict__ 
     }
 }
 
+// The data term of the variational bound over the dense block (oriana_elbo_nnz for the dense genes): out2 += {sum x log den,
+// sum lgamma(x + 1)} over the non-zero counts, log den = log sum_k exp(lu_ik + lv_jk) as a float64 log-sum-exp from the float32
+// E[log U], E[log V] (caller's cell / gene order).  One work-group per (cell tile, gene tile).
+__global__ __launch_bounds__(256) void k_dn_elbo(const uint16_t *__restrict__ Xd, const float *__restrict__ logU,
+                                                 const float *__restrict__ logV, const int32_t *__restrict__ row_perm,
+                                                 const int32_t *__restrict__ col_perm, double *__restrict__ out2, int64_t n,
+                                                 int ngt, int K) {
+    extern __shared__ float lfac[];                // [32 cells][K] then [32 genes][K]
+    __shared__ double red[2][4];
+    const int gt = blockIdx.x;
+    const int64_t ct = blockIdx.y;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 32 * K; e += 256) {
+        const int r = e / K, k = e - r * K;
+        const int64_t ip = ct * 32 + r, jp = (int64_t)gt * 32 + r;
+        const int64_t i = (ip < n) ? (row_perm ? (int64_t)row_perm[ip] : ip) : -1;
+        const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+        lfac[e] = (i >= 0) ? logU[i * K + k] : 0.f;
+        lfac[32 * K + e] = logV[j * K + k];
+    }
+    __syncthreads();
+    double a[2] = {0.0, 0.0};
+    const uint16_t *blk = Xd + (ct * ngt + gt) * 1024;
+    for (int e = tid; e < 1024; e += 256) {
+        const int v = ((e >> 9) << 3) | (e & 7), l = (e >> 3) & 63;
+        const int c = l & 31, h = l >> 5, g = acc_row(v, h);
+        const uint32_t xi = blk[e];
+        if (xi == 0u || ct * 32 + c >= n) continue;
+        const double x = (double)xi;
+        a[0] += x * logsumexp_f64(lfac + c * K, lfac + 32 * K + g * K, K);
+        a[1] += lgamma(x + 1.0);
+    }
+    for (int q = 0; q < 2; ++q) {
+        double t = a[q];
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        if ((tid & 63) == 0) red[q][tid >> 6] = t;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        const double t = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+        if (t != 0.0) atomicAdd(&out2[tid], t);
+    }
+}
+
 template <int KC, int TAIL> constexpr int row_lds_bytes() { return 3 * Cfg<KC, TAIL>::PV * 16 + NW * 32 * TS * 4; }
 template <int KC, int TAIL> constexpr int col_lds_bytes() { return 3 * Cfg<KC, TAIL>::PU * 16 + 2 * NW * 256 * 16; }
 
@@ -860,4 +904,14 @@ extern "C" int oriana_dense_metric(const oriana_dense *d, const double *U, const
     const size_t lb = U ? (size_t)64 * K * sizeof(double) : 0;
     return launch(k_dn_metric, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), lb, (hipStream_t)stream, d->x, U, V,
                   row_perm, col_perm, colsum, colnnz, out2, out4, d->n, ngt, (int)K);
+}
+
+extern "C" int oriana_dense_elbo(const oriana_dense *d, const float *logU, const float *logV, const int32_t *row_perm,
+                                 const int32_t *col_perm, double *out2, int64_t K, void *stream) {
+    if (!dense_ok(d) || K <= 0 || K > 256) return ORIANA_EINVAL;
+    if (d->gd == 0 || d->n == 0) return 0;
+    if (!logU || !logV || !out2) return ORIANA_EINVAL;
+    const int ngt = (int)(d->gd / 32);
+    return launch(k_dn_elbo, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), (size_t)64 * K * sizeof(float),
+                  (hipStream_t)stream, d->x, logU, logV, row_perm, col_perm, out2, d->n, ngt, (int)K);
 }

@@ -119,6 +119,46 @@ __global__ __launch_bounds__(256) void k_metric_nnz(oriana_counts cm, const floa
     }
 }
 
+// out[0] += sum x log den, out[1] += sum lgamma(x + 1) over the stored entries: the data term of the variational bound
+// (models/gap.py: elbo).  log den_ij = log sum_k exp(lu_ik + lv_jk) = mu_u[i] + mu_v[j] + log(x / s), s from the row pass
+// over the shifted factors exp(l - mu) of oriana_factor_prep (mu_u, mu_v: its row maxima, packed order).  Entries the
+// shifted form could not represent (NaN sentinel or 0 in s, a rejected row's NaN maximum) are a float64 log-sum-exp over
+// the K factors here: the bound lives in the log domain and stays finite where den itself underflows.
+__global__ __launch_bounds__(256) void k_elbo_nnz(oriana_counts cm, const float *__restrict__ s_rs,
+                                                  const float *__restrict__ mu_u, const float *__restrict__ mu_v,
+                                                  const float *__restrict__ logU, const float *__restrict__ logV,
+                                                  int K, double *__restrict__ out) {
+    __shared__ double sh[4];
+    const int64_t t = blockIdx.x;
+    const int64_t rb = t / cm.ncb, cb = t - rb * cm.ncb;
+    const int64_t rbase = cm.roff[t];
+    double a0 = 0.0, a1 = 0.0;
+    for (int sl = 0; sl < 16; ++sl) {
+        const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+        for (uint32_t slot = s0 + threadIdx.x; slot < s1; slot += 256) {
+            const oriana_rowrec rec = cm.rowrec[rbase + slot];
+            if (rec.x == 0.f) continue;
+            const float s = s_rs[rbase + slot];
+            const double x = (double)rec.x;
+            const int64_t ip = rb * TILE + sl * 16 + (int)(((slot - s0) & 63u) >> 2);
+            const int64_t jp = cb * TILE + rec.col;
+            if (ip >= cm.n || jp >= cm.m) continue;          // (no stored entry lies there: mu_u, mu_v end at n, m)
+            double ld = NAN;
+            if (s > 0.f && s < INFINITY) ld = (double)mu_u[ip] + (double)mu_v[jp] + log(x / (double)s);
+            if (!(fabs(ld) < INFINITY)) {
+                const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+                const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+                ld = logsumexp_f64(logU + i * K, logV + j * K, K);
+            }
+            a0 += x * ld;
+            a1 += lgamma(x + 1.0);
+        }
+    }
+    a0 = block_sum(a0, sh);
+    a1 = block_sum(a1, sh);
+    if (threadIdx.x == 0) { atomicAdd(&out[0], a0); atomicAdd(&out[1], a1); }
+}
+
 }  // namespace oriana
 
 using namespace oriana;
@@ -155,6 +195,18 @@ extern "C" int oriana_metric_nnz(const oriana_counts *cm, const float *s_rs, con
     if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
     hipLaunchKernelGGL(k_metric_nnz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, U, V, (int)K,
                        out4);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_elbo_nnz(const oriana_counts *cm, const float *s_rs, const float *mu_u, const float *mu_v,
+                               const float *logU, const float *logV, int64_t K, double *out2, void *stream) {
+    if (!cm || !s_rs || !mu_u || !mu_v || !logU || !logV || !out2 || K <= 0) return ORIANA_EINVAL;
+    const int64_t nt = cm->nrb * cm->ncb;
+    if (nt == 0 || cm->rslots == 0) return 0;
+    if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
+    hipLaunchKernelGGL(k_elbo_nnz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, mu_u, mu_v, logU, logV,
+                       (int)K, out2);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

@@ -407,6 +407,47 @@ __global__ void k_mstep_gamma_pair(double *__restrict__ p1u, double *__restrict_
     }
 }
 
+// lgamma for x > 0.  Below 2^-27 (the shapes clamped to 1e-15, gap.py:55) the series -log x - gamma x, whose next term
+// (pi^2 / 12 x^2) is below 1e-17: no dependence on how the library treats arguments next to the pole.
+__device__ __forceinline__ double lgamma_pos(double x) {
+    if (x < 7.450580596923828e-09) return -log(x) - 0.5772156649015329 * x;
+    return lgamma(x);
+}
+
+// out[0] += sum_{i,k} KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)), shape / rate, float64:
+//   (s1 - p1) psi(s1) - lgamma(s1) + lgamma(p1) + p1 (log s2 - log p2) + s1 (p2 - s2) / s2
+// s2_row != 0: s2 is a K-vector, the same rate in every row (pCMF's cell side, oriana_gamma_update_finalize_lazy).
+// Grid-stride over the r K elements; the per-factor constants in LDS (5 K doubles); one atomic per work-group.
+__global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, const double *__restrict__ s1,
+                                                  const double *__restrict__ s2, int s2_row, const double *__restrict__ p1,
+                                                  const double *__restrict__ p2, int64_t r, int K) {
+    extern __shared__ double kc[];                 // [K] p1 | p2 | lgamma(p1) - p1 log p2 | s2 (vector form) | its log
+    __shared__ double red[4];
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const double a = p1[k], b = p2[k];
+        kc[k] = a;
+        kc[K + k] = b;
+        kc[2 * K + k] = lgamma_pos(a) - a * log(b);
+        kc[3 * K + k] = s2_row ? s2[k] : 0.0;
+        kc[4 * K + k] = s2_row ? log(s2[k]) : 0.0;
+    }
+    __syncthreads();
+    const int64_t tot = r * K;
+    double acc = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (int64_t)gridDim.x * 256) {
+        const int k = (int)(e % K);
+        const double a = s1[e];
+        const double b = s2_row ? kc[3 * K + k] : s2[e];
+        const double lb = s2_row ? kc[4 * K + k] : log(b);
+        const double pa = kc[k], pb = kc[K + k];
+        acc += (a - pa) * digamma_f64(a) - lgamma_pos(a) + kc[2 * K + k] + pa * lb + a * (pb - b) / b;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+}
+
 enum { OP_DIGAMMA = 0, OP_TRIGAMMA, OP_INVDIGAMMA, OP_SIGMOID, OP_LOGIT };
 template <int OP>
 __global__ void k_map_f64(double *__restrict__ y, const double *__restrict__ x, int64_t len) {
@@ -665,3 +706,19 @@ extern "C" int oriana_trigamma_f64(double *y, const double *x, int64_t len, void
 extern "C" int oriana_inverse_digamma_f64(double *y, const double *x, int64_t len, void *s) { return launch_map<OP_INVDIGAMMA>(y, x, len, s); }
 extern "C" int oriana_sigmoid_f64(double *y, const double *x, int64_t len, void *s) { return launch_map<OP_SIGMOID>(y, x, len, s); }
 extern "C" int oriana_logit_f64(double *y, const double *x, int64_t len, void *s) { return launch_map<OP_LOGIT>(y, x, len, s); }
+
+extern "C" int oriana_gamma_kl(double *out, const double *s1, const double *s2, int s2_is_row, const double *p1,
+                               const double *p2, int64_t r, int64_t K, void *stream) {
+    if (r < 0 || K <= 0 || K > 1024) return ORIANA_EINVAL;
+    if (r == 0) return 0;
+    if (!out || !s1 || !s2 || !p1 || !p2) return ORIANA_EINVAL;
+    const int64_t tot = r * K;
+    int64_t nblk = (tot + 1023) / 1024;            // four elements per lane, at most eight work-groups per CU
+    const int64_t cap = 8 * oriana_device_cus();
+    if (nblk > cap) nblk = cap;
+    if (nblk < 1) nblk = 1;
+    hipLaunchKernelGGL(k_gamma_kl, dim3((unsigned)nblk), dim3(256), (size_t)5 * K * sizeof(double), (hipStream_t)stream, out, s1,
+                       s2, s2_is_row ? 1 : 0, p1, p2, r, (int)K);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}

@@ -271,11 +271,45 @@ class FactorModel:
         self._graph = g
         return self
 
-    def fit(self, n_iter=50):
-        """The loop user scripts write around step() (reference main.py:37-51)."""
-        for _ in range(int(n_iter)):
+    def fit(self, n_iter=50, tol=None, check_every=5):
+        """The loop user scripts write around step() (reference main.py:37-51): `n_iter` sweeps.
+        With a `tol` the variational bound decides when to stop: elbo() is evaluated after every `check_every` sweeps,
+        each (n_sweeps, value) pair is appended to ``self.elbo_trace_``, and the loop ends early once
+        |E_t - E_prev| <= tol * |E_t|.  tol=None: exactly the n_iter sweeps, nothing else is launched."""
+        n_iter = int(n_iter)
+        if tol is None:
+            for _ in range(n_iter):
+                self.step()
+            return self
+        if self._no_elbo is not None:
+            raise NotImplementedError(self._no_elbo)
+        tol, check_every = float(tol), int(check_every)
+        if check_every < 1:
+            raise ValueError('check_every must be at least 1')
+        if not hasattr(self, 'elbo_trace_'):
+            self.elbo_trace_ = []
+        prev = None
+        for it in range(1, n_iter + 1):
             self.step()
+            if it % check_every == 0:
+                cur = self.elbo()
+                self.elbo_trace_.append((self.n_sweeps, cur))
+                if prev is not None and abs(cur - prev) <= tol * abs(cur):
+                    break
+                prev = cur
         return self
+
+    # The variational bound exists for pCMF only (models/gap.py).  The reference's zero-inflated and sparse updates are not
+    # coordinate ascent on one stated bound: the per-gene sums are weighted with D_hat[i, k] instead of D_hat[i, j]
+    # (zigap.py:94), p_d is pinned to 1 - 1e-10 at every non-zero count (zigap.py:135), and S_tilde = (p_s > tau)
+    # (sparse_gap.py:113) thresholds the posterior the other updates read -- no value is non-decreasing under them.
+    _no_elbo = ('elbo() is defined for pCMF (GaP) only: the zero-inflated and sparse updates of the reference (the D_hat[i, k] '
+                'index of zigap.py:94, p_d pinned to 1 - 1e-10 at the non-zero counts, the tau threshold on p_s) are not '
+                'coordinate ascent on one stated bound, so no such value is monotone for them')
+
+    def elbo(self):
+        """The evidence lower bound of the current variational state (GaP); NotImplementedError on the other models."""
+        raise NotImplementedError(self._no_elbo)
 
     def factors(self):
         """base.py:97-98: (U[:], V[:]) as host arrays."""

@@ -5,6 +5,8 @@ import os
 import torch
 
 from .. import engine
+from .. import dist as odist
+from .._lib import call, ptr, stream_ptr
 from .base import FactorModel
 
 __all__ = ['GaP']
@@ -102,6 +104,63 @@ class GaP(FactorModel):
         FactorModel.step(self)
         if self._graph is not None and self._a2_row is not None and self._lazy_ok:
             self._u_on_access()              # (a replayed graph ran the kernel again: what was materialised is stale)
+
+    # ---- the variational bound ---------------------------------------------------------------------------------------------
+    # With q(Z) at its multinomial optimum for the current q(U) q(V) (Gamma(shape, rate) throughout):
+    #   ELBO = sum_{x != 0} [x log den - lgamma(x + 1)] - sum_k (sum_i U_hat_ik)(sum_j V_hat_jk) - KL_U - KL_V,
+    #   log den_ij = logsumexp_k(E[log U]_ik + E[log V]_jk)            (the float32 expectations the next sweep reads)
+    # Every update of step() maximises the uncollapsed bound in one coordinate and collapsing q(Z) only raises it, so the
+    # value never decreases from sweep to sweep (M-step included) beyond its float32 evaluation error.  Its only
+    # Theta(nnz K) term is the first one, and den is what the row pass forms: one row pass over factors prepared into scratch
+    # of the call's own (the FU the last update prepared for the next sweep stays as it is), a read of s, and Theta((n + m) K)
+    # float64 work.
+    _no_elbo = None
+
+    def _elbo_terms(self):
+        """The five terms {data, lgamma, product, kl_u, kl_v} as a float64 device vector (all-reduced over the row shards)."""
+        ct, K, n, m, dev, ws = self.counts, self.k, self.n, self.m, self.device, self._ws
+        st = stream_ptr()
+        lu, lv = self._log_U_hat, self._log_V_hat
+        FU, FV = ws.extra('EU', n), ws.extra('EV', m)
+        mu = getattr(self, '_elbo_mu', None)
+        if mu is None:
+            mu = self._elbo_mu = torch.zeros(max(n, 1) + max(m, 1), dtype=torch.float32, device=dev)
+        mu_u, mu_v = mu[:max(n, 1)], mu[max(n, 1):]
+        engine.factor_prep(FU, lu, mu=mu_u, row_index=ct.row_perm)
+        engine.factor_prep(FV, lv, mu=mu_v, row_index=ct.col_perm)
+        if ws.s_rs is None:
+            ws.s_rs = torch.zeros(max(ct.rslots, 1), dtype=torch.float32, device=dev)
+        ws.tile_flag.zero_()
+        # (hybrid layout: the sliced part covers the packed genes [gd, m), the dense genes are summed in float64)
+        call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV) + 4 * ct.gd * ws.Kp, None, ptr(ws.R), ptr(ws.s_cs), None,
+             ptr(ws.s_rs), ptr(ws.tile_flag), K, st)
+        # cell-side partials in one packed vector: [sum x log den, sum lgamma(x + 1), KL_U, sum_i U_hat (K)]
+        part = torch.zeros(3 + K, dtype=torch.float64, device=dev)
+        call('oriana_elbo_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(mu_u), ptr(mu_v) + 4 * ct.gd, ptr(lu), ptr(lv), K, ptr(part), st)
+        if ct.dense is not None:
+            call('oriana_dense_elbo', ct.dense.c_struct, ptr(lu), ptr(lv), ptr(ct.row_perm), ptr(ct.col_perm), ptr(part), K, st)
+        # the cell-side rate: the K numbers of the lazy form while a2 is deferred (it is not materialised here)
+        a2 = self.a2
+        row = self._a2_row is not None and not getattr(a2, 'materialised', True)
+        call('oriana_gamma_kl', ptr(part[2:]), ptr(self.a1.tensor), ptr(self._a2_row if row else a2.tensor), 1 if row else 0,
+             ptr(self.alpha1.tensor), ptr(self.alpha2.tensor), n, K, st)
+        if self._u_stale:                       # U_hat = a1 / a2_row is not stored: its column sums from a1
+            part[3:] = self.a1.tensor.sum(0) / self._a2_row
+        else:
+            part[3:] = self._U_buf.sum(0)
+        odist.all_reduce_sum(part, self.pg)
+        # the gene side is replicated: counted once
+        kl_v = torch.zeros(1, dtype=torch.float64, device=dev)
+        call('oriana_gamma_kl', ptr(kl_v), ptr(self.b1.tensor), ptr(self.b2.tensor), 0, ptr(self.beta1.tensor),
+             ptr(self.beta2.tensor), m, K, st)
+        prod = (part[3:] * self._V_hat.sum(0)).sum().reshape(1)
+        return torch.cat([part[:2], prod, part[2:3], kl_v])
+
+    def elbo(self):
+        """The evidence lower bound of the current variational state, q(Z) at its optimum (a Python float).  Non-decreasing
+        from sweep to sweep; leaves the state and the next sweep untouched ("The variational bound")."""
+        t = self._elbo_terms()
+        return float(t[0] - t[1] - t[2] - t[3] - t[4])
 
     def _init_extra(self):
         if os.environ.get('ORIANA_LAZY_U', '1') != '0':
