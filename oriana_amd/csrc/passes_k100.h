@@ -46,6 +46,25 @@ __device__ __forceinline__ int lchunk(int lane, int t) {
     return pc * 2 + q;
 }
 
+// (a << SH) + b in one instruction (the compiler shares a << SH between the reads of a step and adds twelve times)
+template <int SH> __device__ __forceinline__ uint32_t lshl_add(uint32_t a, uint32_t b) {
+    uint32_t d;
+    asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(SH), "v"(b));
+    return d;
+}
+// 32-bit LDS addresses: reads whose address is formed by lshl_add go through them, so that no generic-pointer
+// arithmetic (an addition of the image's base per read) is left
+typedef const f4 __attribute__((address_space(3))) *lds_f4_ptr;
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {
+    return (uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void *)p);
+}
+__device__ __forceinline__ f4 lds_read_f4(uint32_t addr) { return *(lds_f4_ptr)(uintptr_t)addr; }
+// a wave-uniform 64-bit value the compiler holds in vector registers (loaded after the kernel's own stores), made scalar
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
 // broadcast inside a lane pair: lane (U >> 1) of the pair holds the value
 template <int U> __device__ __forceinline__ uint32_t pb_u32(uint32_t v) { return (U >> 1) ? dpp_u32<0xF5>(v) : dpp_u32<0xA0>(v); }
 template <int U> __device__ __forceinline__ float pb_f32(float v) { return (U >> 1) ? dpp_f32<0xF5>(v) : dpp_f32<0xA0>(v); }
@@ -132,9 +151,11 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
     const int slot_lane = g * 4 + 2 * q;        // this lane's two records inside a 64-slot iteration
     const int toff = ((lane >> 1) & 3) * 4 + 2 * q;      // float offset inside the 4-fold tail of an image row
 
-    int lidx[T4];
+    // LDS address of this lane's chunk of step t in image row 0: formed once and kept opaque, so that a read's address
+    // is ONE instruction (col << 9) + loff[t] and the shift is not redone in every iteration
+    uint32_t loff[T4];
     #pragma unroll
-    for (int t = 0; t < T4; ++t) lidx[t] = lchunk(lane, t);
+    for (int t = 0; t < T4; ++t) { loff[t] = lds_addr(lds) + (uint32_t)lchunk(lane, t) * 16u; asm volatile("" : "+v"(loff[t])); }
 
     f4 fu[T4], acc[T4];
     f2 fut = {0.f, 0.f}, acct = {0.f, 0.f};
@@ -162,10 +183,12 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
         const int niter = max(__builtin_amdgcn_readlane(nit, 0), __builtin_amdgcn_readlane(nit, 32));
         const int64_t rbase = cm.roff[t] + s0 + slot_lane;
         const uint4 *recp = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned long long *>(cm.rowrec) + rbase);
-        float *sdst = s_cs + cm.coff[t];
-        float *swdst = HASW ? sw_cs + cm.coff[t] : nullptr;
-        const uint32_t dummy = cm.cslice[t * 17 + 16] + lane;
-        bool bad = false;
+        // (wave-uniform, in scalar registers: the stores address s as base + 32-bit byte offset)
+        const int64_t coff = uniform_i64(cm.coff[t]);
+        float *sdst = s_cs + coff;
+        float *swdst = HASW ? sw_cs + coff : nullptr;
+        const uint32_t dummy = (cm.cslice[t * 17 + 16] + lane) * 4u;      // byte offset of this lane's write-only slot
+        unsigned long long bad = 0ull;                            // lanes that met a slow entry
         // record prefetch ring (two 8-byte records per lane and iteration), clamped to the slice's own length
         uint4 rawq[PD];
         f2 wq[PD];
@@ -182,15 +205,25 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
         stg.store(lds, tid);
         __syncthreads();
         }
+        // One step.  Around its FMAs a step keeps only what every slot needs ("step diet"):
+        //   * what depends on the record alone is formed BEFORE the pair broadcast, once per iteration for the lane's two
+        //     records (one instruction there serves 64 records, after the broadcast 32): the column index `cy / cw` and the
+        //     byte offset of the store `oy / ow` = 4 cdst of an entry, the lane's dummy slot for padding (x == 0);
+        //   * a read's address is one v_lshl_add_u32 (col << 9) + loff[t];
+        //   * s = (den >= den_min) ? x rcp(den) : 0 needs no test of x: a padding slot holds x == +0 (zero-filled stream,
+        //     or cleared past the shorter slice's end), den >= den_min > 0 makes rcp(den) finite and >= 0, and
+        //     (+0) * that is +0 -- the value the select on `valid` gave; with den < den_min it is the select's 0;
+        //   * the slow path is only recorded, as the wave mask of the passed den tests (with the `dead` slots of the sparse
+        //     variants), and settled after the iteration under a wave-uniform branch (ORIANA_ROW_SLOW): the step
+        //     stores the fast value (0 there), the branch overwrites it with NaN from the same lane (stores of one lane to
+        //     one address stay in order) where the slot holds an ENTRY.  A padding slot is never slow: no NaN reaches it.
 #define ORIANA_ROW_STEP2(U)                                                                           \
             {                                                                                         \
-                const uint32_t bm = pb_u32<U>((U & 1) ? cur.w : cur.y);                               \
-                const float x = __uint_as_float(pb_u32<U>((U & 1) ? cur.z : cur.x));                  \
-                const int col = (int)((bm >> 16) & 0xFFu);                                            \
-                const bool valid = (x != 0.f);                                                        \
-                const f4 *vrow = lds + col * ROW4;                                                    \
+                const uint32_t col = pb_u32<U>((U & 1) ? cw : cy);                                    \
+                const float x = pb_f32<U>((U & 1) ? xz : xx);                                        \
                 f4 v[T4];                                                                             \
-                _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) v[tt] = vrow[lidx[tt]];             \
+                _Pragma("unroll") for (int tt = 0; tt < T4; ++tt)                                     \
+                    v[tt] = lds_read_f4(lshl_add<9>(col, loff[tt]));                                  \
                 f2 vt = {0.f, 0.f};                                                                   \
                 if (TAIL) vt = *reinterpret_cast<const f2 *>(tails + col * (TREP * 4) + toff);        \
                 f2 d01 = {0.f, 0.f}, d23 = {0.f, 0.f};                                                \
@@ -203,7 +236,7 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
                 float den = dd.x + dd.y;                                                              \
                 den += dpp_f32<0xB1>(den);                                                            \
                 const bool ok = den >= den_min;          /* false for 0, tiny and NaN */              \
-                const float s = (ok && valid) ? x * __builtin_amdgcn_rcpf(den) : 0.f;                 \
+                const float s = ok ? x * __builtin_amdgcn_rcpf(den) : 0.f;                            \
                 const float sw = HASW ? s * pb_f32<U>((U & 1) ? wcur.y : wcur.x) : s;                 \
                 const f2 ss = {sw, sw};                                                               \
                 if (!SROW) {                  /* (with s_rs the caller only wants s: R is not formed) */ \
@@ -215,16 +248,29 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
                 }                                                                                     \
                 const bool dead = SROW && !rowfilled && den == 0.f &&                                 \
                                   __float_as_uint(v[0].x) == 0x80000000u;                             \
-                const bool slow = valid && !ok && !dead;                                              \
-                bad = bad || slow;                                                                    \
-                const float sout = slow ? NAN : s;                                                    \
-                const uint32_t off = valid ? (bm & 0xFFFFu) : dummy;                                  \
-                sdst[off] = sout;                                                      \
-                if (HASW) swdst[off] = slow ? NAN : sw;                                               \
-                if (SROW && (U >> 1) == q) { if (U & 1) sbuf.y = sout; else sbuf.x = sout; }          \
+                okm[U] = __builtin_amdgcn_ballot_w64(ok || dead);                                     \
+                const uint32_t off = pb_u32<U>((U & 1) ? ow : oy);                                    \
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(sdst) + off) = s;                 \
+                if (HASW) *reinterpret_cast<float *>(reinterpret_cast<char *>(swdst) + off) = sw;     \
+                if (SROW && (U >> 1) == q) { if (U & 1) sbuf.y = s; else sbuf.x = s; }                \
                 _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) asm volatile("" : "+v"(acc[tt]));  \
-                asm volatile("" : "+v"(cur.x), "+v"(cur.y), "+v"(cur.z), "+v"(cur.w));                \
+                asm volatile("" : "+v"(xx), "+v"(xz), "+v"(cy), "+v"(cw), "+v"(oy), "+v"(ow));        \
             }
+        // The failed den tests of an iteration, off the hot path (taken where rows lie beyond n, whose den is 0, and
+        // otherwise rare: whole sweeps have no slow entry).  A slot is slow when it holds an entry (x != 0): NaN in place of
+        // the 0 the step stored, in s, in the weighted s and in the row-side copy, and the tile is flagged.
+#define ORIANA_ROW_SLOW(U)                                                                            \
+                {                                                                                     \
+                    const float x = pb_f32<U>((U & 1) ? xz : xx);                                    \
+                    const uint32_t off = pb_u32<U>((U & 1) ? ow : oy);                                \
+                    const unsigned long long slow = ~okm[U] & __builtin_amdgcn_ballot_w64(x != 0.f);  \
+                    bad |= slow;                                                                      \
+                    if ((slow >> lane) & 1ull) {                                                      \
+                        *reinterpret_cast<float *>(reinterpret_cast<char *>(sdst) + off) = NAN;       \
+                        if (HASW) *reinterpret_cast<float *>(reinterpret_cast<char *>(swdst) + off) = NAN;  \
+                        if (SROW && (U >> 1) == q) { if (U & 1) sbuf.y = NAN; else sbuf.x = NAN; }    \
+                    }                                                                                 \
+                }
         // One iteration = record U of each row at step U.  TRIM (the wave's final iteration): a row's records are packed
         // front-first inside its slice -- k_pack_fill puts the entry of rank k in the row at iteration k >> 2, record k & 3,
         // and every other slot of the zero-filled stream stays x == 0 -- so "record U holds an entry in some row" is
@@ -234,33 +280,44 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
 #define ORIANA_ROW_ITER(TRIM)                                                                         \
         {                                                                                             \
             const bool live = it < nit;                                                               \
-            uint4 cur = rawq[0];                                                                      \
+            const uint4 cur = rawq[0];                                                                \
             const f2 wcur = wq[0];                                                                    \
             if (!(TRIM)) {                                                                            \
                 _Pragma("unroll") for (int d = 0; d + 1 < PD; ++d) { rawq[d] = rawq[d + 1]; wq[d] = wq[d + 1]; }  \
                 const int nx = (it + PD < nit) ? it + PD : nit - 1;                                   \
-                if (nit > 0) { rawq[PD - 1] = recp[(int64_t)nx * 32]; if (HASW) wq[PD - 1] = *reinterpret_cast<const f2 *>(w_nz + rbase + (int64_t)nx * 64); }  \
+                if (nit > 0) { rawq[PD - 1] = recp[(size_t)(uint32_t)nx * 32]; if (HASW) wq[PD - 1] = *reinterpret_cast<const f2 *>(w_nz + rbase + (int64_t)nx * 64); }  \
             }                                                                                         \
-            if (!live) { cur.x = 0u; cur.z = 0u; }               /* past the end of the shorter slice: padding */ \
+            /* the lane's two counts; past the end of the shorter slice: padding.  (Opaque: x != 0 stays ONE float compare) */ \
+            float xx = live ? __uint_as_float(cur.x) : 0.f, xz = live ? __uint_as_float(cur.z) : 0.f; \
+            asm volatile("" : "+v"(xx), "+v"(xz));                                                    \
             int rem = 4;                                                                              \
             if (TRIM) {                          /* lane q of a pair holds records 2q (x) and 2q + 1 (z) */ \
-                const unsigned long long bx = __ballot(__uint_as_float(cur.x) != 0.f);                \
-                const unsigned long long bz = __ballot(__uint_as_float(cur.z) != 0.f);                \
+                const unsigned long long bx = __ballot(xx != 0.f);                                    \
+                const unsigned long long bz = __ballot(xz != 0.f);                                    \
                 const unsigned long long odd = 0xAAAAAAAAAAAAAAAAull;                                 \
                 rem = (bz & odd) ? 4 : (bx & odd) ? 3 : bz ? 2 : bx ? 1 : 0;                          \
             }                                                                                         \
+            /* per record, before the broadcast: column index, byte offset of the store (padding: the dummy slot) */ \
+            uint32_t cy = (cur.y >> 16) & 0xFFu, cw = (cur.w >> 16) & 0xFFu;                          \
+            uint32_t oy = (xx != 0.f) ? (cur.y & 0xFFFFu) << 2 : dummy;                               \
+            uint32_t ow = (xz != 0.f) ? (cur.w & 0xFFFFu) << 2 : dummy;                               \
             f2 sbuf = {0.f, 0.f};                                                                     \
+            unsigned long long okm[4] = {~0ull, ~0ull, ~0ull, ~0ull};                                 \
             if (rem > 0) ORIANA_ROW_STEP2(0)                                                          \
             if (rem > 1) ORIANA_ROW_STEP2(1)                                                          \
             if (rem > 2) ORIANA_ROW_STEP2(2)                                                          \
             if (rem > 3) ORIANA_ROW_STEP2(3)                                                          \
+            if (~(okm[0] & okm[1] & okm[2] & okm[3])) {                                               \
+                ORIANA_ROW_SLOW(0) ORIANA_ROW_SLOW(1) ORIANA_ROW_SLOW(2) ORIANA_ROW_SLOW(3)           \
+            }                                                                                         \
             if (SROW && live) *reinterpret_cast<f2 *>(s_rs + rbase + (int64_t)it * 64) = sbuf;        \
         }
         for (int it = 0; it + 1 < niter; ++it) ORIANA_ROW_ITER(false)
         if (niter > 0) { const int it = niter - 1; ORIANA_ROW_ITER(true) }
 #undef ORIANA_ROW_ITER
+#undef ORIANA_ROW_SLOW
 #undef ORIANA_ROW_STEP2
-        if (__any(bad) && lane == 0) tile_flag[t] = 1;
+        if (bad && lane == 0) tile_flag[t] = 1;
     }
     if (row < cm.n && !SROW) {
         // (slab p >= 1 holds the rows of the split row blocks only: stride (n - 256 nfull) rows)
@@ -344,9 +401,15 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
     const int64_t cbA = DUAL ? c2 : c2 * 2, cbB = DUAL ? c2 : c2 * 2 + 1;
     const bool hasB = !DUAL && cbB < cm.ncb;
     const int toff = Im::toff(lane);
-    int lidx[T4];
+    // LDS address of this lane's chunk of step t in image row 0, formed once and kept opaque (see k_row_pass_k100): a
+    // read's address is one instruction r * (ROW4 * 16) + loff[t]
+    uint32_t loff[T4];
     #pragma unroll
-    for (int t = 0; t < T4; ++t) lidx[t] = Im::lidx(lane, t);
+    for (int t = 0; t < T4; ++t) { loff[t] = k100::lds_addr(lds) + (uint32_t)Im::lidx(lane, t) * 16u; asm volatile("" : "+v"(loff[t])); }
+    auto row_read = [](uint32_t r, uint32_t off) {
+        if constexpr ((ROW4 & (ROW4 - 1)) == 0) return k100::lds_read_f4(k100::lshl_add<__builtin_ctz(ROW4 * 16)>(r, off));
+        else return k100::lds_read_f4(r * (uint32_t)(ROW4 * 16) + off);
+    };
     f4 accA[T4], accB[T4];
     float actA = 0.f, actB = 0.f;
     #pragma unroll
@@ -375,12 +438,11 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
 #define ORIANA_COL_STEP4(ACC, ACT, U)                                                                 \
                 {                                                                                     \
                     const float s = qb_f32<U>(svc);                                                   \
-                    const int r = (int)qb_u32<U>(rvc);                                                \
-                    const f4 *vrow = lds + r * ROW4;                                                  \
+                    const uint32_t r = qb_u32<U>(rvc);                                                \
                     const f2 ss = {s, s};                                                             \
                     {                                                      \
                     _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) {                               \
-                        const f4 v = vrow[lidx[tt]];                                                  \
+                        const f4 v = row_read(r, loff[tt]);                                          \
                         ACC[tt].xy = __builtin_elementwise_fma(ss, v.xy, ACC[tt].xy);                 \
                         ACC[tt].zw = __builtin_elementwise_fma(ss, v.zw, ACC[tt].zw);                 \
                     }                                                                                 \
@@ -393,14 +455,13 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
 #define ORIANA_COL_STEP4D(U)                                                                          \
                 {                                                                                     \
                     const float s = qb_f32<U>(svc);                                                   \
-                    const int r = (int)qb_u32<U>(rvc);                                                \
-                    const f4 *vrow = lds + r * ROW4;                                                  \
+                    const uint32_t r = qb_u32<U>(rvc);                                                \
                     const f2 ss = {s, s};                                                             \
                     _Pragma("unroll") for (int tt = 0; tt < T4; ++tt) {                               \
-                        const f4 v = vrow[lidx[tt]];                                                  \
+                        const f4 v = row_read(r, loff[tt]);                                          \
                         accA[tt].xy = __builtin_elementwise_fma(ss, v.xy, accA[tt].xy);               \
                         accA[tt].zw = __builtin_elementwise_fma(ss, v.zw, accA[tt].zw);               \
-                        const f4 v2 = vrow[IMG4 + lidx[tt]];                                          \
+                        const f4 v2 = row_read(r, loff[tt] + IMG4 * 16);                             \
                         accB[tt].xy = __builtin_elementwise_fma(ss, v2.xy, accB[tt].xy);              \
                         accB[tt].zw = __builtin_elementwise_fma(ss, v2.zw, accB[tt].zw);              \
                     }                                                                                 \
