@@ -494,6 +494,27 @@ int oriana_gamma_update_finalize_lazy(double *a1, double *a2_row, float *Elog,
                                  const double *rate_vec, int64_t r, int64_t K, float *FU_next, float *mu_out, float *upart,
                                  void *stream);
 
+/* The step between two row passes of a FOLD-IN (oriana_amd/models/gap.py: transform; no counterpart in the reference): pCMF's
+ * cell-side update for cells the model was not fitted on, the gene side frozen -- per cell a fixed-point iteration of
+ *   a1 <- max(1e-15, alpha1 + Z_i),  Z_i = Z + F * sum_slabs R  (as oriana_gamma_update_finalize_lazy: packed rows, nslab, slab_row0,
+ *   row_index),  E[log U] = f32(psi(f32(a1))) - logf(f32(a2_row))   (a2_row [K] = alpha2 + sum_j V_hat: constant over the iteration),
+ *   stored MINUS its row maximum (mu_out = 0): the softmax over the factors does not see the shift, and the float32 exponentials
+ *   of the slow path then do not underflow for a cell whose shapes sit near the clamp.
+ * Per row: a cell with active[o] != 0 whose update satisfies |a1_new - a1| <= tol * a1 in every factor FREEZES: active[o] = 0,
+ * froze_at[o] = it, and neither its a1, its Elog nor its row of FU_next is written by this or any later call.  Every other active
+ * cell gets a1 (float64), Elog (float32) and the PREP outputs of oriana_gamma_update_finalize_prep: FU_next (r, Kp), mu_out [r],
+ * upart [4 * oriana_foldin_update_blocks(r)] (the statistics cover all rows: a frozen row enters with the mu_out it stored last).
+ * *n_active += the cells still active after the call (one atomic per work-group; the caller zeroes it).  No (r, K) float64
+ * matrix but a1 is touched, no column sums are formed, Z is not written back.  FU_next may be F itself (in place).
+ * R == NULL: the START -- a1 is taken as it is, every active cell gets Elog, FU_next, mu_out from it; Z, F, alpha1, froze_at,
+ * n_active are not read.  Every K with oriana_kpad(K) != 0 and any pointer alignment is served (odd K above 64 and unaligned
+ * buffers by an element-per-lane instantiation); ORIANA_EKRANGE only where no row pass exists (K above 256). */
+int64_t oriana_foldin_update_blocks(int64_t r);
+int oriana_foldin_update(double *a1, float *Elog, uint8_t *active, int32_t *froze_at, int32_t *n_active,
+                         const double *alpha1, const double *a2_row, const float *Z, const float *F, const float *R,
+                         int64_t nslab, int64_t slab_row0, const int32_t *row_index, int64_t r, int64_t K, double tol,
+                         int64_t it, float *FU_next, float *mu_out, float *upart, void *stream);
+
 /* M-step for one Gamma node (gap.py:117-129; utils.py:39-51):
  *   p1 = max(1e-15, nan_to_num(inverse_digamma(log(p2) + f32(colsum_Elog / count))))
  *   p2 = max(1e-15, nan_to_num(p1 / (colsum_E / count)))            (K-vectors, f64, in place) */

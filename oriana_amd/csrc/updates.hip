@@ -341,6 +341,171 @@ __global__ __launch_bounds__(256) void k_gamma_update_vec(const GuVecArgs A) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The step between two row passes of a FOLD-IN (models/gap.py transform: new cells against a frozen gene side): the cell
+// side of k_gamma_update_vec<FIN> with everything a fold-in has no use for left out -- no a2 / U_hat stores, no column sums,
+// Z is read (the slow path's additions) and not written back -- and a per-cell convergence test in their place.  Per row, in
+// packed order (o = row_index[p]):
+//   a1_new = max(1e-15, alpha1 + Z[o] + F[p] * sum_slabs R[p]);   still = exists k: !(|a1_new - a1| <= tol * a1)
+//   active[o] && !still : the cell FREEZES -- active[o] = 0, froze_at[o] = it; nothing else of the row is written, now or later
+//   active[o] && still  : a1[o] = a1_new, Elog[o] = f32(psi(f32(a1_new))) - logf(f32(a2_row)) (gamma_meanlog_f32_lg: the cast
+//                         of the sweep) MINUS ITS ROW MAXIMUM, and the PREP outputs of k_gamma_update_vec: FUn[p], mu[p] (= 0),
+//                         the statistics partials.
+// The row maximum: the responsibilities are a softmax over the factors, which a shift of the cell's whole row leaves as it is.
+// A sweep stores E[log U] unshifted (the M-step reads it) and its slow path restates the reference's float32 exp(lu + lv), which
+// underflows to r = 0 for a cell whose every E[log U] is below ~-100 (a shape near the clamp: psi(1e-15) = -1e15) -- such a
+// cell would never leave alpha1.  Nothing but the next row phase reads a fold-in's E[log U], so it is stored with maximum 0:
+// FUn = exp(E[log U] - max) is the same numbers, every row passes the validity test, and the slow path's exponentials of
+// the factors that carry the cell's mass are of order exp(lv).
+// The statistics of the validity test cover ALL rows: a frozen row enters with the maximum it stored last (mu[p] is read back).
+// FUn may be the buffer F points to (every lane reads its own elements of a row before it writes them; no other kernel reads
+// F meanwhile -- a fold-in has no column pass).  n_active += the rows still active: one atomic per work-group.
+// R == NULL is the START: a1 is taken as it is and every active row gets Elog, FUn and mu from it (no test, no counter).
+// NC pieces of VEC factors per lane, LPR lanes per row: NC = 1 are the configurations of gu_vec_cfg; <1, 64, 4> -- a wave per
+// row, element accesses -- serves the K and the pointers those leave out (odd K above 64, unaligned buffers).
+struct FoldinArgs {
+    double *a1;
+    float *Elog;
+    uint8_t *active;
+    int32_t *froze_at, *n_active;
+    const double *alpha1, *a2_row;
+    const float *Z, *F, *R;
+    const int32_t *row_index;
+    float *FUn, *mu, *upart;
+    int64_t r, slab_row0;
+    int K, Kp, nslab, rpb, it;
+    double tol;
+};
+
+template <int VEC, int LPR, int NC>
+__global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
+    constexpr int RPW = 64 / LPR, NW = 4;
+    static_assert(LPR >= 8, "lanes_max / lanes_or reduce over groups of at least 8 lanes");
+    __shared__ float sred[5][NW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int cg = lane & (LPR - 1), sr = lane / LPR;
+    const int K = A.K, Kp = A.Kp;
+    const int64_t r = A.r;
+    const int64_t r0 = (int64_t)blockIdx.x * A.rpb;
+    const int64_t r1 = (r0 + A.rpb < r) ? r0 + A.rpb : r;
+    const bool start = A.R == nullptr;
+    // the K-vectors, once per work-group: this lane's factors of alpha1 and of log a2
+    double p1[NC][VEC];
+    float lg[NC][VEC];
+    #pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int k0 = (cg + c * LPR) * VEC;
+        #pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            p1[c][v] = (k0 < K && !start) ? A.alpha1[k0 + v] : 1.0;
+            lg[c][v] = k0 < K ? logf((float)A.a2_row[k0 + v]) : 0.0f;
+        }
+    }
+    float st_sum = 0.f, st_sq = 0.f, st_cnt = 0.f, st_min = INFINITY, n_still = 0.f;
+    for (int64_t rb = r0 + w * RPW; rb < r1; rb += NW * RPW) {
+        const int64_t row = rb + sr;
+        const bool inr = row < r1;
+        const int64_t orow = inr ? (A.row_index ? (int64_t)A.row_index[row] : row) : 0;
+        const bool was = inr && A.active[orow] != 0;
+        double s1[NC][VEC];
+        float el[NC][VEC];
+        bool moved = false;
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int k0 = (cg + c * LPR) * VEC;
+            #pragma unroll
+            for (int v = 0; v < VEC; ++v) { el[c][v] = -INFINITY; s1[c][v] = 1.0; }
+            if (was && k0 < K) {
+                double old[VEC];
+                ld_f64<VEC>(old, A.a1 + orow * K + k0);
+                if (start) {
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) s1[c][v] = old[v];
+                    moved = true;
+                } else {
+                    float rr[VEC], f[VEC], z[VEC];
+                    ld_f32<VEC>(rr, A.R + row * Kp + k0);
+                    ld_f32<VEC>(f, A.F + row * Kp + k0);
+                    ld_f32<VEC>(z, A.Z + orow * K + k0);
+                    const int ns = row >= A.slab_row0 ? A.nslab : 1;
+                    for (int sl = 1; sl < ns; ++sl) {
+                        float r2[VEC];
+                        ld_f32<VEC>(r2, A.R + ((int64_t)sl * (r - A.slab_row0) + row) * Kp + k0);
+                        #pragma unroll
+                        for (int v = 0; v < VEC; ++v) rr[v] += r2[v];
+                    }
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                        const float zf = fmaf(f[v], rr[v], z[v]) + 0.0f;                        // k_finalize (accumulate)
+                        s1[c][v] = clamp_eps(p1[c][v] + (double)zf);
+                        if (!(fabs(s1[c][v] - old[v]) <= A.tol * old[v])) moved = true;
+                    }
+                }
+                #pragma unroll
+                for (int v = 0; v < VEC; ++v) el[c][v] = gamma_meanlog_f32_lg(s1[c][v], lg[c][v]);
+            }
+        }
+        // (wave-uniform from here: every lane takes part in its row's reductions; lanes beyond K, of a frozen row or beyond
+        //  the last row hold -inf)
+        const bool write = was && lanes_or<LPR>(moved ? 1u : 0u) != 0u;
+        float mx = -INFINITY;
+        bool bad = false;
+        #pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            #pragma unroll
+            for (int v = 0; v < VEC; ++v) { if (el[c][v] != el[c][v]) bad = true; mx = fmaxf(mx, el[c][v]); }
+        }
+        mx = lanes_max<LPR>(mx);
+        const int badi = (int)lanes_or<LPR>(bad ? 1u : 0u);
+        if (write) {
+            #pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int k0 = (cg + c * LPR) * VEC;
+                if (k0 < K) {
+                    float fu[VEC];
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) fu[v] = (float)exp((double)el[c][v] - (double)mx);
+                    // (E[log U] goes out MINUS its row maximum, see above; a row with a NaN as it is)
+                    float els[VEC];
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) els[v] = badi ? el[c][v] : el[c][v] - mx;
+                    if (!start) st_f64<VEC>(A.a1 + orow * K + k0, s1[c]);
+                    st_f32<VEC>(A.Elog + orow * K + k0, els);
+                    st_f32<VEC>(A.FUn + row * Kp + k0, fu);
+                }
+            }
+        }
+        if (inr && cg == 0) {
+            float m1;
+            if (write) {
+                m1 = badi ? NAN : 0.0f;                             // (the maximum of what was stored)
+                A.mu[row] = m1;
+                n_still += 1.f;
+            } else {
+                m1 = A.mu[row];                                     // a frozen row: the maximum of its last update
+                if (was) { A.active[orow] = 0; A.froze_at[orow] = A.it; }
+            }
+            if (m1 == m1) {
+                if (fabsf(m1) <= STAT_MAX) { st_sum += m1; st_sq += m1 * m1; st_cnt += 1.f; }                  // as k_row_stats
+                st_min = fminf(st_min, m1);
+            }
+        }
+    }
+    st_sum = wave_sum(st_sum); st_sq = wave_sum(st_sq); st_cnt = wave_sum(st_cnt); st_min = -wave_max(-st_min);
+    n_still = wave_sum(n_still);
+    if (lane == 0) { sred[0][w] = st_sum; sred[1][w] = st_sq; sred[2][w] = st_cnt; sred[3][w] = st_min; sred[4][w] = n_still; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float *pp = A.upart + 4 * (size_t)blockIdx.x;
+        pp[0] = ((sred[0][0] + sred[0][1]) + sred[0][2]) + sred[0][3];
+        pp[1] = ((sred[1][0] + sred[1][1]) + sred[1][2]) + sred[1][3];
+        pp[2] = ((sred[2][0] + sred[2][1]) + sred[2][2]) + sred[2][3];
+        pp[3] = fminf(fminf(sred[3][0], sred[3][1]), fminf(sred[3][2], sred[3][3]));
+        const int left = (int)(((sred[4][0] + sred[4][1]) + sred[4][2]) + sred[4][3]);       // (<= 512 rows: exact in float32)
+        if (A.n_active && left > 0) atomicAdd(A.n_active, left);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_colsum_f64(double *__restrict__ out, const double *__restrict__ A,
                                                     const float *__restrict__ mul, int64_t r, int K, int rpb) {
     __shared__ double red[256];
@@ -653,6 +818,52 @@ extern "C" int oriana_gamma_update_finalize_lazy(double *a1, double *a2_row, flo
     GuVecArgs a = {a1, nullptr, nullptr, Elog, colsum_E, colsum_Elog, prior1, prior2, nullptr, nullptr, rate_vec, nullptr, nullptr, r, (int)K, 0,
                    Z, F, R, row_index, (int)Kp, (int)nslab, slab_row0, FU_next, mu_out, upart, a2_row};
     if (!gu_vec_launch<true>(a, (hipStream_t)stream)) return ORIANA_EKRANGE;
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+// rows per work-group of k_foldin_update: a function of r alone (every configuration walks whole multiples of its rows per
+// iteration, 4 .. 32), so that the caller can size `upart` before it knows which configuration its pointers get
+static inline int foldin_rpb(int64_t r) { return rows_per_block(r, 32); }
+
+extern "C" int64_t oriana_foldin_update_blocks(int64_t r) {
+    if (r <= 0) return 0;
+    const int rpb = foldin_rpb(r);
+    return (r + rpb - 1) / rpb;
+}
+
+template <int VEC>
+static void foldin_launch_lpr(const FoldinArgs &a, int lpr, int64_t nblk, hipStream_t s) {
+    const dim3 g((unsigned)nblk), b(256);
+    switch (lpr) {
+    case 8: hipLaunchKernelGGL((k_foldin_update<VEC, 8, 1>), g, b, 0, s, a); break;
+    case 16: hipLaunchKernelGGL((k_foldin_update<VEC, 16, 1>), g, b, 0, s, a); break;
+    case 32: hipLaunchKernelGGL((k_foldin_update<VEC, 32, 1>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_foldin_update<VEC, 64, 1>), g, b, 0, s, a); break;
+    }
+}
+
+extern "C" int oriana_foldin_update(double *a1, float *Elog, uint8_t *active, int32_t *froze_at, int32_t *n_active,
+                                    const double *alpha1, const double *a2_row, const float *Z, const float *F, const float *R,
+                                    int64_t nslab, int64_t slab_row0, const int32_t *row_index, int64_t r, int64_t K, double tol,
+                                    int64_t it, float *FU_next, float *mu_out, float *upart, void *stream) {
+    if (r < 0 || K <= 0 || nslab < 1 || nslab > 65535 || slab_row0 < 0 || it < 0 || it > 0x7fffffffLL || !(tol >= 0.0)) return ORIANA_EINVAL;
+    const int64_t Kp = oriana_kpad(K);
+    if (Kp == 0) return ORIANA_EKRANGE;                // (no row pass serves this K: there is no F / R layout to read)
+    if (r == 0) return 0;
+    if (!a1 || !Elog || !active || !a2_row || !FU_next || !mu_out || !upart) return ORIANA_EINVAL;
+    if (R && (!Z || !F || !alpha1 || !froze_at)) return ORIANA_EINVAL;
+    FoldinArgs a = {a1, Elog, active, froze_at, R ? n_active : nullptr, alpha1, a2_row, Z, F, R, row_index, FU_next, mu_out, upart,
+                    r, slab_row0, (int)K, (int)Kp, (int)nslab, foldin_rpb(r), (int)it, tol};
+    const int64_t nblk = (r + a.rpb - 1) / a.rpb;
+    const bool wide_ok = aligned_to(a1, 16) && aligned_to(Elog, 16) && aligned_to(Z, 16) && aligned_to(F, 16) && aligned_to(R, 16) &&
+                         aligned_to(FU_next, 16);
+    hipStream_t s = (hipStream_t)stream;
+    int vec, lpr;
+    if (!gu_vec_cfg(K, wide_ok, &vec, &lpr)) hipLaunchKernelGGL((k_foldin_update<1, 64, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else if (vec == 4) foldin_launch_lpr<4>(a, lpr, nblk, s);
+    else if (vec == 2) foldin_launch_lpr<2>(a, lpr, nblk, s);
+    else foldin_launch_lpr<1>(a, lpr, nblk, s);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

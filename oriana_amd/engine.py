@@ -799,6 +799,77 @@ def zq_gap(ws, Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, **kw):
     zq(ws, Z_hat_i, Z_hat_j, None, log_U_hat, log_V_hat, **kw)
 
 
+def row_sums_over_k(ws, K):
+    """rowsum(x) / K per cell and factor, (n, K) float32 in the caller's row order: the row pass against all-ones factors
+    (uniform responsibilities: s = x / K, R = sum_j s), completed as the sweeps complete Z_i."""
+    ct = ws.ct
+    ones_u, ones_v = ws.extra('ONE_U', ct.n), ws.extra('ONE_V', ct.m)
+    ones_u[:, :K] = 1.0
+    ones_v[:, :K] = 1.0
+    Z = torch.zeros(max(ct.n, 1), K, dtype=torch.float32, device=ct.device)
+    ws.tile_flag.zero_()
+    st = stream_ptr()
+    call('oriana_row_pass', ct.sparse_struct, ptr(ones_u), ptr(ones_v), None, ptr(ws.R), ptr(ws.s_cs), None, None,
+         ptr(ws.tile_flag), K, st)
+    call('oriana_finalize_slabs_from', ptr(Z), ptr(ones_u), ptr(ws.R), 1, 0, ptr(ct.row_perm), ct.n, K, st)
+    return Z[:ct.n]
+
+
+def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5, ws=None):
+    """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted pCMF model whose gene side stays as it is: the
+    per-cell fixed point of  a1 <- max(1e-15, alpha1 + sum_j x_ij r_ijk),  r_ij. = softmax_k(E[log U]_ik + E[log V]_jk),
+    E[log U] = psi(a1) - log a2_row  (gap.py:97-102 with sum_j V_hat frozen).  `a1` (n', K) float64 device tensor: the start,
+    updated in place; log_V_hat (m, K) float32, alpha1 / a2_row [K] float64: the model's, only read.
+    Each iteration is the row phase of a sweep on a workspace of this call's own (zq_gap(phase='rows', finalize_rows=False):
+    validity test + gene-side factor from log_V_hat through the new tiles' gene order, row pass, slow path) and ONE launch of
+    oriana_foldin_update, which completes Z_i, updates a1 / E[log U], freezes the cells that moved by at most tol * a1 and
+    prepares the next row pass's FU in place.  The host reads the number of active cells every `check_every` iterations
+    and stops at zero.  Returns (froze_at int32 [n'] -- the 0-based iteration a cell froze at, n_iter if never --, the number
+    of cells still active, the iterations run)."""
+    if ct_new.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    n, m, dev = ct_new.n, ct_new.m, ct_new.device
+    n_iter, check_every, tol = int(n_iter), int(check_every), float(tol)
+    if n_iter < 0 or check_every < 1 or not tol >= 0.0:
+        raise ValueError('fold_in needs n_iter >= 0, check_every >= 1 and tol >= 0')
+    _check_f32(log_V_hat, (m, K))
+    if a1.dtype != torch.float64 or tuple(a1.shape) != (n, K) or not a1.is_contiguous():
+        raise TypeError('a1 must be a C-contiguous (n\', K) float64 device tensor')
+    froze_at = torch.full((n,), n_iter, dtype=torch.int32, device=dev)
+    if n == 0:
+        return froze_at, 0, 0
+    if ws is None:
+        ws = ZWorkspace(ct_new, K)
+    f32 = dict(dtype=torch.float32, device=dev)
+    # the cell side of every factor preparation comes from oriana_foldin_update (the fused form of factor_prep_pair), in
+    # place: no kernel reads FU while it is rewritten, so the double buffer of the sweeps is one buffer here
+    ws.prep_blocks = int(_lib.load().oriana_foldin_update_blocks(n))
+    ws.FU_alt = ws.FU
+    ws.mu_u = torch.zeros(n, **f32)
+    ws.upart = torch.zeros(4 * ws.prep_blocks, **f32)
+    lu = torch.empty(n, K, **f32)
+    Zi, Zj = torch.empty(n, K, **f32), torch.empty(max(m, 1), K, **f32)       # (Z_j: the slow path adds into it; never read)
+    active = torch.ones(n, dtype=torch.uint8, device=dev)
+    left = torch.zeros(max(n_iter, 1), dtype=torch.int32, device=dev)        # one counter per iteration: no clearing launch
+    st = stream_ptr()
+    call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), None, None, None, ptr(a2_row), None, None, None, 1, 0,
+         ptr(ct_new.row_perm), n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
+    n_left, done = n, 0
+    for it in range(n_iter):
+        ws.fu_pending, ws.fu_source = True, lu.data_ptr()
+        zq_gap(ws, Zi, Zj, lu, log_V_hat, phase='rows', finalize_rows=False)
+        with _span(ws, 'foldin_update'):
+            call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), ptr(froze_at), ptr(left) + 4 * it, ptr(alpha1), ptr(a2_row),
+                 ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0, ptr(ct_new.row_perm), n, K, tol, it,
+                 ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
+        done = it + 1
+        if done % check_every == 0 or done == n_iter:
+            n_left = int(left[it].item())
+            if n_left == 0:
+                break
+    return froze_at, n_left, done
+
+
 def _have_sliced(ct):
     """Do the sliced kernels run?  Not on a hybrid layout whose genes are all dense."""
     return ct.ms > 0 or ct.dense is None

@@ -311,6 +311,18 @@ class FactorModel:
         """The evidence lower bound of the current variational state (GaP); NotImplementedError on the other models."""
         raise NotImplementedError(self._no_elbo)
 
+    # Folding new cells into a fitted model exists for pCMF only (models/gap.py).  A new cell of the zero-inflated models needs
+    # a dropout posterior of its own (p_d over its zeros, which the cell-side rate then reads through D_hat^T), and the sparse
+    # models' responsibilities run against the masked gene images (S_tilde, S_hat): neither is the frozen-gene-side iteration
+    # of oriana_foldin_update.
+    _no_transform = ('transform() is defined for pCMF (GaP) only: folding a new cell into a zero-inflated model needs the dropout '
+                     'posterior of that unseen cell, and the sparse models evaluate the responsibilities against masked gene '
+                     'images; neither fold-in is implemented')
+
+    def transform(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False):
+        """E[U] of cells the model was not fitted on (GaP); NotImplementedError on the other models."""
+        raise NotImplementedError(self._no_transform)
+
     def factors(self):
         """base.py:97-98: (U[:], V[:]) as host arrays."""
         return self.U[:], self.V[:]

@@ -162,6 +162,70 @@ class GaP(FactorModel):
         t = self._elbo_terms()
         return float(t[0] - t[1] - t[2] - t[3] - t[4])
 
+    # ---- folding in new cells ----------------------------------------------------------------------------------------------
+    # For a cell the model was not fitted on, with the gene side held fixed, the cell-side update of the sweep (lines 97-102 of
+    # the reference's gap.py) is a fixed-point iteration of that cell alone: a2 = alpha2 + sum_j V_hat never moves, a1 <- alpha1 +
+    # sum_j x_ij r_ijk with r the softmax of E[log U]_i. + E[log V]_j. .  engine.fold_in runs it on a workspace of its own:
+    # nothing the model or its workspace hold is written ("Folding in new cells").
+    transform_unconverged_ = None
+
+    def _query_counts(self, cmatrix):
+        """The new cells as CountTiles on the sliced layout (packed here unless they already are), gene count checked first."""
+        from .base import _is_sparse_input
+        if isinstance(cmatrix, engine.CountTiles):
+            ct = cmatrix
+        else:
+            sparse = _is_sparse_input(cmatrix)
+            if sparse:
+                X = cmatrix._sparse if hasattr(cmatrix, '_sparse') else cmatrix
+            else:
+                X = cmatrix.as_array() if hasattr(cmatrix, 'as_array') else cmatrix
+                if not isinstance(X, torch.Tensor):
+                    import numpy as np
+                    X = np.asarray(X)
+            if len(X.shape) != 2 or int(X.shape[1]) != self.m:
+                raise ValueError('transform() needs an (n\', %d) count matrix: the model was fitted on %d genes, got shape %s'
+                                 % (self.m, self.m, tuple(X.shape)))
+            pack = engine.CountTiles.from_scipy if sparse else engine.CountTiles.from_dense
+            ct = pack(X, self.device, dense_density=None)
+        if ct.m != self.m:
+            raise ValueError('transform() needs counts over the %d genes the model was fitted on, got %d' % (self.m, ct.m))
+        if ct.gd:
+            raise ValueError('transform() walks the sliced layout only: pack the new counts without dense_density')
+        return ct
+
+    def transform(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False, check_every=5):
+        """Fold new cells into the fitted model: E[U] = a1 / a2_row of `cmatrix` (anything the constructor takes; the same
+        genes) as a host (n', K) float64 array, V and the priors as they are.  Each cell iterates its own update until it
+        moves by at most tol * a1 in every factor (then it is frozen: its result does not depend on the other cells) or
+        `n_iter` is reached; ``transform_unconverged_`` counts the cells that never froze.  `init`: (n', K) starting a1
+        (default alpha1 + rowsum(x) / K: uniform responsibilities, no RNG).  return_params=True: (E[U], a1, a2_row, the
+        0-based iteration each cell froze at -- n_iter for those that did not).  Under row sharding the call is local to the
+        rank (V is replicated): no collective."""
+        import numpy as np
+        ct = self._query_counts(cmatrix)
+        K, dev, nq = self.k, self.device, ct.n
+        sum_v = self._accV[0] if self._v_sums_in_acc else self._sumV[0]          # as the sweep reads sum_j V_hat
+        a2_row = torch.clamp(torch.nan_to_num(self.alpha2.tensor + sum_v), min=1e-15)       # gap.py:98, 100
+        alpha1 = self.alpha1.tensor
+        ws = engine.ZWorkspace(ct, K) if nq > 0 else None
+        if init is not None:
+            a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
+            if tuple(a1.shape) != (nq, K):
+                raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
+            a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
+        elif nq > 0:
+            a1 = alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)
+        else:
+            a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
+        a1 = torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
+        froze_at, left, _ = engine.fold_in(ct, K, self._log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=check_every, ws=ws)
+        self.transform_unconverged_ = int(left)
+        E = (a1 / a2_row).cpu().numpy()
+        if return_params:
+            return E, a1.cpu().numpy(), a2_row.cpu().numpy(), froze_at.cpu().numpy()
+        return E
+
     def _init_extra(self):
         if os.environ.get('ORIANA_LAZY_U', '1') != '0':
             from ..parameters import LazyParameter

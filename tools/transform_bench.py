@@ -1,0 +1,164 @@
+# -*- coding: utf-8 -*-
+"""Times a fold-in (GaP.transform's loop, engine.fold_in) against the same loop composed from the entries that existed before
+oriana_foldin_update: row phase + oriana_gamma_update_finalize_prep on throw-away (n', K) buffers.
+
+Default: 65,536 x 30,000 new cells, K = 100, 90 % zeros (the benchmark's generator), 20 forced iterations (tol = 0) against
+the gene side of a model fitted on `--fit-rows` cells of the same generator for `--fit-sweeps` sweeps.  Device events
+around whole loops (after a warm-up loop of each form, the two forms alternating, `--reps` times), then one loop of each
+form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
+
+    python tools/transform_bench.py --out profiles/transform_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--cells', type=int, default=65536)
+    ap.add_argument('--genes', type=int, default=30000)
+    ap.add_argument('--k', type=int, default=100)
+    ap.add_argument('--zeros', type=float, default=0.10, help='zero_inflation_level of the generator (0.10: ~90 %% zeros)')
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--fit-rows', type=int, default=1000000)
+    ap.add_argument('--fit-sweeps', type=int, default=10)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--chunk-rows', type=int, default=8192)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
+    from oriana_amd import engine
+    from oriana_amd._lib import call, ptr, stream_ptr
+    from oriana_amd.models import GaP
+    from oriana_amd.singlecell import SyntheticCounts
+    dev = torch.device('cuda', 0)
+    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
+
+    # ---- the fitted gene side -------------------------------------------------------------------------------------------------
+    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
+                                           dense_density=engine.auto_dense_density(args.fit_rows, m, K))
+    a1, b1 = gen.initial_shapes()
+    model = GaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    del a1, b1
+    model.fit(args.fit_sweeps)
+    torch.cuda.synchronize()
+
+    # ---- the new cells (same seed: the same V; their own loadings) ------------------------------------------------------------
+    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
+    torch.cuda.synchronize()
+    pack_ms = (time.perf_counter() - t0) * 1e3
+
+    alpha1, alpha2, lv = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat
+    sum_v = (model._accV[0] if model._v_sums_in_acc else model._sumV[0]).clone()
+    a2_row = torch.clamp(alpha2 + sum_v, min=1e-15)
+    ws_f = engine.ZWorkspace(ct, K)
+    start = (alpha1[None, :] + engine.row_sums_over_k(ws_f, K).to(torch.float64)).contiguous()
+
+    def fused(timer=None):
+        ws_f.timer = timer
+        a1q = start.clone()
+        engine.fold_in(ct, K, lv, alpha1, a2_row, a1q, args.iters, 0.0, ws=ws_f)
+        ws_f.timer = None
+        return a1q
+
+    # the composed loop: what a caller could assemble before -- the sweep's cell side on buffers of its own
+    ws_c = engine.ZWorkspace(ct, K)
+    f64 = dict(dtype=torch.float64, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    c_a2, c_E = torch.ones(nq, K, **f64), torch.empty(nq, K, **f64)
+    c_lu, c_Zi, c_Zj = torch.empty(nq, K, **f32), torch.empty(nq, K, **f32), torch.empty(m, K, **f32)
+    c_sums = torch.zeros(2, K, **f64)
+
+    def composed(timer=None):
+        ws_c.timer = timer
+        a1q = start.clone()
+        st = stream_ptr()
+        ws_c.fu_pending = False
+        c_sums.zero_()
+        call('oriana_gamma_update_prep', ptr(a1q), ptr(c_a2), ptr(c_E), ptr(c_lu), ptr(c_sums[0]), ptr(c_sums[1]), None, None, None,
+             None, None, None, None, nq, K, None, None, None, st)              # E[log U] of the start (a2 = 1, as a new model)
+        for _ in range(args.iters):
+            engine.zq_gap(ws_c, c_Zi, c_Zj, c_lu, lv, phase='rows', finalize_rows=False, clear=(c_sums,))
+            prep = ws_c.prep_outputs(True) or (None, None, None)
+            with engine._span(ws_c, 'composed_update'):
+                call('oriana_gamma_update_finalize_prep', ptr(a1q), ptr(c_a2), ptr(c_E), ptr(c_lu), ptr(c_sums[0]), ptr(c_sums[1]),
+                     ptr(alpha1), ptr(alpha2), ptr(c_Zi), ptr(ws_c.FU), ptr(ws_c.R), ws_c.row_gene_splits, ws_c.row_slab_row0,
+                     ptr(ct.row_perm), ptr(sum_v), nq, K, ptr(prep[0]), ptr(prep[1]), ptr(prep[2]), st)
+            if prep[0] is not None:
+                ws_c.fu_pending, ws_c.fu_source = True, c_lu.data_ptr()
+        ws_c.timer = None
+        return a1q
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    ra, rb = fused(), composed()                                     # warm-up of every shape the timed loops use
+    torch.cuda.synchronize()
+    # (from the second iteration on the two loops evaluate the same map: the composed one starts from a2 = 1)
+    rel = float(((ra - rb).abs() / (rb.abs() + rb.abs().max(0, keepdim=True).values)).max())
+    t_f, t_c = [], []
+    for _ in range(args.reps):
+        t_f.append(timed(fused))
+        t_c.append(timed(composed))
+
+    def breakdown(fn):
+        timer = engine.KernelTimer(prealloc=8 * args.iters)
+        fn(timer)
+        torch.cuda.synchronize()
+        return {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    bf, bc = breakdown(fused), breakdown(composed)
+
+    def per_iter(ts):
+        return float(np.median(ts)) / args.iters
+
+    def outside(total_ms, bd):
+        rp = bd.get('row_pass', {'count': 0, 'mean_ms': 0.0})
+        return total_ms - rp['mean_ms'] * rp['count'] / args.iters
+
+    pf, pc = per_iter(t_f), per_iter(t_c)
+    of, oc = outside(pf, bf), outside(pc, bc)
+    out = {
+        'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
+        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps,
+        'pack_ms': round(pack_ms, 2),
+        'fused_ms_per_iter': round(pf, 4), 'composed_ms_per_iter': round(pc, 4),
+        'fused_loop_ms': [round(t, 3) for t in t_f], 'composed_loop_ms': [round(t, 3) for t in t_c],
+        'fused_outside_row_pass_ms': round(of, 4), 'composed_outside_row_pass_ms': round(oc, 4),
+        'fused_outside_share': round(of / pf, 4), 'composed_outside_share': round(oc / pc, 4),
+        'outside_fused_over_composed': round(of / oc, 4),
+        'fused_launches': bf, 'composed_launches': bc,
+        'a1_fused_vs_composed_colrel': rel,
+        'note': 'loop times: device events around the whole loop (start launch, host reads of the active counter every 5 '
+                'iterations and the clone of the start included); launches: per-launch events of one further loop',
+    }
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out, indent=1) + '\n')
+
+
+if __name__ == '__main__':
+    main()
