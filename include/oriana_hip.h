@@ -690,7 +690,11 @@ int oriana_plan_dense_splits(int64_t n, int64_t gd, int64_t cus, int64_t *gene_s
  * (dense_density > 0 and oriana_dense_supported(K); <= 0: sliced only), the column work list, the row split, the scratch of a
  * call -- built by the planning functions above for oriana_device_cus() compute units.  X: dense (n, ldx) float32 on the
  * DEVICE, or CSR on the HOST (indptr [n + 1], indices, data; expanded on the device in row chunks of at most 512 MB, so
- * neither side ever holds the dense matrix; duplicate entries add up).  The create calls synchronise the stream; the zq
+ * neither side ever holds the dense matrix).  The CSR arrays need not be canonical: the column indices of a row may come in
+ * any order, an entry whose value is 0 is no entry, and entries of one row that name the same column ADD UP (SciPy's
+ * meaning of duplicates, float32 sums; never last-writer-wins); an index outside [0, m) or a decreasing indptr is
+ * ORIANA_EINVAL before anything is launched.  Only columns [0, m) of a dense X with ldx > m are read.
+ * The create calls synchronise the stream; the zq
  * calls are asynchronous on it, take DEVICE matrices in the reference's argument order (outputs first, zero-filled by the
  * callee, 2-D C-contiguous float32) and must not run concurrently on one handle. */
 typedef struct oriana_resident oriana_resident;

@@ -311,10 +311,17 @@ class CountTiles:
         """Pack a SciPy sparse (n, m) count matrix: row chunks of the CSR form are expanded on the
         device (chunk_rows x m floats at a time), so neither host nor device ever holds the dense
         matrix (real single-cell matrices are > 90 % zeros; reference cmatrix.py:39-53 only offers
-        the dense route)."""
+        the dense route).  Any SciPy format; duplicate entries add up, explicit zeros are no entries.  The caller's
+        matrix is only read: a CSR input in canonical format (sorted indices, no duplicates) is packed from its own
+        arrays, any other CSR input from a copy -- csr_matrix() of a CSR shares its arrays and sum_duplicates() rewrites
+        them in place."""
         import scipy.sparse as sp
+        shared = sp.issparse(A) and A.format == 'csr'
         A = sp.csr_matrix(A)
-        A.sum_duplicates()
+        if not A.has_canonical_format:
+            if shared:
+                A = A.copy()
+            A.sum_duplicates()
         n, m = A.shape
         dev = torch.device(device)
         indptr = A.indptr.astype(np.int64)
