@@ -84,7 +84,7 @@ const char *oriana_version(void);
 /* ---- packing the count matrix (replaces `self.X[:].astype(np.float32)`, gap.py:94) --------
  * Two passes over dense row chunks (a chunk starts at a multiple of 256 rows):
  *   1. oriana_pack_count   -> per-tile nnz / slot counts and the slice offsets
- *   2. (caller) exclusive scans of tile_rslots, tile_cslots -> roff, coff; zero-filled rowrec, ridx
+ *   2. oriana_pack_offsets -> roff, coff and the two slot totals; (caller) zero-filled rowrec, ridx of those sizes
  *   3. oriana_pack_fill    -> rowrec / ridx (/ side_nz)
  * X is dense (rows, m) with leading dimension ldx (elements), float32 or (xdtype = 1) int64 /
  * (xdtype = 2) int32 / (xdtype = 3) float64.  rb0 = first row block of the chunk.
@@ -105,6 +105,11 @@ int oriana_pack_fill(const void *X, int xdtype, int64_t rows, int64_t m, int64_t
                       * row-side slot order */
                      const float *side, int64_t ldside, float *side_nz,
                      void *stream);
+/* Step 2, the one scan of every host (csrc/pack_nest.h, engine.py).  DEVICE: tile_rslots, tile_cslots [nt] (in; may be NULL
+ * when nt == 0), roff, coff [nt + 1] (out).  HOST: totals [2] (out) = {roff[nt], coff[nt]}, the row-side and column-side slots
+ * that size the record arrays.  SYNCHRONISES the stream. */
+int oriana_pack_offsets(int64_t *roff, int64_t *coff, const int32_t *tile_rslots, const int32_t *tile_cslots, int64_t nt,
+                        int64_t *totals, void *stream);
 
 /* ---- factor preparation ---------------------------------------------------------------------
  * From E[log U] (gamma.py:52-61 output, dense (r, K) f32) build the factor matrix
@@ -679,6 +684,13 @@ int oriana_plan_gene_order(const int64_t *col_nnz, const int64_t *bad, int64_t m
 int64_t oriana_plan_col_work_capacity(int64_t nrb, int64_t ncb, int64_t width);
 int oriana_plan_col_work(const int32_t *tile_iters, int64_t nrb, int64_t ncb, int64_t width, int64_t cus,
                          int64_t target_items, int rounds, int sum_price, int32_t *items, int64_t cap, int64_t *n_items);
+/* oriana_plan_inputs: what the two planners read of a packed layout, formed in one place for every host.  DEVICE (in):
+ * tile_rslots [nrb * ncb] as oriana_pack_count left it, cslice [nrb * ncb][17].  HOST (out, either may be NULL, its device
+ * input is then not read): gene_tile_cost [ncb], the tile_cost of oriana_row_pass_plan = mean over the row blocks of
+ * tile_rslots / 1024 (iterations of a 16-row slice) + 2.0 (staging the tile's 256 factor rows, in iterations); tile_iters
+ * [nrb * ncb], the input of oriana_plan_col_work.  SYNCHRONISES the stream. */
+int oriana_plan_inputs(const int32_t *tile_rslots, const uint32_t *cslice, int64_t nrb, int64_t ncb,
+                       double *gene_tile_cost, int32_t *tile_iters, void *stream);
 /* Splits of the dense-gene kernels of a hybrid layout: gene ranges of oriana_dense_row_pass_tail (at most two work-groups per CU)
  * and cell ranges of oriana_dense_col_pass (four per CU, a multiple of 8 cell tiles). */
 int oriana_plan_dense_splits(int64_t n, int64_t gd, int64_t cus, int64_t *gene_splits, int64_t *cell_splits);

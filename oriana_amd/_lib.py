@@ -47,6 +47,7 @@ _SIGS = {
     'oriana_version': (c_char_p, []),
     'oriana_pack_count': (c_int, [_P, c_int, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'oriana_pack_fill': (c_int, [_P, c_int, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    'oriana_pack_offsets': (c_int, [_P, _P, _P, _P, _I, _P, _P]),
     'oriana_factor_prep': (c_int, [_P, _P, _P, _P, _P, _I, _I, _P]),
     'oriana_factor_prep_pair': (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     'oriana_factor_prep_pair_clear': (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, ctypes.POINTER(OrianaClearList), _P]),
@@ -63,6 +64,7 @@ _SIGS = {
     'oriana_plan_gene_order': (c_int, [_P, _P, _I, _I, c_double, c_double, _P, _P]),
     'oriana_plan_col_work_capacity': (_I, [_I, _I, _I]),
     'oriana_plan_col_work': (c_int, [_P, _I, _I, _I, _I, _I, c_int, c_int, _P, _I, _P]),
+    'oriana_plan_inputs': (c_int, [_P, _P, _I, _I, _P, _P, _P]),
     'oriana_plan_dense_splits': (c_int, [_I, _I, _I, _P, _P]),
     'oriana_counts_create_dense_f32': (c_int, [_P, _P, _I, _I, _I, _I, c_double, _P]),
     'oriana_counts_create_csr': (c_int, [_P, _P, _P, _P, _I, _I, _I, c_double, _P]),

@@ -3,7 +3,8 @@
 //
 // Replaces `self.X[:].astype(np.float32)` (oriana/models/gap.py:94), which the reference redoes on
 // every sweep: X is constant across sweeps (gap.py:29-32), so it is converted ONCE into the layout
-// the responsibility kernels stream ("Data layout in HBM").
+// the responsibility kernels stream ("Data layout in HBM").  The counting and the filling kernel, and the scan
+// between them; the sequence that strings them together is pack_nest.h (C hosts) / CountTiles._build (engine.py).
 #include "common.h"
 
 namespace oriana {
@@ -170,6 +171,34 @@ static int launch_fill(const void *X, int64_t rows, int64_t m, int64_t ldx, int6
     return 0;
 }
 
+// exclusive scan of int32 counts into int64 offsets (off[nt] = the total), one work-group: nt is at most a few 1e5
+__global__ __launch_bounds__(1024) void k_scan_tiles(int64_t *__restrict__ off, const int32_t *__restrict__ cnt, int64_t nt) {
+    __shared__ int64_t wsum[16];
+    __shared__ int64_t carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < nt; base += 1024) {
+        const int64_t i = base + tid;
+        const int64_t v = (i < nt) ? (int64_t)cnt[i] : 0;
+        int64_t inc = v;
+        #pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int64_t t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        int64_t pre = carry_s;
+        for (int j = 0; j < w; ++j) pre += wsum[j];
+        if (i < nt) off[i] = pre + inc - v;
+        __syncthreads();
+        if (tid == 1023) carry_s = pre + inc;
+        __syncthreads();
+    }
+    if (tid == 0) off[nt] = carry_s;
+}
+
 }  // namespace oriana
 
 using namespace oriana;
@@ -210,4 +239,18 @@ extern "C" int oriana_pack_fill(const void *X, int xdtype, int64_t rows, int64_t
         default: return ORIANA_EINVAL;
     }
 #undef ORIANA_PF
+}
+
+extern "C" int oriana_pack_offsets(int64_t *roff, int64_t *coff, const int32_t *tile_rslots, const int32_t *tile_cslots, int64_t nt,
+                                   int64_t *totals, void *stream) {
+    if (nt < 0 || !roff || !coff || !totals || (nt > 0 && (!tile_rslots || !tile_cslots))) return ORIANA_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, roff, tile_rslots, nt);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, coff, tile_cslots, nt);
+    ORIANA_LAUNCH_CHECK();
+    // the one host synchronisation of every packing sequence: the slot totals size the record arrays
+    ORIANA_HIP_CHECK(hipMemcpyAsync(&totals[0], roff + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    ORIANA_HIP_CHECK(hipMemcpyAsync(&totals[1], coff + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    ORIANA_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
 }

@@ -7,7 +7,7 @@
 // CPU against a NumPy restatement), engine.py calls them, and oriana_counts_create_* / oriana_zq_*_resident keep a count
 // matrix packed across calls for a non-Python host: the reference calls its loop nest once per step() with the same X
 // (oriana/models/gap.py:89-94).
-#include "zq_nest.h"
+#include "pack_nest.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -89,34 +89,6 @@ __global__ __launch_bounds__(256) void k_gather_nz(oriana_counts cm, const float
             w_nz[rbase + slot] = w;
         }
     }
-}
-
-__global__ __launch_bounds__(1024) void k_scan_i32(int64_t *__restrict__ off, const int32_t *__restrict__ cnt, int64_t nt) {
-    // (the scan of stateless.hip: one work-group, nt is at most a few 1e5)
-    __shared__ int64_t wsum[16];
-    __shared__ int64_t carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nt; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t v = (i < nt) ? (int64_t)cnt[i] : 0;
-        int64_t inc = v;
-        #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int64_t pre = carry_s;
-        for (int j = 0; j < w; ++j) pre += wsum[j];
-        if (i < nt) off[i] = pre + inc - v;
-        __syncthreads();
-        if (tid == 1023) carry_s = pre + inc;
-        __syncthreads();
-    }
-    if (tid == 0) off[nt] = carry_s;
 }
 
 }  // namespace oriana
@@ -279,6 +251,32 @@ extern "C" int oriana_plan_col_work(const int32_t *tile_iters, int64_t nrb, int6
     return 0;
 }
 
+// The planners' inputs from a layout's device tables (include/oriana_hip.h).  gene_tile_cost: the mean iterations of a 16-row slice
+// (16 slices of 64 slots) + 2.0 for staging the tile's 256 factor rows, in iterations (flat between 0.5 and 4, DESIGN_HISTORY.md 10 l).
+extern "C" int oriana_plan_inputs(const int32_t *tile_rslots, const uint32_t *cslice, int64_t nrb, int64_t ncb,
+                                  double *gene_tile_cost, int32_t *tile_iters, void *stream) {
+    if (nrb < 0 || ncb < 0 || (gene_tile_cost && !tile_rslots) || (tile_iters && !cslice)) return ORIANA_EINVAL;
+    const int64_t nt = nrb * ncb;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> rslots((size_t)(gene_tile_cost ? nt : 0));
+    struct Scratch { int32_t *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } longest;
+    if (!rslots.empty())
+        ORIANA_HIP_CHECK(hipMemcpyAsync(rslots.data(), tile_rslots, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, s));
+    if (tile_iters && nt > 0) {
+        if (hipMalloc((void **)&longest.p, sizeof(int32_t) * nt) != hipSuccess) { (void)hipGetLastError(); return -1000 - (int)hipErrorOutOfMemory; }
+        hipLaunchKernelGGL(k_tile_longest, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, longest.p, cslice, nt);
+        ORIANA_LAUNCH_CHECK();
+        ORIANA_HIP_CHECK(hipMemcpyAsync(tile_iters, longest.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, s));
+    }
+    ORIANA_HIP_CHECK(hipStreamSynchronize(s));
+    for (int64_t c = 0; gene_tile_cost && nt > 0 && c < ncb; ++c) {
+        double sum = 0.0;
+        for (int64_t rb = 0; rb < nrb; ++rb) sum += (double)rslots[(size_t)(rb * ncb + c)];
+        gene_tile_cost[c] = sum / (double)nrb / (16.0 * 64.0) + 2.0;
+    }
+    return 0;
+}
+
 // splits of the dense-gene kernels of a hybrid layout: gene ranges of the row kernel (two work-groups per CU at most) and
 // cell ranges of the gene-side kernel (four per CU, a multiple of 8 cell tiles)
 extern "C" int oriana_plan_dense_splits(int64_t n, int64_t gd, int64_t cus, int64_t *gene_splits, int64_t *cell_splits) {
@@ -433,95 +431,57 @@ int resident_build(oriana_resident *h, ChunkSource &src, double dense_density, h
     ORIANA_TRY(dev_alloc(h, &h->cslice, nt1 * 17, true, s));
     ORIANA_TRY(dev_alloc(h, &h->roff, nt1 + 1, true, s));
     ORIANA_TRY(dev_alloc(h, &h->coff, nt1 + 1, true, s));
+    // ---- 3. records and, beside them, the dense block: the packing sequence of pack_nest.h over chunks in the packed gene order
+    const int64_t nct = h->nrb * 8, ngt = gd / 32;
+    if (gd > 0) ORIANA_TRY(dev_alloc(h, &h->dense_x, (size_t)(nct * ngt * 1024), true, s));
     float *perm_buf = nullptr;
     ORIANA_TRY(tmp_alloc((void **)&perm_buf, sizeof(float) * chunk * m));
-    auto permuted = [&](int64_t r0, int64_t rows) -> int {
+    auto permuted = [&](int64_t r0, int64_t rows, bool fill, const float **out, int64_t *ld_out) -> int {
         const float *Xc; int64_t ld;
         ORIANA_TRY(src.get(r0, rows, &Xc, &ld, s));
         hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)((m + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, s, perm_buf, Xc,
                            h->col_perm, rows, m, ld);
         ORIANA_LAUNCH_CHECK();
+        if (fill && gd > 0) ORIANA_TRY(oriana_dense_pack(perm_buf, 0, rows, gd, m, r0 / 32, h->dense_x, s));
+        *out = perm_buf + gd; *ld_out = m;
         return 0;
     };
-    if (h->ms > 0) {
-        for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-            const int64_t rows = std::min(n, r0 + chunk) - r0;
-            ORIANA_TRY(permuted(r0, rows));
-            ORIANA_TRY(oriana_pack_count(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->tile_nnz, h->tile_rslots, h->tile_cslots,
-                                      h->rslice, h->cslice, s));
-        }
-        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, h->roff, h->tile_rslots, h->nt);
-        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, h->coff, h->tile_cslots, h->nt);
-        ORIANA_LAUNCH_CHECK();
-    }
-    int64_t tot[2] = {0, 0};
-    std::vector<int32_t> tile_rslots_h((size_t)nt1, 0), tile_nnz_h((size_t)nt1, 0);
-    if (h->nt > 0) {
-        ORIANA_HIP_CHECK(hipMemcpyAsync(&tot[0], h->roff + h->nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        ORIANA_HIP_CHECK(hipMemcpyAsync(&tot[1], h->coff + h->nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        ORIANA_HIP_CHECK(hipMemcpyAsync(tile_rslots_h.data(), h->tile_rslots, sizeof(int32_t) * h->nt, hipMemcpyDeviceToHost, s));
-        ORIANA_HIP_CHECK(hipMemcpyAsync(tile_nnz_h.data(), h->tile_nnz, sizeof(int32_t) * h->nt, hipMemcpyDeviceToHost, s));
-    }
-    ORIANA_HIP_CHECK(hipStreamSynchronize(s));
-    h->rslots = tot[0]; h->cslots = tot[1];
-    int64_t nnz_sparse = 0;
-    for (int64_t t = 0; t < h->nt; ++t) nnz_sparse += tile_nnz_h[(size_t)t];
-    // ---- 3. records (padding slots: x == 0, row index 0), the dense block
-    ORIANA_TRY(dev_alloc(h, &h->rowrec, (size_t)std::max<int64_t>(h->rslots, 1), true, s));
-    ORIANA_TRY(dev_alloc(h, &h->ridx, (size_t)std::max<int64_t>(h->cslots, 1), true, s));
-    const int64_t nct = h->nrb * 8, ngt = gd / 32;
-    if (gd > 0) ORIANA_TRY(dev_alloc(h, &h->dense_x, (size_t)(nct * ngt * 1024), true, s));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int64_t rows = std::min(n, r0 + chunk) - r0;
-        ORIANA_TRY(permuted(r0, rows));
-        if (gd > 0) ORIANA_TRY(oriana_dense_pack(perm_buf, 0, rows, gd, m, r0 / 32, h->dense_x, s));
-        if (h->ms > 0)
-            ORIANA_TRY(oriana_pack_fill(perm_buf + gd, 0, rows, h->ms, m, r0 / TILE, h->ncb, h->roff, h->coff, h->rslice, h->cslice, h->rowrec,
-                                     h->ridx, nullptr, 0, nullptr, s));
-    }
-    int64_t nnz_dense = 0;
-    for (int64_t p = 0; p < gd; ++p) nnz_dense += col_nnz[(size_t)order[(size_t)p]];
-    h->nnz = nnz_sparse + nnz_dense;
+    auto place = [&](int64_t rslots, int64_t cslots, oriana_rowrec **rowrec, uint8_t **ridx, float **) -> int {
+        h->rslots = rslots; h->cslots = cslots;
+        ORIANA_TRY(dev_alloc(h, &h->rowrec, (size_t)std::max<int64_t>(rslots, 1), true, s));
+        ORIANA_TRY(dev_alloc(h, &h->ridx, (size_t)std::max<int64_t>(cslots, 1), true, s));
+        *rowrec = h->rowrec; *ridx = h->ridx;
+        return 0;
+    };
+    const PackTables t{h->tile_nnz, h->tile_rslots, h->tile_cslots, h->roff, h->coff, h->rslice, h->cslice};
     oriana_counts &cm = h->cm;
-    cm.n = n; cm.m = h->ms; cm.nrb = h->nrb; cm.ncb = h->ncb; cm.nnz = nnz_sparse; cm.rslots = h->rslots; cm.cslots = h->cslots;
-    cm.roff = h->roff; cm.coff = h->coff; cm.rslice = h->rslice; cm.cslice = h->cslice; cm.rowrec = h->rowrec; cm.ridx = h->ridx;
-    cm.col_perm = h->col_perm + gd; cm.row_perm = nullptr;
+    int64_t nnz_dense = 0;                                   // (the per-gene counts of step 1 are counts of the same float32 values)
+    for (int64_t p = 0; p < m; ++p) h->nnz += col_nnz[(size_t)p];
+    for (int64_t p = 0; p < gd; ++p) nnz_dense += col_nnz[(size_t)order[(size_t)p]];
+    ORIANA_TRY(pack_sliced(&cm, n, h->ms, chunk, t, h->col_perm + gd, nullptr, 0, h->nnz - nnz_dense, permuted, place, s));
     h->dn.n = n; h->dn.gd = gd; h->dn.nct = nct; h->dn.x = h->dense_x;
     // ---- 4. plans: row split (equal-cost gene ranges), column work list, dense-gene splits
     h->split.nfull = (int32_t)h->nrb; h->split.parts = 1; h->split.edge[0] = 0; h->split.edge[1] = (int32_t)h->ncb;
     if (h->nt > 0) {
         std::vector<double> tile_cost((size_t)h->ncb, 0.0);
-        for (int64_t c = 0; c < h->ncb; ++c) {
-            double sum = 0.0;
-            for (int64_t rb = 0; rb < h->nrb; ++rb) sum += (double)tile_rslots_h[(size_t)(rb * h->ncb + c)];
-            tile_cost[(size_t)c] = sum / (double)h->nrb / (16.0 * 64.0) + 2.0;
-        }
-        ORIANA_TRY(oriana_row_pass_plan_cus(&cm, K, tile_cost.data(), h->cus, &h->split));
-        int32_t *d_longest = nullptr;
-        ORIANA_TRY(tmp_alloc((void **)&d_longest, sizeof(int32_t) * h->nt));
-        hipLaunchKernelGGL(k_tile_longest, dim3((unsigned)((h->nt + 255) / 256)), dim3(256), 0, s, d_longest, h->cslice, h->nt);
-        ORIANA_LAUNCH_CHECK();
         std::vector<int32_t> longest((size_t)h->nt);
-        ORIANA_HIP_CHECK(hipMemcpyAsync(longest.data(), d_longest, sizeof(int32_t) * h->nt, hipMemcpyDeviceToHost, s));
-        ORIANA_HIP_CHECK(hipStreamSynchronize(s));
+        ORIANA_TRY(oriana_plan_inputs(h->tile_rslots, h->cslice, h->nrb, h->ncb, tile_cost.data(), longest.data(), s));
+        ORIANA_TRY(oriana_row_pass_plan_cus(&cm, K, tile_cost.data(), h->cus, &h->split));
         const int64_t width = std::max<int64_t>(oriana_col_block_tiles(K), 1);
-        const int64_t cap = oriana_plan_col_work_capacity(h->nrb, h->ncb, width);
-        std::vector<int32_t> items((size_t)cap * 3);
-        if (h->cslots > 0) {
-            ORIANA_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, width, h->cus, 0, 1, 0, items.data(), cap, &h->n_col_work));
-            ORIANA_TRY(dev_alloc(h, &h->col_work, (size_t)std::max<int64_t>(h->n_col_work * 3, 1), false, s));
-            ORIANA_HIP_CHECK(hipMemcpyAsync(h->col_work, items.data(), sizeof(int32_t) * h->n_col_work * 3, hipMemcpyHostToDevice, s));
+        auto col_work = [&](int64_t w, int32_t **list, int64_t *count) -> int {
+            const int64_t cap = oriana_plan_col_work_capacity(h->nrb, h->ncb, w);
+            std::vector<int32_t> items((size_t)cap * 3);
+            ORIANA_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, w, h->cus, 0, 1, 0, items.data(), cap, count));
+            ORIANA_TRY(dev_alloc(h, list, (size_t)std::max<int64_t>(*count * 3, 1), false, s));
+            ORIANA_HIP_CHECK(hipMemcpyAsync(*list, items.data(), sizeof(int32_t) * *count * 3, hipMemcpyHostToDevice, s));
             ORIANA_HIP_CHECK(hipStreamSynchronize(s));
+            return 0;
+        };
+        if (h->cslots > 0) {
+            ORIANA_TRY(col_work(width, &h->col_work, &h->n_col_work));
             // the dual column pass of the sparse nests (two factor images per tile: one column tile per item)
             if (width == 1) { h->col_work1 = h->col_work; h->n_col_work1 = h->n_col_work; }
-            else {
-                const int64_t cap1 = oriana_plan_col_work_capacity(h->nrb, h->ncb, 1);
-                std::vector<int32_t> items1((size_t)cap1 * 3);
-                ORIANA_TRY(oriana_plan_col_work(longest.data(), h->nrb, h->ncb, 1, h->cus, 0, 1, 0, items1.data(), cap1, &h->n_col_work1));
-                ORIANA_TRY(dev_alloc(h, &h->col_work1, (size_t)std::max<int64_t>(h->n_col_work1 * 3, 1), false, s));
-                ORIANA_HIP_CHECK(hipMemcpyAsync(h->col_work1, items1.data(), sizeof(int32_t) * h->n_col_work1 * 3, hipMemcpyHostToDevice, s));
-                ORIANA_HIP_CHECK(hipStreamSynchronize(s));
-            }
+            else ORIANA_TRY(col_work(1, &h->col_work1, &h->n_col_work1));
         }
     }
     if (gd > 0) ORIANA_TRY(oriana_plan_dense_splits(n, gd, h->cus, &h->dn_gene_splits, &h->dn_cell_splits));

@@ -2,37 +2,9 @@
 // after, dense float32 matrices, callee zero-fills, gap.py:67-80 and twins).  X is repacked on
 // every call, as the reference re-casts X on every call (gap.py:94); the model classes keep the
 // packed layout resident instead and call the passes directly.
-#include "zq_nest.h"
+#include "pack_nest.h"
 
 namespace oriana {
-
-// exclusive scan of int32 counts into int64 offsets, one workgroup (ntiles is at most a few 1e5)
-__global__ __launch_bounds__(1024) void k_scan_tiles(int64_t *__restrict__ off, const int32_t *__restrict__ cnt, int64_t nt) {
-    __shared__ int64_t wsum[16];
-    __shared__ int64_t carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < nt; base += 1024) {
-        const int64_t i = base + tid;
-        const int64_t v = (i < nt) ? (int64_t)cnt[i] : 0;
-        int64_t inc = v;
-        #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[w] = inc;
-        __syncthreads();
-        int64_t pre = carry_s;
-        for (int j = 0; j < w; ++j) pre += wsum[j];
-        if (i < nt) off[i] = pre + inc - v;
-        __syncthreads();
-        if (tid == 1023) carry_s = pre + inc;
-        __syncthreads();
-    }
-    if (tid == 0) off[nt] = carry_s;
-}
 
 struct WsLayout {
     int64_t nt, Kp;
@@ -118,62 +90,48 @@ static int zq_dense(float *Zi, float *Zj, float *Zlog, const float *log_U_hat, c
     if (n == 0 || m == 0) return 0;
     if (!X || !ws || ((uintptr_t)ws & 255)) return ORIANA_EINVAL;
     const bool sparse = S_hat != nullptr, weighted = D_hat != nullptr;
-    const int64_t nrb = (n + TILE - 1) / TILE, ncb = (m + TILE - 1) / TILE, nt = nrb * ncb;
     // fixed-size part first: counts, offsets, slice tables
     const WsLayout L0 = ws_layout(n, m, K, 0, 0);
     if ((size_t)ws_bytes < L0.total) return ORIANA_EINVAL;
     char *b = (char *)ws;
-    int32_t *tile_nnz = (int32_t *)(b + L0.tile_nnz), *tile_rslots = (int32_t *)(b + L0.tile_rslots);
-    int32_t *tile_cslots = (int32_t *)(b + L0.tile_cslots), *tile_flag = (int32_t *)(b + L0.tile_flag);
-    int64_t *roff = (int64_t *)(b + L0.roff), *coff = (int64_t *)(b + L0.coff);
-    uint32_t *rslice = (uint32_t *)(b + L0.rslice), *cslice = (uint32_t *)(b + L0.cslice);
-
-    int rc = oriana_pack_count(X, 0, n, m, m, 0, ncb, tile_nnz, tile_rslots, tile_cslots, rslice, cslice, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, roff, tile_rslots, nt);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, coff, tile_cslots, nt);
-    ORIANA_LAUNCH_CHECK();
-    // the one host synchronisation of this entry point: the slot totals size the record arrays
-    int64_t tot[2] = {0, 0};
-    ORIANA_HIP_CHECK(hipMemcpyAsync(&tot[0], roff + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    ORIANA_HIP_CHECK(hipMemcpyAsync(&tot[1], coff + nt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    ORIANA_HIP_CHECK(hipStreamSynchronize(s));
-    const WsLayout L = ws_layout(n, m, K, tot[0], tot[1]);
-    if (L.total > (size_t)ws_bytes) return ORIANA_EINVAL;
-    const int64_t rs1 = tot[0] > 0 ? tot[0] : 1, cs1 = tot[1] > 0 ? tot[1] : 1;
-    oriana_rowrec *rowrec = (oriana_rowrec *)(b + L.rowrec);
-    uint8_t *ridx = (uint8_t *)(b + L.ridx);
-    float *s_cs = (float *)(b + L.s_cs);
-    float *w_nz = weighted ? (float *)(b + L.w_nz) : nullptr;
-    float *sw_cs = weighted ? (float *)(b + L.sw_cs) : nullptr;
-    float *s_rs = sparse ? (float *)(b + L.s_rs) : nullptr;
-    // padding slots: x == 0 records, row index 0, s == 0
-    ORIANA_HIP_CHECK(hipMemsetAsync(rowrec, 0, sizeof(oriana_rowrec) * rs1, s));
-    ORIANA_HIP_CHECK(hipMemsetAsync(ridx, 0, cs1, s));
-    ORIANA_HIP_CHECK(hipMemsetAsync(s_cs, 0, sizeof(float) * cs1, s));
-    if (weighted) {
-        ORIANA_HIP_CHECK(hipMemsetAsync(w_nz, 0, sizeof(float) * rs1, s));
-        ORIANA_HIP_CHECK(hipMemsetAsync(sw_cs, 0, sizeof(float) * cs1, s));
-    }
-    if (sparse) ORIANA_HIP_CHECK(hipMemsetAsync(s_rs, 0, sizeof(float) * rs1, s));
-    rc = oriana_pack_fill(X, 0, n, m, m, 0, ncb, roff, coff, rslice, cslice, rowrec, ridx, D_hat, m, w_nz, stream);
-    if (rc) return rc;
+    const PackTables t{(int32_t *)(b + L0.tile_nnz), (int32_t *)(b + L0.tile_rslots), (int32_t *)(b + L0.tile_cslots), (int64_t *)(b + L0.roff),
+                       (int64_t *)(b + L0.coff), (uint32_t *)(b + L0.rslice), (uint32_t *)(b + L0.cslice)};
+    // X packed as one chunk in the caller's gene order; the slot totals place the record arrays and what follows them in the workspace
+    WsLayout L = L0;
+    ZqView v;
+    auto chunk = [&](int64_t, int64_t, bool, const float **Xc, int64_t *ld) -> int { *Xc = X; *ld = m; return 0; };
+    auto place = [&](int64_t rslots, int64_t cslots, oriana_rowrec **rowrec, uint8_t **ridx, float **side_nz) -> int {
+        L = ws_layout(n, m, K, rslots, cslots);
+        if (L.total > (size_t)ws_bytes) return ORIANA_EINVAL;
+        const int64_t rs1 = rslots > 0 ? rslots : 1, cs1 = cslots > 0 ? cslots : 1;
+        *rowrec = (oriana_rowrec *)(b + L.rowrec); *ridx = (uint8_t *)(b + L.ridx);
+        v.s_cs = (float *)(b + L.s_cs);
+        // padding slots: x == 0 records, row index 0, s == 0
+        ORIANA_HIP_CHECK(hipMemsetAsync(*rowrec, 0, sizeof(oriana_rowrec) * rs1, s));
+        ORIANA_HIP_CHECK(hipMemsetAsync(*ridx, 0, cs1, s));
+        ORIANA_HIP_CHECK(hipMemsetAsync(v.s_cs, 0, sizeof(float) * cs1, s));
+        if (weighted) {
+            v.w_nz = *side_nz = (float *)(b + L.w_nz); v.sw_cs = (float *)(b + L.sw_cs);
+            ORIANA_HIP_CHECK(hipMemsetAsync(*side_nz, 0, sizeof(float) * rs1, s));
+            ORIANA_HIP_CHECK(hipMemsetAsync(v.sw_cs, 0, sizeof(float) * cs1, s));
+        }
+        if (sparse) {
+            v.s_rs = (float *)(b + L.s_rs);
+            ORIANA_HIP_CHECK(hipMemsetAsync(v.s_rs, 0, sizeof(float) * rs1, s));
+        }
+        return 0;
+    };
     oriana_counts cm;
-    cm.n = n; cm.m = m; cm.nrb = nrb; cm.ncb = ncb; cm.nnz = 1;   /* >0: lets oriana_fixup look at the flags */
-    cm.rslots = tot[0]; cm.cslots = tot[1];
-    cm.roff = roff; cm.coff = coff; cm.rslice = rslice; cm.cslice = cslice; cm.rowrec = rowrec; cm.ridx = ridx;
-    cm.col_perm = nullptr; cm.row_perm = nullptr;
+    ORIANA_TRY(pack_sliced(&cm, n, m, n, t, nullptr, D_hat, m, 1, chunk, place, s));
     // the nest over the workspace: no dense block, no split, no work lists, no two-image kernels, the fixed den threshold;
     // the outputs are zeroed above, C / tile_flag / C2 by the preparation's clear list
-    ZqView v;
     v.cm = &cm; v.n = n; v.m = m; v.K = K; v.Kp = L.Kp;
     v.FU = (float *)(b + L.FU); v.FV = (float *)(b + L.FV); v.R = (float *)(b + L.R); v.C = (float *)(b + L.C);
-    v.s_cs = s_cs; v.prep = (float *)(b + L.prep); v.tile_flag = tile_flag;
+    v.prep = (float *)(b + L.prep); v.tile_flag = (int32_t *)(b + L0.tile_flag);
     v.F2 = (float *)(b + L.F2); v.G2 = v.GQ = (float *)(b + L.G2); v.C2 = (float *)(b + L.C2);
-    v.w_nz = w_nz; v.sw_cs = sw_cs; v.s_rs = s_rs;
     if (quirk) {
         v.dq = (float *)(b + L.dq);
-        if ((rc = oriana_take_cols_f32(v.dq, D_hat, n, m, K, stream))) return rc;
+        ORIANA_TRY(oriana_take_cols_f32(v.dq, D_hat, n, m, K, stream));
     }
     ORIANA_HIP_CHECK(hipMemsetAsync(v.prep, 0, 8 * sizeof(float), s));            // the arrival counter
     return zq_run(v, Zi, Zj, Zlog, log_U_hat, log_V_hat, S_tilde, S_hat, nullptr, stream);

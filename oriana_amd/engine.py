@@ -67,14 +67,6 @@ class CountTiles:
         self._struct = None
 
     # ---- building -------------------------------------------------------------------------
-    def set_col_order(self, col_nnz):
-        """Pack genes in decreasing order of their non-zero count (`col_nnz`: int64 [m], already
-        summed over all row shards): tiles then hold columns of similar density, which shortens
-        the padding of the slices.  Internal only -- every dense input / output of the API stays
-        in the caller's gene order."""
-        order, _ = self.dense_order(col_nnz, 0, None, 0.0)
-        self.col_perm = order.to(self.device).to(torch.int32).contiguous()
-
     @staticmethod
     def dense_order(col_nnz, n_total, bad, density, min_share=0.0):
         """(gene order, gd) of a hybrid layout: genes whose share of non-zero cells is >= `density` and whose counts
@@ -129,11 +121,11 @@ class CountTiles:
         i64 = dict(dtype=torch.int64, device=self.device)
         self.roff = torch.zeros(nt + 1, **i64)
         self.coff = torch.zeros(nt + 1, **i64)
-        if nt:
-            self.roff[1:] = torch.cumsum(self.tile_rslots[:nt].to(torch.int64), dim=0)
-            self.coff[1:] = torch.cumsum(self.tile_cslots[:nt].to(torch.int64), dim=0)
-        tot = torch.stack([self.roff[-1], self.coff[-1], self.tile_nnz[:max(nt, 1)].to(torch.int64).sum()]).tolist()
-        self.rslots, self.cslots, self.nnz_sparse = int(tot[0]), int(tot[1]), int(tot[2]) if nt else 0
+        nnz = self.tile_nnz[:nt].sum()
+        tot = np.zeros(2, dtype=np.int64)           # (the scan of every host, csrc/pack.hip: it synchronises)
+        call('oriana_pack_offsets', ptr(self.roff), ptr(self.coff), ptr(self.tile_rslots), ptr(self.tile_cslots), nt,
+             tot.ctypes.data, stream_ptr())
+        self.rslots, self.cslots, self.nnz_sparse = int(tot[0]), int(tot[1]), int(nnz.item())
         self.nnz = self.nnz_sparse
         # padding slots are recognised by x == 0 / read row index 0: zero-fill before the fill pass
         self.rowrec = torch.zeros(max(self.rslots, 1), **i64)                                   # 8-byte records
@@ -170,9 +162,8 @@ class CountTiles:
         nt = self.nrb * self.ncb
         if nt == 0 or self.cslots == 0:
             return None
-        cs = self.cslice[:nt * 17].view(nt, 17).to(torch.int64)
-        nit = ((cs[:, 1:] - cs[:, :-1]) // 64).max(dim=1).values                     # longest slice per tile
-        nit = np.ascontiguousarray(nit.cpu().numpy().astype(np.int32))
+        nit = np.empty(nt, dtype=np.int32)                                           # longest slice per tile
+        call('oriana_plan_inputs', None, ptr(self.cslice), self.nrb, self.ncb, None, nit.ctypes.data, stream_ptr())
         lib = _lib.load()
         cap = int(lib.oriana_plan_col_work_capacity(self.nrb, self.ncb, int(width)))
         items = np.empty((max(cap, 1), 3), dtype=np.int32)
@@ -194,13 +185,11 @@ class CountTiles:
 
     def finish(self):
         self._col_work = {}
-        # relative cost of the gene tiles on the row side (mean iterations of a 16-row slice + the staging of the tile's factor
-        # rows, in iterations): where the row pass cuts gene ranges (oriana_row_pass_plan)
+        # relative cost of the gene tiles on the row side (oriana_plan_inputs): where the row pass cuts gene ranges (oriana_row_pass_plan)
         self.gene_tile_cost = None
         if self.tile_rslots is not None and self.nrb * self.ncb > 0:
-            per = self.tile_rslots[:self.nrb * self.ncb].view(self.nrb, self.ncb).to(torch.float64).mean(dim=0) / (16 * 64)
-            stage = 2.0                      # (staging a tile's 256 factor rows, in slice iterations: flat between 0.5 and 4, DESIGN_HISTORY.md 10 l)
-            self.gene_tile_cost = np.ascontiguousarray((per + stage).cpu().numpy(), dtype=np.float64)
+            self.gene_tile_cost = np.empty(self.ncb, dtype=np.float64)
+            call('oriana_plan_inputs', ptr(self.tile_rslots), None, self.nrb, self.ncb, self.gene_tile_cost.ctypes.data, None, stream_ptr())
         self.tile_rslots = self.tile_cslots = None
         if self.gd and self.col_perm is None:
             raise _lib.OrianaHipError('a hybrid layout needs an explicit gene order')
@@ -244,42 +233,50 @@ class CountTiles:
         return cn, order, gd
 
     @classmethod
-    def from_dense(cls, X, device='cuda', chunk_bytes=1 << 30, side=None, sort_cols=True, reduce_fn=None,
-                   sort_rows=False, dense_density=None, n_total=None, dense_min_share=0.0):
-        """Pack a dense (n, m) matrix (NumPy or torch, host or device).  `side`: optional dense
-        (n, m) float32 DEVICE matrix gathered at the non-zeros (returned as .side_nz, row-side
-        slots).  `reduce_fn`: sums the per-gene counts over row shards (all-reduce) so that every
-        rank packs the genes in the same order.  `dense_density`: build a HYBRID layout -- genes expressed in at
-        least this share of the cells (of all shards: `n_total`) go to a dense block evaluated on the matrix cores
-        (csrc/dense_pass.hip; pCMF only, K with oriana_dense_supported)."""
-        n, m = X.shape
-        dev = torch.device(device)
+    def _build(cls, n, m, chunk_fn, chunk_rows, device, side=None, sort_cols=True, reduce_fn=None, sort_rows=False,
+               dense_density=None, n_total=None, dense_min_share=0.0):
+        """THE packing sequence of the Python host (csrc/pack_nest.h is its C twin) over `chunk_fn(r0, r1) -> dense device
+        tensor`: per-gene statistics -> gene order, dense set -> counting pass (learns the cell order of sort_rows) -> offsets
+        -> fill pass (replays it; gathers `side`; packs the dense block, which refuses a side matrix) -> plans."""
         if n == 0 or m == 0:
             self = cls(n, m, device)
             self.finish_count()
             return self.finish()
-        rows = max(TILE, (chunk_bytes // max(1, m * 8)) // TILE * TILE)
+        dev = torch.device(device)
+        chunks = [(r0, min(n, r0 + chunk_rows)) for r0 in range(0, n, chunk_rows)]
         gd, order = 0, None
         if sort_cols or dense_density:
-            cn, order, gd = cls._gene_stats(lambda: (_as_device_chunk(X, r0, min(n, r0 + rows), dev) for r0 in range(0, n, rows)),
-                                            m, dev, reduce_fn, dense_density if side is None else None, n_total, dense_min_share)
+            cn, order, gd = cls._gene_stats(lambda: (chunk_fn(r0, r1) for r0, r1 in chunks), m, dev, reduce_fn, dense_density, n_total, dense_min_share)
+            if order is None:
+                # decreasing non-zero count (over all row shards): tiles of similar density, shorter padding.  Internal only: the API keeps the caller's order
+                order, _ = cls.dense_order(cn, 0, None, 0.0)
         self = cls(n, m, device, gd=gd)
         self.dense_density = dense_density if gd else None
         self.sort_rows = bool(sort_rows)
         if order is not None:
             self.col_perm = order.to(torch.int32).contiguous()
-        elif sort_cols:
-            self.set_col_order(cn)
-        for r0 in range(0, n, rows):
-            self.count_chunk(_as_device_chunk(X, r0, min(n, r0 + rows), self.device), r0)
+        for r0, r1 in chunks:
+            self.count_chunk(chunk_fn(r0, r1), r0)
         self.finish_count()
         if side is not None:
             self.side_nz = torch.zeros(max(self.rslots, 1), dtype=torch.float32, device=self.device)
-        for r0 in range(0, n, rows):
-            r1 = min(n, r0 + rows)
-            self.fill_chunk(_as_device_chunk(X, r0, r1, self.device), r0,
-                            side[r0:r1] if side is not None else None, self.side_nz)
+        for r0, r1 in chunks:
+            self.fill_chunk(chunk_fn(r0, r1), r0, side[r0:r1] if side is not None else None, self.side_nz)
         return self.finish()
+
+    @classmethod
+    def from_dense(cls, X, device='cuda', chunk_bytes=1 << 30, side=None, sort_cols=True, reduce_fn=None,
+                   sort_rows=False, dense_density=None, n_total=None, dense_min_share=0.0):
+        """Pack a dense (n, m) matrix (NumPy or torch, host or device).  `side`: optional dense
+        (n, m) float32 DEVICE matrix gathered at the non-zeros (returned as .side_nz, row-side
+        slots; dense_density is then ignored).  `reduce_fn`: sums the per-gene counts over row shards (all-reduce) so that every
+        rank packs the genes in the same order.  `dense_density`: build a HYBRID layout -- genes expressed in at
+        least this share of the cells (of all shards: `n_total`) go to a dense block evaluated on the matrix cores
+        (csrc/dense_pass.hip; pCMF only, K with oriana_dense_supported)."""
+        n, m = X.shape
+        dev = torch.device(device)
+        return cls._build(n, m, lambda r0, r1: _as_device_chunk(X, r0, r1, dev), max(TILE, (chunk_bytes // max(1, m * 8)) // TILE * TILE), device,
+                          side, sort_cols, reduce_fn, sort_rows, dense_density if side is None else None, n_total, dense_min_share)
 
     @classmethod
     def from_chunks(cls, n, m, chunk_fn, chunk_rows, device='cuda', sort_cols=True, reduce_fn=None, sort_rows=False,
@@ -287,23 +284,7 @@ class CountTiles:
         """Passes over `chunk_fn(r0, r1) -> dense device tensor` (deterministic generator):
         per-gene counts (when sort_cols), tile counts, fill.  `dense_density`, `n_total`: as from_dense."""
         assert chunk_rows % TILE == 0
-        gd, order = 0, None
-        if (sort_cols or dense_density) and n > 0 and m > 0:
-            cn, order, gd = cls._gene_stats(lambda: (chunk_fn(r0, min(n, r0 + chunk_rows)) for r0 in range(0, n, chunk_rows)),
-                                            m, torch.device(device), reduce_fn, dense_density, n_total, dense_min_share)
-        self = cls(n, m, device, gd=gd)
-        self.dense_density = dense_density if gd else None
-        self.sort_rows = bool(sort_rows)
-        if order is not None:
-            self.col_perm = order.to(torch.int32).contiguous()
-        elif sort_cols and n > 0 and m > 0:
-            self.set_col_order(cn)
-        for r0 in range(0, n, chunk_rows):
-            self.count_chunk(chunk_fn(r0, min(n, r0 + chunk_rows)).contiguous(), r0)
-        self.finish_count()
-        for r0 in range(0, n, chunk_rows):
-            self.fill_chunk(chunk_fn(r0, min(n, r0 + chunk_rows)).contiguous(), r0)
-        return self.finish()
+        return cls._build(n, m, chunk_fn, chunk_rows, device, None, sort_cols, reduce_fn, sort_rows, dense_density, n_total, dense_min_share)
 
     @classmethod
     def from_scipy(cls, A, device='cuda', chunk_rows=8192, sort_cols=True, reduce_fn=None, dense_density=None, n_total=None,
@@ -336,12 +317,8 @@ class CountTiles:
                 vals = torch.from_numpy(np.asarray(A.data[lo:hi], dtype=np.float32)).to(dev)
                 out[rows, cols] = vals
             return out
-        if n == 0 or m == 0:
-            self = cls(n, m, dev)
-            self.finish_count()
-            return self.finish()
-        return cls.from_chunks(n, m, chunk_fn, max(TILE, chunk_rows // TILE * TILE), dev, sort_cols=sort_cols,
-                               reduce_fn=reduce_fn, dense_density=dense_density, n_total=n_total, dense_min_share=dense_min_share)
+        return cls._build(n, m, chunk_fn, max(TILE, chunk_rows // TILE * TILE), dev, None, sort_cols, reduce_fn, False, dense_density, n_total,
+                          dense_min_share)
 
     @property
     def c_struct(self):

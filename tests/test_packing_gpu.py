@@ -3,7 +3,8 @@
 include/oriana_hip.h and DESIGN.md section 3): the chunked route of CountTiles.from_dense (row chunks past the first: rb0,
 the dense block's first cell tile, the per-chunk cell order, the side matrix), SciPy inputs in every format (and that they are
 only read), the second grid launch of the packers (more than 65535 row blocks in one chunk) and the two untested shapes of
-the resident C handle (ldx > m; CSR that is not canonical).  Everything is exact but the comparisons with the oracle's
+the resident C handle (ldx > m; CSR that is not canonical); the steps every host shares (oriana_pack_offsets,
+oriana_plan_inputs) against NumPy and from_chunks against from_dense (one builder).  Everything is exact but the comparisons with the oracle's
 loop nest, which use helpers.RTOL.  GPU only."""
 import ctypes
 
@@ -452,3 +453,116 @@ def test_resident_csr_that_is_not_canonical(lib, form, dd):
     assert err_colrel(res[1][1], res[0][1]) < helpers.RTOL and err_colrel(res[1][2], res[0][2]) < helpers.RTOL
     for info, Zi, Zj in res:
         assert err_colrel(Zi, rZi) < helpers.RTOL and err_colrel(Zj, rZj) < helpers.RTOL
+
+
+# ---- E. the steps every host shares: the scan, the planners' inputs, the one builder ------------------------------------------
+def _offsets(lib, rs, cs):
+    """oriana_pack_offsets on device copies of the int32 counts -> (roff, coff, totals) on the host."""
+    from oriana_amd._lib import ptr, stream_ptr
+    nt = int(rs.size)
+    drs, dcs = (torch.from_numpy(np.concatenate([a, np.zeros(1, np.int32)])).cuda() for a in (rs, cs))      # (never empty)
+    roff = torch.full((nt + 1,), -1, dtype=torch.int64, device='cuda')
+    coff = torch.full((nt + 1,), -1, dtype=torch.int64, device='cuda')
+    tot = np.full(2, -1, dtype=np.int64)
+    assert lib.oriana_pack_offsets(ptr(roff), ptr(coff), ptr(drs), ptr(dcs), nt, tot.ctypes.data, stream_ptr()) == 0
+    return roff.cpu().numpy(), coff.cpu().numpy(), tot                  # (the entry has synchronised: tot is final here)
+
+
+def _assert_offsets(lib, rs, cs):
+    roff, coff, tot = _offsets(lib, rs, cs)
+    for off, cnt, total in ((roff, rs, tot[0]), (coff, cs, tot[1])):
+        want = np.concatenate([np.zeros(1, np.int64), np.cumsum(cnt.astype(np.int64))])
+        assert off.dtype == np.int64 and np.array_equal(off, want)
+        assert off[-1] == total == int(cnt.astype(np.int64).sum())
+
+
+@pytest.mark.parametrize('nt', [0, 1, 63, 64, 1023, 1024, 1025, 3 * 1024 + 7])
+def test_pack_offsets_equal_cumsum(lib, nt):
+    """The wave boundary (64), the work-group carry (1024) and an empty table."""
+    rng = np.random.default_rng(nt)
+    _assert_offsets(lib, rng.integers(0, 70000, size=nt).astype(np.int32), rng.integers(0, 70000, size=nt).astype(np.int32))
+
+
+def test_pack_offsets_carry_past_32_bits(lib):
+    nt = 3 * 1024 + 7
+    big = np.full(nt, 1 << 21, dtype=np.int32)
+    assert nt * (1 << 21) > 1 << 32
+    _assert_offsets(lib, big, big + 64)
+
+
+def _plan_inputs(lib, rs, cslice, nrb, ncb, want_cost=True, want_iters=True):
+    from oriana_amd._lib import ptr, stream_ptr
+    cost = np.full(ncb, np.nan) if want_cost else None
+    iters = np.full(nrb * ncb, -1, dtype=np.int32) if want_iters else None
+    assert lib.oriana_plan_inputs(ptr(rs) if want_cost else None, ptr(cslice) if want_iters else None, nrb, ncb,
+                                  cost.ctypes.data if want_cost else None, iters.ctypes.data if want_iters else None,
+                                  stream_ptr()) == 0
+    return cost, iters
+
+
+@pytest.fixture(scope='module')
+def packed_e(eng):
+    """(n, m, dense_density) -> (CountTiles, its tile_rslots as they were before finish() dropped them), packed once."""
+    out = {}
+    orig = eng.CountTiles.finish
+    saved = []
+
+    def finish(self):
+        saved.append(self.tile_rslots.clone())
+        return orig(self)
+    eng.CountTiles.finish = finish
+    try:
+        for n, m, dd in [(513, 257, None), (257, 5, None), (1000, 300, 0.2)]:
+            ct = eng.CountTiles.from_dense(_counts_a(n, m, np.float32, hybrid=bool(dd)), 'cuda', dense_density=dd)
+            out[n, m, dd] = (ct, saved.pop())
+            assert not saved and (ct.gd >= 32) == bool(dd)
+    finally:
+        eng.CountTiles.finish = orig
+    return out
+
+
+@pytest.mark.parametrize('n,m,dd', [(513, 257, None), (257, 5, None), (1000, 300, 0.2)], ids=['513x257', '257x5', '1000x300-hybrid'])
+def test_plan_inputs_equal_numpy(lib, packed_e, n, m, dd):
+    """Both planner inputs from a packed layout's own tables, exactly: the longest column slice per tile as integers, the
+    gene-tile cost as the bit pattern of the doubles -- against sum / nrb / 1024 + 2 and against the expression the Python
+    host used before it called this entry (float64 mean / (16 * 64) + 2.0): the row split cannot have moved."""
+    ct, rs = packed_e[n, m, dd]
+    nrb, ncb, nt = ct.nrb, ct.ncb, ct.nrb * ct.ncb
+    assert nt > 0 and ncb == (m - ct.gd + TILE - 1) // TILE
+    h = ct.host_arrays()
+    cost, iters = _plan_inputs(lib, rs, ct.cslice, nrb, ncb)
+    cs = h['cslice'][:nt].astype(np.int64)
+    want_iters = ((cs[:, 1:] - cs[:, :-1]) // 64).max(axis=1).astype(np.int32)
+    assert iters.dtype == np.int32 and np.array_equal(iters, want_iters) and want_iters.max() > 0
+    rsh = rs.cpu().numpy()[:nt].reshape(nrb, ncb)
+    assert np.array_equal(rsh.sum(axis=1, dtype=np.int64), np.diff(h['roff'])[:nt].reshape(nrb, ncb).sum(axis=1))     # the layout's own
+    want_cost = rsh.sum(axis=0, dtype=np.float64) / float(nrb) / 1024.0 + 2.0
+    parent = rsh.astype(np.float64).mean(axis=0) / (16 * 64) + 2.0
+    assert cost.dtype == np.float64 and np.array_equal(cost.view(np.int64), want_cost.view(np.int64))
+    assert np.array_equal(cost.view(np.int64), parent.view(np.int64))
+    assert np.array_equal(ct.gene_tile_cost.view(np.int64), cost.view(np.int64))         # what finish() handed to the row plan
+
+
+@pytest.mark.parametrize('which', ['no_cost', 'no_iters'])
+def test_plan_inputs_either_output_may_be_null(lib, packed_e, which):
+    """A NULL output (its device table is then NULL too) leaves the other one as it is with both."""
+    ct, rs = packed_e[513, 257, None]
+    cost, iters = _plan_inputs(lib, rs, ct.cslice, ct.nrb, ct.ncb)
+    c1, i1 = _plan_inputs(lib, rs, ct.cslice, ct.nrb, ct.ncb, want_cost=which != 'no_cost', want_iters=which != 'no_iters')
+    if which == 'no_cost':
+        assert c1 is None and np.array_equal(i1, iters)
+    else:
+        assert i1 is None and np.array_equal(c1.view(np.int64), cost.view(np.int64))
+
+
+@pytest.mark.parametrize('sort_rows,dd', [(True, None), (False, 0.2)], ids=['sliced_sort_rows', 'hybrid'])
+def test_from_chunks_equals_from_dense(eng, sort_rows, dd):
+    """One builder: a generator of 256-row chunks and the dense matrix cut into 256-row chunks give the same layout, the
+    per-chunk cell order included."""
+    n, m = 1000, 300
+    X = _counts_a(n, m, np.float32, hybrid=bool(dd))
+    Xd = torch.from_numpy(X).cuda()
+    ct_c = eng.CountTiles.from_chunks(n, m, lambda r0, r1: Xd[r0:r1], 256, 'cuda', sort_rows=sort_rows, dense_density=dd)
+    ct_d = eng.CountTiles.from_dense(X, 'cuda', chunk_bytes=1, sort_rows=sort_rows, dense_density=dd)
+    assert (ct_c.gd >= 32) == bool(dd) and (ct_c.row_perm is not None) == sort_rows
+    _assert_same_layout(ct_c, ct_d)

@@ -75,9 +75,9 @@ def test_resident_plans_equal_the_python_hosts(lib):
     """engine.CountTiles (the Python host) and the handle call the same planning functions on the same tables: same gene
     order, same dense set, same slots, same number of column work items, same row split."""
     from oriana_amd import engine
-    n, m, K = 2600, 900, 100
-    _, X, lu, lv = _data(3, n, m, K, z=0.3)
-    for dd in (0.0, 0.2):
+    # (40 x 33: one tile, fewer than 256 rows; 600 x 64 at 1e-6: every expressed gene dense, the sliced part (nearly) empty)
+    for n, m, K, dd in [(2600, 900, 100, 0.0), (2600, 900, 100, 0.2), (40, 33, 7, 0.0), (600, 64, 36, 1e-6)]:
+        _, X, lu, lv = _data(3, n, m, K, z=0.3)
         h = _create(lib, X, K, dd)
         info = _info(lib, h)
         ct = engine.CountTiles.from_dense(X, 'cuda', dense_density=dd or None)
