@@ -90,6 +90,34 @@ PS_FLOOR = {'p_s': 1.4e-5, 'S_hat': 1.4e-5, 'pi_s': 2e-6}   # absolute, against 
 PS_FACTOR = 8.0                                            # ... or this many times the reference's own distance from exact (<= 2.0e-6)
 
 
+# The log sums Z_log (and Z_i, Z_j beside them) under scale drift (tests/test_sparse_side_gpu.py, tests/logsum_reference.py:
+# n = 300, m = 260, lu = 1.5 N + shift_u, lv = 1.5 N + shift_v at (0, 0), (35, -30), (-40, 38) and (35, -30) with one cell at
+# lu - 80; seven kernel forms) are judged against the float64 loop nest (cavi_oracle.zq_exact) in err_colrel: the HIP output may
+# be no further from exact than ZLOG_FLOOR, or ZLOG_FACTOR times the distance of the reference's own float32 nest on the same
+# inputs, which the test measures at run time.  Measured, all 28 cases (profiles/zlog_drift_errors.json):
+#   * HIP / reference distance: Z_log <= 1.32 x, Z_j <= 1.20 x, Z_i <= 1.67 x (HIP 1.1e-7 .. 3.0e-7 on the fast path);
+#   * two plain float32 sums without the per-factor centre (logsum_reference.logsum_f32(center=False)) at (-40, 38):
+#     3.0e-6 .. 8.1e-6 = 15.2 x (K = 200) .. 24.1 x (K = 100) the reference's distance; the centred evaluation of the same sums
+#     <= 1.7 x.  At (35, -30) the un-centred form is only 3.7 .. 6.2 x: that shift alone does not tell the two apart, (-40, 38) does.
+#     On the GPU itself, oriana_scale_factor_centered and oriana_finalize_zlog called with acc = NULL at K = 20: 3.3e-6 against
+#     1.3e-7 with the centre (test_log_centre_is_applied_consistently).
+# ZLOG_FACTOR sits above twice the worst HIP ratio (3.35) and below half the smallest un-centred ratio (7.6).
+ZLOG_FACTOR = 4.0
+# ... or this, absolute: four float32 roundings (2^-24 each), for a reference that happens to land within a rounding of exact
+ZLOG_FLOOR = 2.4e-7
+# The yardstick itself must be sharp: the reference's float32 nest within 1e-6 of exact (measured <= 3.9e-7 on the fast path).
+# The cell at lu - 80 has lu + lv ~ -75, which the reference rounds to float32 BEFORE the exponential: half an ulp of 75 is
+# 2^-18 = 3.8e-6 relative on that cell's r_ijk, and the cell dominates the Z_log entries it touches (measured <= 2.3e-6; the
+# slow path of the HIP side reproduces that arithmetic and lands at the same distance).
+ZLOG_REF_MAX = 1e-6
+ZLOG_REF_MAX_SLOW = 4e-6
+
+
+def zlog_bound(d_ref):
+    """The largest err_colrel from exact a HIP loop-nest output may have where the reference's float32 nest has d_ref."""
+    return max(ZLOG_FLOOR, ZLOG_FACTOR * d_ref)
+
+
 def assert_state_close(got, ref, rtol=RTOL, keys=None, what='', exact=None):
     """|got - ref| <= rtol*|ref| + rtol*colmax|ref| on every key, plus identical clamp
     patterns (entries sitting exactly on the 1e-15 floor / the 1-1e-10 ceiling).  `exact`: the state of the exact twin
