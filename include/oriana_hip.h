@@ -520,6 +520,21 @@ int oriana_foldin_update(double *a1, float *Elog, uint8_t *active, int32_t *froz
                          int64_t nslab, int64_t slab_row0, const int32_t *row_index, int64_t r, int64_t K, double tol,
                          int64_t it, float *FU_next, float *mu_out, float *upart, void *stream);
 
+/* The same step for a fold-in into a ZERO-INFLATED model (oriana_amd/models/zigap.py: fold_in), where the rate is a matrix: a
+ * cell carries the pair (a1, a2), each (r, K) float64 in the caller's row order, and one call applies
+ *   a1' = max(1e-15, nan_to_num(alpha1 + Z_i)),   a2' = max(1e-15, nan_to_num(alpha2 + rate[o]))
+ * with rate (r, K) = sum_j d_ij V_hat_jk formed by oriana_zi_foldin_rate from the U_hat of the pair that enters.  A cell FREEZES
+ * when |a1' - a1| <= tol * a1 AND |a2' - a2| <= tol * a2 hold in every factor; a frozen cell is never written again.  Every
+ * other active cell gets a1, a2, U_hat = a1' / a2' (r, K float64), Elog = f32(psi(f32(a1'))) - logf(f32(a2')) minus its row
+ * maximum, and the prep outputs FU_next / mu_out / upart, exactly as oriana_foldin_update.  R == NULL: the START -- the pair is
+ * taken as it is; U_hat, Elog, FU_next, mu_out are written from it.  The same K and alignment coverage as oriana_foldin_update
+ * (a2, rate and U_hat join the buffers whose 16-byte alignment selects the vector instantiations). */
+int oriana_foldin_update_zi(double *a1, double *a2, double *U_hat, float *Elog, uint8_t *active, int32_t *froze_at,
+                            int32_t *n_active, const double *alpha1, const double *alpha2, const double *rate,
+                            const float *Z, const float *F, const float *R, int64_t nslab, int64_t slab_row0,
+                            const int32_t *row_index, int64_t r, int64_t K, double tol, int64_t it, float *FU_next,
+                            float *mu_out, float *upart, void *stream);
+
 /* M-step for one Gamma node (gap.py:117-129; utils.py:39-51):
  *   p1 = max(1e-15, nan_to_num(inverse_digamma(log(p2) + f32(colsum_Elog / count))))
  *   p2 = max(1e-15, nan_to_num(p1 / (colsum_E / count)))            (K-vectors, f64, in place) */
@@ -606,6 +621,21 @@ int oriana_dropout_sweep_fused_tiles(float *D_hat, const double *U, const double
                                      void *stream);
 int64_t oriana_nzmask_tiles_words(int64_t n, int64_t m);
 int oriana_nzmask_tiles(uint32_t *tiles, const uint32_t *nzmask, int64_t n, int64_t m, void *stream);
+/* The oriana_nzmask_f32 layout straight from packed counts, in the caller's row and gene order (cm->row_perm, cm->col_perm):
+ * mask[(i / 32) * ld + j] bit (i % 32) |= (x_ij != 0), ld >= cm->m.  The mask must be ZEROED first (ceil(cm->n / 32) * ld words);
+ * no (n, m) float matrix exists at any point.  With oriana_nzmask_tiles: both mask forms of a query. */
+int oriana_nzmask_counts(uint32_t *mask, const oriana_counts *cm, int64_t ld, void *stream);
+/* The cell-side rate of a fold-in into a ZI model: DV[i, :] += sum_j d_ij V[j, :]  (DV (n, K) float64, zeroed by the caller) with
+ *   d_ij = 1 where x_ij != 0;  1e-10 / 1 where pi_d_j <= 0 / >= 1;  f32(sigmoid(logit(pi_d_j) - U_i . V_j)) elsewhere
+ * -- the D_hat of oriana_dropout_sweep_fused_tiles, formed tile by tile in registers and NEVER stored: no D_hat, no column sums.
+ * K <= 128 (else ORIANA_EKRANGE); the kernel family that serves a K is the one that entry runs for it (the same rule and the
+ * same preconditions, minus the D_hat pointer), compiled without the store and the column-sum path.  nzmask (required) and
+ * nztiles (optional, as above) describe the cells at hand; scratch: oriana_dropout_sweep_scratch_floats(m, K) floats, 16-byte
+ * aligned.  active [n] bytes or NULL (= every cell): a work-group whose cells are all inactive returns at once; rows of U and DV
+ * that belong to inactive cells are neither read nor written. */
+int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
+                          const uint32_t *nztiles, const uint8_t *active, float *scratch, int arithmetic, int64_t n, int64_t m,
+                          int64_t K, void *stream);
 /* out[m, K] += D_hat^T W[n, K] (zigap.py:124), D_hat streamed once; `out` must be initialised.  arithmetic as above;
  * scratch: oriana_dense_t_scratch_floats(n, K) floats (16-byte aligned; the bf16 operand images of W), may be NULL
  * with ORIANA_MATRIX_F32. */

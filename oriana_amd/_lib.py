@@ -109,6 +109,7 @@ _SIGS = {
     'oriana_gamma_update_finalize_lazy': (c_int, [_P] * 10 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     'oriana_foldin_update_blocks': (_I, [_I]),
     'oriana_foldin_update': (c_int, [_P] * 10 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),
+    'oriana_foldin_update_zi': (c_int, [_P] * 13 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),
     'oriana_mstep_gamma_pair': (c_int, [_P, _P, _P, _P, c_double, _P, _P, _P, _P, c_double, _P, _I, _P]),
     'oriana_colsum_f64': (c_int, [_P, _P, _P, _I, _I, _P]),
     'oriana_dropout_update': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
@@ -119,6 +120,8 @@ _SIGS = {
     'oriana_dropout_sweep_fused_tiles': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _I, _I, _I, _P]),
     'oriana_nzmask_tiles_words': (_I, [_I, _I]),
     'oriana_nzmask_tiles': (c_int, [_P, _P, _I, _I, _P]),
+    'oriana_nzmask_counts': (c_int, [_P, ctypes.POINTER(OrianaCounts), _I, _P]),
+    'oriana_zi_foldin_rate': (c_int, [_P] * 8 + [c_int, _I, _I, _I, _P]),
     'oriana_dense_t_times_factor_f32': (c_int, [_P, _P, _P, _P, c_int, _I, _I, _I, _P]),
     'oriana_dense_t_scratch_floats': (_I, [_I, _I]),
     'oriana_factor_cast_f32': (c_int, [_P, _P, _P, _P, _I, _I, _P]),

@@ -77,6 +77,26 @@ __global__ __launch_bounds__(256) void k_dropout_fix_nz(oriana_counts cm, double
     }
 }
 
+// The oriana_nzmask_f32 layout straight from the packed counts (no (n, m) float matrix): the same walk, one atomicOr per
+// non-zero count into a zeroed mask, in the caller's row and gene order.
+__global__ __launch_bounds__(256) void k_nzmask_counts(oriana_counts cm, uint32_t *__restrict__ mask, int64_t ld) {
+    const int64_t t = blockIdx.x;
+    const int64_t rb = t / cm.ncb, cb = t - rb * cm.ncb;
+    const int64_t rbase = cm.roff[t];
+    for (int sl = 0; sl < 16; ++sl) {
+        const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+        for (uint32_t slot = s0 + threadIdx.x; slot < s1; slot += 256) {
+            const oriana_rowrec rec = cm.rowrec[rbase + slot];
+            if (rec.x == 0.f) continue;
+            const int64_t ip = rb * TILE + sl * 16 + (int)(((slot - s0) & 63u) >> 2);
+            const int64_t jp = cb * TILE + rec.col;
+            const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+            const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+            if (i >= 0 && i < cm.n && j >= 0 && j < cm.m) atomicOr(&mask[(i >> 5) * ld + j], 1u << (int)(i & 31));
+        }
+    }
+}
+
 // out[j] += sum_i A[i,j] for a wide (rows, m) f64 matrix (pi_d = mean(p_d, axis=0), zigap.py:158)
 __global__ __launch_bounds__(256) void k_colsum_wide(double *__restrict__ out, const double *__restrict__ A,
                                                      int64_t rows, int64_t m) {
@@ -292,6 +312,16 @@ extern "C" int oriana_dropout_fix_nz_ld(const oriana_counts *cm, double *p_d, fl
     const int64_t nt = cm->nrb * cm->ncb;
     if (nt == 0 || cm->rslots == 0) return 0;
     hipLaunchKernelGGL(k_dropout_fix_nz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, p_d, D_hat, value, ld);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_nzmask_counts(uint32_t *mask, const oriana_counts *cm, int64_t ld, void *stream) {
+    if (!cm || ld < cm->m) return ORIANA_EINVAL;
+    const int64_t nt = cm->nrb * cm->ncb;
+    if (nt == 0 || cm->rslots == 0) return 0;
+    if (!mask || nt > 0x7fffffffLL) return ORIANA_EINVAL;
+    hipLaunchKernelGGL(k_nzmask_counts, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, mask, ld);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

@@ -69,12 +69,15 @@ struct SweepLds {
 //   8 (v / 4) + 4 h + v % 4: the reduction simply visits the genes in that order);
 //   D_hat goes to HBM through a 32 x 32 transpose in LDS (128-byte runs per cell row); the same read-back yields
 //   the tile's column sums.
-template <int NT>
+// RATE (oriana_zi_foldin_rate): DV alone -- the transpose, the D_hat store and the column sums are compiled out; a work-group
+// none of whose 128 cells is active returns at its top, U_hat rows of inactive cells are not read, their DV rows not written.
+template <int NT, bool RATE = false>
 __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float *__restrict__ D_hat, const double *__restrict__ U,
                                                        const double *__restrict__ V, const float *__restrict__ lgit,
                                                        const uint32_t *__restrict__ nzmask, double *__restrict__ colsum,
                                                        const double *__restrict__ Vn, double *__restrict__ DV,
-                                                       int64_t n, int64_t m, int K, int KP2, int64_t j_per_split) {
+                                                       int64_t n, int64_t m, int K, int KP2, int64_t j_per_split,
+                                                       const uint8_t *__restrict__ active) {
     extern __shared__ float lds[];
     const SweepLds L(KP2, NT);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
@@ -84,12 +87,15 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
     const int KS = KP2 >> 1;
     float *Us = lds + L.us + w * KP2 * 32;
     float *T = lds + L.tb + w * 32 * TS;
+    if constexpr (RATE) {
+        if (!dn::any_active<128>(active, (int64_t)blockIdx.x * 128, n, lane)) return;     // (work-group uniform)
+    }
 
     // the wave's strip of U_hat, [k][cell]
     for (int e = lane; e < KP2 * 32; e += 64) {
         const int cell = e / KP2, kk = e - cell * KP2;            // consecutive lanes: consecutive k of one cell
         const int64_t i = i0w + cell;
-        Us[kk * 32 + cell] = (i < n && kk < K) ? (float)U[i * K + kk] : 0.f;
+        Us[kk * 32 + cell] = ((RATE ? dn::cell_active(active, i, n) : i < n) && kk < K) ? (float)U[i * K + kk] : 0.f;
     }
 
     // Staging of one gene tile, 8 threads per gene.  The vector-memory counter of gfx9 retires loads, stores and
@@ -181,7 +187,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
     for (int64_t j0 = jb; j0 < je; j0 += 32) {
         const bool more = j0 + 32 < je;
         { const int64_t jn = more ? j0 + 32 : j0; stage_load(jn); meta_load(jn); }   // (the last tile again: unused)
-        if (j0 > jb) colsum_flush(j0 - 32, par ^ 1);
+        if constexpr (!RATE) { if (j0 > jb) colsum_flush(j0 - 32, par ^ 1); }
         ORIANA_VMEM_FENCE();
         // ---- Lambda^T = V U^T: four steps per turn, the operands of the next turn requested before the matrix
         // instructions of this one (an LDS round trip is longer than one 16-pass instruction)
@@ -235,14 +241,16 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
 #pragma unroll
             for (int v = 0; v < 16; ++v) if (!rowok || acc_row(v, h) >= jrem) l0[v] = 0.f;
         }
+        if constexpr (!RATE) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) T[c * TS + acc_row(v, h)] = l0[v];
+            for (int v = 0; v < 16; ++v) T[c * TS + acc_row(v, h)] = l0[v];
+        }
         __builtin_amdgcn_wave_barrier();
         stage_store(buf ^ 1);
         meta_store(buf ^ 1);
         ORIANA_VMEM_FENCE();
         // ---- D_hat rows out, column sums of the tile
-        {
+        if constexpr (!RATE) {
             const int gq = (lane & 7) * 4;
             const bool full = vec_ok && jrem == 32;              // uniform: whole 16-byte pieces
             f4v csum = {0.f, 0.f, 0.f, 0.f};
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
         buf ^= 1;
         par ^= 1;
     }
-    if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1);
+    if constexpr (!RATE) { if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1); }
     if (Vn && DV) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -306,7 +314,8 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
             for (int v = 0; v < 16; ++v) {
                 const int64_t i = i0w + acc_row(v, h);
                 const int k = nt * 32 + c;
-                if (i < n && k < K) atomicAdd(&DV[i * K + k], (double)dvs[nt][v] + (double)dv[nt][v]);
+                if ((RATE ? dn::cell_active(active, i, n) : i < n) && k < K)
+                    atomicAdd(&DV[i * K + k], (double)dvs[nt][v] + (double)dv[nt][v]);
             }
     }
 }
@@ -579,13 +588,13 @@ __global__ __launch_bounds__(256) void k_split_images(u4v *__restrict__ img1, u4
     }
 }
 
-template <int NT, int KC>
+template <int NT, int KC, bool RATE = false>        // RATE: as k_dropout_sweep
 __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict__ D_hat, const double *__restrict__ U,
                                                               const u4v *__restrict__ img1, const float *__restrict__ lgit,
                                                               const uint32_t *__restrict__ nzmask,
                                                               double *__restrict__ colsum, const u4v *__restrict__ img2,
                                                               double *__restrict__ DV, int64_t n, int64_t m, int K,
-                                                              int64_t j_per_split) {
+                                                              int64_t j_per_split, const uint8_t *__restrict__ active) {
     extern __shared__ float lds[];
     char *ldsb = reinterpret_cast<char *>(lds);
     const B16Lds L(KC, NT);
@@ -596,19 +605,23 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
     float *T = reinterpret_cast<float *>(ldsb + L.tb) + w * 32 * TS;
     u4v *vt_img = reinterpret_cast<u4v *>(ldsb + L.vt);
     u4v *v2_img = reinterpret_cast<u4v *>(ldsb + L.v2);
+    if constexpr (RATE) {
+        if (!dn::any_active<128>(active, (int64_t)blockIdx.x * 128, n, lane)) return;     // (work-group uniform)
+    }
 
     // the wave's strip of U_hat as the B operand of the first product: per k chunk, factors 16 kc + 8 h + e of cell c
     u4v ub[KC][3];
     {
         const int64_t i = i0w + c;
-        const double *urow = U + (i < n ? i : n - 1) * K;
+        const bool on = RATE ? dn::cell_active(active, i, n) : i < n;
+        const double *urow = U + (RATE ? (on ? i : 0) : (i < n ? i : n - 1)) * K;
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int kk = 16 * kc + 8 * h + e;
-                x[e] = (i < n && kk < K) ? (float)urow[kk < K ? kk : K - 1] : 0.f;
+                x[e] = (on && kk < K) ? (float)urow[kk < K ? kk : K - 1] : 0.f;
             }
             split8(x, ub[kc]);
         }
@@ -688,7 +701,7 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
     for (int64_t j0 = jb; j0 < je; j0 += 32) {
         const bool more = j0 + 32 < je;
         { const int64_t jn = more ? j0 + 32 : j0; stage_load(jn); meta_load(jn); }   // (the last tile again: unused)
-        if (j0 > jb) colsum_flush(j0 - 32, par ^ 1);
+        if constexpr (!RATE) { if (j0 > jb) colsum_flush(j0 - 32, par ^ 1); }
         ORIANA_VMEM_FENCE();
         // ---- Lambda^T = V U^T
         f16v l0;
@@ -719,14 +732,16 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
 #pragma unroll
             for (int v = 0; v < 16; ++v) if (!rowok || acc_row(v, h) >= jrem) l0[v] = 0.f;
         }
+        if constexpr (!RATE) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) T[c * TS + acc_row(v, h)] = l0[v];
+            for (int v = 0; v < 16; ++v) T[c * TS + acc_row(v, h)] = l0[v];
+        }
         __builtin_amdgcn_wave_barrier();
         stage_store(buf ^ 1);
         meta_store(buf ^ 1);
         ORIANA_VMEM_FENCE();
         // ---- D_hat rows out, column sums of the tile
-        {
+        if constexpr (!RATE) {
             const int gq = (lane & 7) * 4;
             const bool full = vec_ok && jrem == 32;
             f4v csum = {0.f, 0.f, 0.f, 0.f};
@@ -782,7 +797,7 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
         buf ^= 1;
         par ^= 1;
     }
-    if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1);
+    if constexpr (!RATE) { if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1); }
     if (has_next && DV) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -790,7 +805,8 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
             for (int v = 0; v < 16; ++v) {
                 const int64_t i = i0w + acc_row(v, h);
                 const int k = nt * 32 + c;
-                if (i < n && k < K) atomicAdd(&DV[i * K + k], (double)dvs[nt][v] + (double)dv[nt][v]);
+                if ((RATE ? dn::cell_active(active, i, n) : i < n) && k < K)
+                    atomicAdd(&DV[i * K + k], (double)dvs[nt][v] + (double)dv[nt][v]);
             }
     }
 }
@@ -831,9 +847,10 @@ __global__ void k_logit_f32(float *__restrict__ lg, float *__restrict__ lgs, flo
     if (lgs) { lgs[j] = -v * 1.4426950408889634f; flo[j] = (pi <= 0.0) ? 1e-10f : 0.0f; }
 }
 
-template <int NT>
+template <int NT, bool RATE = false>
 static int launch_sweep(float *D_hat, const double *U, const double *V, const float *pi_d, const uint32_t *nzmask,
-                        double *colsum, const double *Vn, double *DV, int64_t n, int64_t m, int K, hipStream_t st) {
+                        double *colsum, const double *Vn, double *DV, int64_t n, int64_t m, int K, hipStream_t st,
+                        const uint8_t *active = nullptr) {
     const int KP2 = (K + 1) & ~1;
     const SweepLds L(KP2, NT);
     const size_t lds = (size_t)L.total * sizeof(float);
@@ -844,8 +861,8 @@ static int launch_sweep(float *D_hat, const double *U, const double *V, const fl
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
     if (splits > 65535 || rb > 0x7fffffffLL) return ORIANA_EINVAL;
-    return launch(k_dropout_sweep<NT>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, V, pi_d, nzmask, colsum,
-                  Vn, DV, n, m, K, KP2, jps);
+    return launch(k_dropout_sweep<NT, RATE>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, V, pi_d, nzmask, colsum,
+                  Vn, DV, n, m, K, KP2, jps, active);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -999,10 +1016,10 @@ static int launch_dt_b16(double *out, const float *D, const double *W, float *sc
 // scratch of oriana_dropout_sweep_fused (floats): logit(pi_d) [m rounded up to 64] | first images | second images
 static inline int64_t b16_img_floats(int64_t m, int pieces) { return ((m + 31) / 32) * (int64_t)pieces * 4; }
 
-template <int NT, int KC>
+template <int NT, int KC, bool RATE = false>
 static int launch_sweep_b16(float *D_hat, const double *U, const double *V, const float *lg, const uint32_t *nzmask,
                             double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m,
-                            int K, hipStream_t st) {
+                            int K, hipStream_t st, const uint8_t *active = nullptr) {
     const B16Lds L(KC, NT);
     const size_t lds = (size_t)L.total;
     u4v *img1 = reinterpret_cast<u4v *>(img_scratch);
@@ -1015,8 +1032,8 @@ static int launch_sweep_b16(float *D_hat, const double *U, const double *V, cons
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
     if (splits > 65535 || rb > 0x7fffffffLL) return ORIANA_EINVAL;
-    return launch(k_dropout_sweep_b16<NT, KC>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, img1, lg, nzmask,
-                  colsum, img2, DV, n, m, K, jps);
+    return launch(k_dropout_sweep_b16<NT, KC, RATE>, dim3((unsigned)rb, (unsigned)splits), dim3(256), lds, st, D_hat, U, img1, lg, nzmask,
+                  colsum, img2, DV, n, m, K, jps, active);
 }
 
 template <int NT, int GQ>
@@ -1086,6 +1103,41 @@ extern "C" int oriana_dropout_sweep_fused_tiles(float *D_hat, const double *U, c
                         return launch_sweep_b16<P::a, P::b>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, img, n, m, (int)K, st);
                     else
                         return launch_sweep<P::a>(D_hat, U, V, pi_d, nzmask, colsum, V_next, DV_next, n, m, (int)K, st);
+                });
+        });
+    });
+}
+
+// The cell-side rate of a ZI FOLD-IN (models/zigap.py fold_in): DV[i, :] += sum_j d_ij V[j, :] with d the float32 dropout
+// posterior of the D update above, formed from (U, V, pi_d) tile by tile and never stored -- the same rule (zi_candidate,
+// ZiOp::update), the same preconditions (zi_update_ok with no D_hat pointer) and the same kernels with RATE = true.
+extern "C" int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const double *pi_d64, const uint32_t *nzmask,
+                                     const uint32_t *nztiles, const uint8_t *active, float *scratch, int arithmetic, int64_t n,
+                                     int64_t m, int64_t K, void *stream) {
+    if (n < 0 || m < 0 || K <= 0) return ORIANA_EINVAL;
+    if (K > 128) return ORIANA_EKRANGE;
+    if (n == 0 || m == 0) return 0;
+    if (!DV || !U || !V || !pi_d64 || !nzmask || !scratch) return ORIANA_EINVAL;
+    if (((uintptr_t)scratch & 15) != 0) return ORIANA_EINVAL;
+    if (arithmetic != ORIANA_MATRIX_F32 && arithmetic != ORIANA_MATRIX_BF16X3) return ORIANA_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t mpad = (m + 63) / 64 * 64;
+    const float *pi_d = scratch, *lgs = scratch + mpad;
+    float *img = scratch + 3 * mpad;
+    hipLaunchKernelGGL(k_logit_f32, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, scratch, scratch + mpad, scratch + 2 * mpad,
+                       pi_d64, m);
+    return with_variant<ORIANA_MATRIX_F32, ORIANA_MATRIX_BF16X3>(arithmetic, [&](auto A) {
+        return dn::with_cfg<1, dn::ZI_KP_MAX / 16>(dn::kc_tail(oriana_kpad(K)), [&](auto c) {
+            return dn::zi_first<dn::ZiOp::update, decltype(c)::KP, decltype(A)::value>(
+                [&](dn::ZiFam f) { return dn::zi_update_ok(f, nullptr, lgs, nztiles, V, DV, m); },
+                [&](auto p) {
+                    using P = decltype(p);
+                    if constexpr (P::fam == dn::ZiFam::tiles)
+                        return dn::zi_rate({P::a, P::b}, U, V, lgs, mpad, nztiles, DV, active, img, n, m, (int)K, st);
+                    else if constexpr (P::fam == dn::ZiFam::b16)
+                        return launch_sweep_b16<P::a, P::b, true>(nullptr, U, V, pi_d, nzmask, nullptr, V, DV, img, n, m, (int)K, st, active);
+                    else
+                        return launch_sweep<P::a, true>(nullptr, U, V, pi_d, nzmask, nullptr, V, DV, n, m, (int)K, st, active);
                 });
         });
     });

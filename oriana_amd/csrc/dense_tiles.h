@@ -51,6 +51,24 @@ __device__ __forceinline__ int acc_row(int v, int h) { return 8 * (v >> 2) + 4 *
 constexpr int TS = 36;            // row stride of the transpose buffer (floats): 16-byte aligned rows
 constexpr int NW = 8;             // waves per work-group
 
+// The rate-only form of the D update (oriana_zi_foldin_rate, template flag RATE of the three kernel families): some cell of
+// [i0, i0 + CELLS) is active -- the same answer in every lane of every wave of the work-group, which returns at its top on
+// `false`.  active == NULL: every cell counts as active.
+template <int CELLS>
+__device__ __forceinline__ bool any_active(const uint8_t *__restrict__ active, int64_t i0, int64_t n, int lane) {
+    if (!active) return true;
+    bool a = false;
+#pragma unroll
+    for (int o = 0; o < CELLS; o += 64) {
+        const int64_t i = i0 + o + lane;
+        a = a || (i < n && active[i] != 0);
+    }
+    return __ballot(a) != 0ull;
+}
+__device__ __forceinline__ bool cell_active(const uint8_t *__restrict__ active, int64_t i, int64_t n) {
+    return i < n && (!active || active[i] != 0);
+}
+
 // Operand images, in 16-byte pieces [..][split][lane]: a wave-wide copy of 64 consecutive pieces is one LDS-DMA
 // instruction (global_load_lds_dwordx4 writes lane x 16 bytes from a wave-uniform base).
 //   first image  (A operand of den^T = FV FU^T)   [k chunk][split][lane = 32 G' + g]: F[g][16 kc + 8 G' .. + 7]
@@ -216,6 +234,9 @@ int zi_tiles(uint32_t *out, const uint32_t *nzmask, int64_t n, int64_t m, hipStr
 int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
              double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st);
 int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st);
+// zi_sweep without the D_hat store and the column sums (k_zi_row<KC, TAIL, RATE = true>): DV += d V over the active cells only
+int zi_rate(KcTl cfg, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles, double *DV,
+            const uint8_t *active, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st);
 
 }  // namespace dn
 }  // namespace oriana

@@ -133,12 +133,15 @@ __device__ __forceinline__ void zi_tile_dma(const u4v *__restrict__ imgV, const 
 template <int KC, int TAIL>
 constexpr int zi_row_lds_bytes() { return 3 * Cfg<KC, TAIL>::PVZ * 16 + NW * 32 * 32 * 4 + 2 * NW * 32 * 4; }
 
-template <int KC, int TAIL>
+// RATE (oriana_zi_foldin_rate: the fold-in of new cells into a fitted ZI model): DV alone -- no D_hat store, no transpose, no
+// column sums (D_hat and colsum are not touched); a work-group none of whose 256 cells is active returns at once, the U_hat
+// rows of inactive cells are not read (they enter as padding) and their DV rows are not written.
+template <int KC, int TAIL, bool RATE = false>
 __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const double *__restrict__ U,
                                                 const u4v *__restrict__ imgV, const float *__restrict__ lgit, int64_t mpad,
                                                 const uint32_t *__restrict__ nztiles, double *__restrict__ colsum,
                                                 double *__restrict__ DV, int64_t n, int64_t m, int K, int ngt,
-                                                int gt_per_split) {
+                                                int gt_per_split, const uint8_t *__restrict__ active) {
     using C = Cfg<KC, TAIL>;
     constexpr int NT = C::NT;
     constexpr int MP = C::PV_RAW;                                          // first mask piece inside an image buffer
@@ -158,26 +161,30 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
     const int gt0 = blockIdx.y * gt_per_split;
     const int gt1 = (gt0 + gt_per_split < ngt) ? gt0 + gt_per_split : ngt;
     if (gt0 >= gt1) return;
+    if constexpr (RATE) {
+        if (!any_active<NW * 32>(active, ct_blk0 * 32, n, lane)) return;     // (work-group uniform, before the first barrier)
+    }
 
     // the wave's strip of U_hat as the B operand of the first product: per k chunk, factors 16 kc + 8 h + e of cell c
     // (padding cells: zeros -- their rows are neither stored nor summed)
     u4v ub[KC][3];
     f4v fut = {0.f, 0.f, 0.f, 0.f};
     {
-        const double *urow = U + (i < n ? i : 0) * K;
+        const bool on = RATE ? cell_active(active, i, n) : i < n;
+        const double *urow = U + (on ? i : 0) * K;
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int kk = 16 * kc + 8 * h + e;
-                x[e] = (i < n && kk < K) ? (float)urow[kk < K ? kk : K - 1] : 0.f;
+                x[e] = (on && kk < K) ? (float)urow[kk < K ? kk : K - 1] : 0.f;
             }
             split8(x, ub[kc]);
         }
         if (TAIL) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) fut[e] = (i < n && C::KM + e < K) ? (float)urow[C::KM + e < K ? C::KM + e : K - 1] : 0.f;
+            for (int e = 0; e < 4; ++e) fut[e] = (on && C::KM + e < K) ? (float)urow[C::KM + e < K ? C::KM + e : K - 1] : 0.f;
         }
     }
     const float futb0 = h ? fut.y : fut.x, futb1 = h ? fut.w : fut.z;
@@ -254,7 +261,7 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
         const u4v *im1 = img + bufn * C::PVZ;                               // tile gt + 1: first product
         const u4v *im0 = img + buf * C::PVZ;                                // tile gt: second product, masks, logits
         const int64_t j0 = (int64_t)gt * 32;
-        if (gt > gt0) colsum_flush(gt - 1, par ^ 1);
+        if constexpr (!RATE) { if (gt > gt0) colsum_flush(gt - 1, par ^ 1); }
         // The image, masks and logits of tile gt + 2 go out into the buffer tile gt - 1 has left: in the middle of the
         // matrix work for the long loops (item 16 below; measured at 100k x 20k: 5.10 against 5.26 ms at K = 100, 4.38 / 4.46
         // at K = 80), here at the top for KC <= 3 (3.45 against 3.78 ms at K = 48)
@@ -322,31 +329,35 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
                         asm("v_bfi_b32 %0, %1, 1.0, %2" : "=v"(p) : "v"(sel), "v"(p));            // (sel & 1.0f) | (~sel & p)
                     }
                     l0[v] = p;
-                    if ((v & 3) == 3)
+                    if (!RATE && (v & 3) == 3)
                         *reinterpret_cast<__attribute__((address_space(3))) f4v *>(Tw0 ^ (uint32_t)(q << 5)) =
                             f4v{l0[v - 3], l0[v - 2], l0[v - 1], l0[v]};
                 } else if (it == 16) {
-                    __builtin_amdgcn_wave_barrier();
+                    if constexpr (!RATE) {
+                        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) tq[q] = *reinterpret_cast<const f4v *>(Tr + 8 * q * 32);
+                        for (int q = 0; q < 4; ++q) tq[q] = *reinterpret_cast<const f4v *>(Tr + 8 * q * 32);
+                    }
                     if (!DMA_TOP)
                         zi_tile_dma<KC, TAIL>(imgV, nztiles, lgit, mpad, img + bufnn * C::PVZ, (gt + 2 < gt1) ? gt + 2 : gt1 - 1, ct_blk0, ngt, m,
                                   w, lane);
                 } else if (it == 17) {
-                    // D_hat rows out
-                    const uint32_t vo = (j0 + gq < m) ? dvoff : 0x80000000u;
+                    if constexpr (!RATE) {
+                        // D_hat rows out
+                        const uint32_t vo = (j0 + gq < m) ? dvoff : 0x80000000u;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, tq[q]), drsrc, vo,
-                                                               (int)((j0 + (int64_t)8 * q * m) * 4), 0);
-                    // sum_i p_d of the wave's 32 cells: lanes with the same lane % 8 hold the same four genes
-                    // (padding cells -- only the matrix's last cell tile has any -- enter with weight 0)
-                    f4v cs4 = tq[0] * (0 < rleft ? 1.f : 0.f);
-                    cs4 = tq[1] * (8 < rleft ? 1.f : 0.f) + cs4;
-                    cs4 = tq[2] * (16 < rleft ? 1.f : 0.f) + cs4;
-                    cs4 = tq[3] * (24 < rleft ? 1.f : 0.f) + cs4;
-                    cs4.x = sum_mod8(cs4.x); cs4.y = sum_mod8(cs4.y); cs4.z = sum_mod8(cs4.z); cs4.w = sum_mod8(cs4.w);
-                    *reinterpret_cast<f4v *>(csb + (par * NW + w) * 32 + gq) = cs4;      // (eight lanes, the same value)
+                        for (int q = 0; q < 4; ++q)
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, tq[q]), drsrc, vo,
+                                                                   (int)((j0 + (int64_t)8 * q * m) * 4), 0);
+                        // sum_i p_d of the wave's 32 cells: lanes with the same lane % 8 hold the same four genes
+                        // (padding cells -- only the matrix's last cell tile has any -- enter with weight 0)
+                        f4v cs4 = tq[0] * (0 < rleft ? 1.f : 0.f);
+                        cs4 = tq[1] * (8 < rleft ? 1.f : 0.f) + cs4;
+                        cs4 = tq[2] * (16 < rleft ? 1.f : 0.f) + cs4;
+                        cs4 = tq[3] * (24 < rleft ? 1.f : 0.f) + cs4;
+                        cs4.x = sum_mod8(cs4.x); cs4.y = sum_mod8(cs4.y); cs4.z = sum_mod8(cs4.z); cs4.w = sum_mod8(cs4.w);
+                        *reinterpret_cast<f4v *>(csb + (par * NW + w) * 32 + gq) = cs4;      // (eight lanes, the same value)
+                    }
                 } else {
                     const int vv = it - 18;
                     const float x0 = l0[vv];
@@ -408,7 +419,7 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
         buf = bufn;
         par ^= 1;
     }
-    colsum_flush(gt1 - 1, par ^ 1);
+    if constexpr (!RATE) colsum_flush(gt1 - 1, par ^ 1);
     // ---- out: DV[cell, k] += the strip's sums (float64, zeroed by the caller)
     if (DV) {
 #pragma unroll
@@ -417,7 +428,8 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
             for (int v = 0; v < 16; ++v) {
                 const int64_t cell = ct * 32 + acc_row(v, h);
                 const int k = nt * 32 + c;
-                if (cell < n && k < (TIB ? C::KM + 4 : C::KM) && k < K) atomicAdd(&DV[cell * K + k], (double)rs[nt][v]);
+                if ((RATE ? cell_active(active, cell, n) : cell < n) && k < (TIB ? C::KM + 4 : C::KM) && k < K)
+                    atomicAdd(&DV[cell * K + k], (double)rs[nt][v]);
             }
         if (TAIL && !TIB) {
             rt.x += __shfl_xor(rt.x, 32, 64); rt.y += __shfl_xor(rt.y, 32, 64);
@@ -427,7 +439,7 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int64_t cell = ct * 32 + 4 * (lane >> 2) + e;
-                    if (cell < n && k < K) atomicAdd(&DV[cell * K + k], (double)rt[e]);
+                    if ((RATE ? cell_active(active, cell, n) : cell < n) && k < K) atomicAdd(&DV[cell * K + k], (double)rt[e]);
                 }
             }
         }
@@ -630,8 +642,10 @@ int zi_tiles(uint32_t *out, const uint32_t *nzmask, int64_t n, int64_t m, hipStr
 }
 
 // lgit: [0, mpad) the scaled logits -logit(pi_d) log2(e), [mpad, 2 mpad) the floors (k_logit_f32)
-int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
-             double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
+template <bool RATE>
+static int zi_sweep_launch(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad,
+                           const uint32_t *nztiles, double *colsum, const double *Vn, double *DV, const uint8_t *active,
+                           float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
     const int ngt = (int)((m + 31) / 32);
     const int64_t blocks = ((n + 31) / 32 + NW - 1) / NW;
     int64_t splits = zi_pick_splits(blocks, (ngt + 7) / 8);
@@ -646,10 +660,20 @@ int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const flo
         } else {
             const int rc = launch(k_zi_images<KC, TL, true>, dim3((unsigned)ngt), dim3(512), 0, st, img, V, Vn, m, K);
             if (rc) return rc;
-            return launch(k_zi_row<KC, TL>, dim3((unsigned)blocks, (unsigned)splits), dim3(512), (size_t)zi_row_lds_bytes<KC, TL>(), st,
-                          D_hat, U, img, lgit, mpad, nztiles, colsum, DV, n, m, K, ngt, per);
+            return launch(k_zi_row<KC, TL, RATE>, dim3((unsigned)blocks, (unsigned)splits), dim3(512), (size_t)zi_row_lds_bytes<KC, TL>(), st,
+                          D_hat, U, img, lgit, mpad, nztiles, colsum, DV, n, m, K, ngt, per, active);
         }
     });
+}
+
+int zi_sweep(KcTl cfg, float *D_hat, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles,
+             double *colsum, const double *Vn, double *DV, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
+    return zi_sweep_launch<false>(cfg, D_hat, U, V, lgit, mpad, nztiles, colsum, Vn, DV, nullptr, img_scratch, n, m, K, st);
+}
+
+int zi_rate(KcTl cfg, const double *U, const double *V, const float *lgit, int64_t mpad, const uint32_t *nztiles, double *DV,
+            const uint8_t *active, float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
+    return zi_sweep_launch<true>(cfg, nullptr, U, V, lgit, mpad, nztiles, nullptr, V, DV, active, img_scratch, n, m, K, st);
 }
 
 int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch, int64_t n, int64_t m, int K, hipStream_t st) {

@@ -375,9 +375,18 @@ struct FoldinArgs {
     int64_t r, slab_row0;
     int K, Kp, nslab, rpb, it;
     double tol;
+    // ZI (the zero-inflated fold-in, oriana_foldin_update_zi): the rate is a MATRIX -- a2 (r, K) read and written, rate (r, K) =
+    // sum_j d_ij V_hat_jk of the pair that enters the iteration, alpha2 [K], U_hat (r, K) = a1 / a2 out; all in the caller's
+    // row order, like a1.  a2_row is not read.
+    double *a2;
+    const double *rate, *alpha2;
+    double *U_hat;
 };
 
-template <int VEC, int LPR, int NC>
+// ZI: a2_new = max(1e-15, alpha2 + rate[o]), a cell freezes when BOTH |a1_new - a1| <= tol * a1 and |a2_new - a2| <= tol * a2
+// hold in every factor, E[log U] takes logf(f32(a2_new)) of the cell's own rate, and a cell still active also gets a2[o] and
+// U_hat[o] = a1_new / a2_new (the operand of the next oriana_zi_foldin_rate).  The start form writes U_hat from the pair as given.
+template <int VEC, int LPR, int NC, bool ZI = false>
 __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
     constexpr int RPW = 64 / LPR, NW = 4;
     static_assert(LPR >= 8, "lanes_max / lanes_or reduce over groups of at least 8 lanes");
@@ -390,7 +399,7 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
     const int64_t r1 = (r0 + A.rpb < r) ? r0 + A.rpb : r;
     const bool start = A.R == nullptr;
     // the K-vectors, once per work-group: this lane's factors of alpha1 and of log a2
-    double p1[NC][VEC];
+    double p1[NC][VEC], p2[ZI ? NC : 1][VEC];
     float lg[NC][VEC];
     #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -398,7 +407,8 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
         #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             p1[c][v] = (k0 < K && !start) ? A.alpha1[k0 + v] : 1.0;
-            lg[c][v] = k0 < K ? logf((float)A.a2_row[k0 + v]) : 0.0f;
+            if constexpr (ZI) { p2[c][v] = (k0 < K && !start) ? A.alpha2[k0 + v] : 1.0; lg[c][v] = 0.0f; }
+            else lg[c][v] = k0 < K ? logf((float)A.a2_row[k0 + v]) : 0.0f;
         }
     }
     float st_sum = 0.f, st_sq = 0.f, st_cnt = 0.f, st_min = INFINITY, n_still = 0.f;
@@ -407,7 +417,7 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
         const bool inr = row < r1;
         const int64_t orow = inr ? (A.row_index ? (int64_t)A.row_index[row] : row) : 0;
         const bool was = inr && A.active[orow] != 0;
-        double s1[NC][VEC];
+        double s1[NC][VEC], s2[ZI ? NC : 1][VEC];
         float el[NC][VEC];
         bool moved = false;
         #pragma unroll
@@ -415,9 +425,28 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
             const int k0 = (cg + c * LPR) * VEC;
             #pragma unroll
             for (int v = 0; v < VEC; ++v) { el[c][v] = -INFINITY; s1[c][v] = 1.0; }
+            if constexpr (ZI) { _Pragma("unroll") for (int v = 0; v < VEC; ++v) s2[c][v] = 1.0; }
             if (was && k0 < K) {
                 double old[VEC];
                 ld_f64<VEC>(old, A.a1 + orow * K + k0);
+                if constexpr (ZI) {
+                    double old2[VEC];
+                    ld_f64<VEC>(old2, A.a2 + orow * K + k0);
+                    if (start) {
+                        #pragma unroll
+                        for (int v = 0; v < VEC; ++v) s2[c][v] = old2[v];
+                    } else {
+                        double rt[VEC];
+                        ld_f64<VEC>(rt, A.rate + orow * K + k0);
+                        #pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            s2[c][v] = clamp_eps(p2[c][v] + rt[v]);
+                            if (!(fabs(s2[c][v] - old2[v]) <= A.tol * old2[v])) moved = true;
+                        }
+                    }
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) lg[c][v] = logf((float)s2[c][v]);
+                }
                 if (start) {
                     #pragma unroll
                     for (int v = 0; v < VEC; ++v) s1[c][v] = old[v];
@@ -470,6 +499,13 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
                     #pragma unroll
                     for (int v = 0; v < VEC; ++v) els[v] = badi ? el[c][v] : el[c][v] - mx;
                     if (!start) st_f64<VEC>(A.a1 + orow * K + k0, s1[c]);
+                    if constexpr (ZI) {
+                        double e[VEC];
+                        #pragma unroll
+                        for (int v = 0; v < VEC; ++v) e[v] = s1[c][v] / s2[c][v];                   // gamma.py:37-46
+                        if (!start) st_f64<VEC>(A.a2 + orow * K + k0, s2[c]);
+                        st_f64<VEC>(A.U_hat + orow * K + k0, e);
+                    }
                     st_f32<VEC>(A.Elog + orow * K + k0, els);
                     st_f32<VEC>(A.FUn + row * Kp + k0, fu);
                 }
@@ -832,15 +868,26 @@ extern "C" int64_t oriana_foldin_update_blocks(int64_t r) {
     return (r + rpb - 1) / rpb;
 }
 
-template <int VEC>
+template <int VEC, bool ZI>
 static void foldin_launch_lpr(const FoldinArgs &a, int lpr, int64_t nblk, hipStream_t s) {
     const dim3 g((unsigned)nblk), b(256);
     switch (lpr) {
-    case 8: hipLaunchKernelGGL((k_foldin_update<VEC, 8, 1>), g, b, 0, s, a); break;
-    case 16: hipLaunchKernelGGL((k_foldin_update<VEC, 16, 1>), g, b, 0, s, a); break;
-    case 32: hipLaunchKernelGGL((k_foldin_update<VEC, 32, 1>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_foldin_update<VEC, 64, 1>), g, b, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((k_foldin_update<VEC, 8, 1, ZI>), g, b, 0, s, a); break;
+    case 16: hipLaunchKernelGGL((k_foldin_update<VEC, 16, 1, ZI>), g, b, 0, s, a); break;
+    case 32: hipLaunchKernelGGL((k_foldin_update<VEC, 32, 1, ZI>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_foldin_update<VEC, 64, 1, ZI>), g, b, 0, s, a); break;
     }
+}
+
+// the configuration for this K and these pointers (gu_vec_cfg; the element-per-lane instantiation for what it leaves out)
+template <bool ZI>
+static void foldin_launch(const FoldinArgs &a, bool wide_ok, hipStream_t s) {
+    const int64_t nblk = (a.r + a.rpb - 1) / a.rpb;
+    int vec, lpr;
+    if (!gu_vec_cfg(a.K, wide_ok, &vec, &lpr)) hipLaunchKernelGGL((k_foldin_update<1, 64, 4, ZI>), dim3((unsigned)nblk), dim3(256), 0, s, a);
+    else if (vec == 4) foldin_launch_lpr<4, ZI>(a, lpr, nblk, s);
+    else if (vec == 2) foldin_launch_lpr<2, ZI>(a, lpr, nblk, s);
+    else foldin_launch_lpr<1, ZI>(a, lpr, nblk, s);
 }
 
 extern "C" int oriana_foldin_update(double *a1, float *Elog, uint8_t *active, int32_t *froze_at, int32_t *n_active,
@@ -854,16 +901,30 @@ extern "C" int oriana_foldin_update(double *a1, float *Elog, uint8_t *active, in
     if (!a1 || !Elog || !active || !a2_row || !FU_next || !mu_out || !upart) return ORIANA_EINVAL;
     if (R && (!Z || !F || !alpha1 || !froze_at)) return ORIANA_EINVAL;
     FoldinArgs a = {a1, Elog, active, froze_at, R ? n_active : nullptr, alpha1, a2_row, Z, F, R, row_index, FU_next, mu_out, upart,
-                    r, slab_row0, (int)K, (int)Kp, (int)nslab, foldin_rpb(r), (int)it, tol};
-    const int64_t nblk = (r + a.rpb - 1) / a.rpb;
+                    r, slab_row0, (int)K, (int)Kp, (int)nslab, foldin_rpb(r), (int)it, tol, nullptr, nullptr, nullptr, nullptr};
     const bool wide_ok = aligned_to(a1, 16) && aligned_to(Elog, 16) && aligned_to(Z, 16) && aligned_to(F, 16) && aligned_to(R, 16) &&
                          aligned_to(FU_next, 16);
-    hipStream_t s = (hipStream_t)stream;
-    int vec, lpr;
-    if (!gu_vec_cfg(K, wide_ok, &vec, &lpr)) hipLaunchKernelGGL((k_foldin_update<1, 64, 4>), dim3((unsigned)nblk), dim3(256), 0, s, a);
-    else if (vec == 4) foldin_launch_lpr<4>(a, lpr, nblk, s);
-    else if (vec == 2) foldin_launch_lpr<2>(a, lpr, nblk, s);
-    else foldin_launch_lpr<1>(a, lpr, nblk, s);
+    foldin_launch<false>(a, wide_ok, (hipStream_t)stream);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_foldin_update_zi(double *a1, double *a2, double *U_hat, float *Elog, uint8_t *active, int32_t *froze_at,
+                                       int32_t *n_active, const double *alpha1, const double *alpha2, const double *rate,
+                                       const float *Z, const float *F, const float *R, int64_t nslab, int64_t slab_row0,
+                                       const int32_t *row_index, int64_t r, int64_t K, double tol, int64_t it, float *FU_next,
+                                       float *mu_out, float *upart, void *stream) {
+    if (r < 0 || K <= 0 || nslab < 1 || nslab > 65535 || slab_row0 < 0 || it < 0 || it > 0x7fffffffLL || !(tol >= 0.0)) return ORIANA_EINVAL;
+    const int64_t Kp = oriana_kpad(K);
+    if (Kp == 0) return ORIANA_EKRANGE;
+    if (r == 0) return 0;
+    if (!a1 || !a2 || !U_hat || !Elog || !active || !FU_next || !mu_out || !upart) return ORIANA_EINVAL;
+    if (R && (!Z || !F || !alpha1 || !alpha2 || !rate || !froze_at)) return ORIANA_EINVAL;
+    FoldinArgs a = {a1, Elog, active, froze_at, R ? n_active : nullptr, alpha1, nullptr, Z, F, R, row_index, FU_next, mu_out, upart,
+                    r, slab_row0, (int)K, (int)Kp, (int)nslab, foldin_rpb(r), (int)it, tol, a2, rate, alpha2, U_hat};
+    const bool wide_ok = aligned_to(a1, 16) && aligned_to(a2, 16) && aligned_to(U_hat, 16) && aligned_to(rate, 16) && aligned_to(Elog, 16) &&
+                         aligned_to(Z, 16) && aligned_to(F, 16) && aligned_to(R, 16) && aligned_to(FU_next, 16);
+    foldin_launch<true>(a, wide_ok, (hipStream_t)stream);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

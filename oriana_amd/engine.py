@@ -799,6 +799,25 @@ def row_sums_over_k(ws, K):
     return Z[:ct.n]
 
 
+def _fold_in_buffers(ws, n_iter):
+    """What both fold-in loops keep beside the pair: the workspace set up for in-place factor preparation, and (E[log U], Z_i,
+    Z_j, the active bytes, one counter of active cells per iteration)."""
+    ct, K = ws.ct, ws.K
+    n, m, dev = ct.n, ct.m, ct.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    # the cell side of every factor preparation comes from oriana_foldin_update (the fused form of factor_prep_pair), in
+    # place: no kernel reads FU while it is rewritten, so the double buffer of the sweeps is one buffer here
+    ws.prep_blocks = int(_lib.load().oriana_foldin_update_blocks(n))
+    ws.FU_alt = ws.FU
+    ws.mu_u = torch.zeros(n, **f32)
+    ws.upart = torch.zeros(4 * ws.prep_blocks, **f32)
+    lu = torch.empty(n, K, **f32)
+    Zi, Zj = torch.empty(n, K, **f32), torch.empty(max(m, 1), K, **f32)       # (Z_j: the slow path adds into it; never read)
+    active = torch.ones(n, dtype=torch.uint8, device=dev)
+    left = torch.zeros(max(n_iter, 1), dtype=torch.int32, device=dev)        # one counter per iteration: no clearing launch
+    return lu, Zi, Zj, active, left
+
+
 def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5, ws=None):
     """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted pCMF model whose gene side stays as it is: the
     per-cell fixed point of  a1 <- max(1e-15, alpha1 + sum_j x_ij r_ijk),  r_ij. = softmax_k(E[log U]_ik + E[log V]_jk),
@@ -824,17 +843,7 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
         return froze_at, 0, 0
     if ws is None:
         ws = ZWorkspace(ct_new, K)
-    f32 = dict(dtype=torch.float32, device=dev)
-    # the cell side of every factor preparation comes from oriana_foldin_update (the fused form of factor_prep_pair), in
-    # place: no kernel reads FU while it is rewritten, so the double buffer of the sweeps is one buffer here
-    ws.prep_blocks = int(_lib.load().oriana_foldin_update_blocks(n))
-    ws.FU_alt = ws.FU
-    ws.mu_u = torch.zeros(n, **f32)
-    ws.upart = torch.zeros(4 * ws.prep_blocks, **f32)
-    lu = torch.empty(n, K, **f32)
-    Zi, Zj = torch.empty(n, K, **f32), torch.empty(max(m, 1), K, **f32)       # (Z_j: the slow path adds into it; never read)
-    active = torch.ones(n, dtype=torch.uint8, device=dev)
-    left = torch.zeros(max(n_iter, 1), dtype=torch.int32, device=dev)        # one counter per iteration: no clearing launch
+    lu, Zi, Zj, active, left = _fold_in_buffers(ws, n_iter)
     st = stream_ptr()
     call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), None, None, None, ptr(a2_row), None, None, None, 1, 0,
          ptr(ct_new.row_perm), n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
@@ -846,6 +855,77 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
             call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), ptr(froze_at), ptr(left) + 4 * it, ptr(alpha1), ptr(a2_row),
                  ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0, ptr(ct_new.row_perm), n, K, tol, it,
                  ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
+        done = it + 1
+        if done % check_every == 0 or done == n_iter:
+            n_left = int(left[it].item())
+            if n_left == 0:
+                break
+    return froze_at, n_left, done
+
+
+def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter, tol, check_every=5, ws=None, arithmetic=1):
+    """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted ZI-pCMF model whose gene side stays as it is: per
+    cell the fixed point of the pair (a1, a2) under zigap.py:115-136 with V_hat, E[log V] and pi_d frozen --
+      a1' = max(1e-15, alpha1 + sum_j x_ij r_ijk)        (the pCMF row pass: D_hat = f32(1 - 1e-10) = 1 at the non-zeros)
+      a2' = max(1e-15, alpha2 + sum_j d_ij V_hat_jk),    d_ij = 1 at x_ij != 0, the column overrides of zigap.py:133-134, else
+                                                         f32(sigmoid(logit(pi_d_j) - U_hat_i . V_hat_j)),  U_hat = a1 / a2
+    both from the OLD pair (the reference's sweep order: the rate reads the D_hat formed from the U_hat that enters the sweep).
+    `a1`, `a2` (n', K) float64 device tensors: the start, updated in place; log_V_hat (m, K) float32, V_hat (m, K) float64,
+    pi_d [m], alpha1 / alpha2 [K] float64: the model's, only read.
+    Each iteration: the rate buffer is zeroed, the row phase of a sweep runs on a workspace of this call's own (as fold_in),
+    ONE oriana_zi_foldin_rate launch forms sum_j d_ij V_hat_jk from the call's own U_hat over the cells still active -- d is never
+    stored: no (n', m) matrix exists at any point -- and ONE oriana_foldin_update_zi launch updates the pair, U_hat, E[log U],
+    freezes the cells that moved by at most tol in both halves and prepares the next row pass's FU in place.  The per-gene
+    operands are padded to a multiple of 4 genes with inert ones (V_hat row 0, pi_d 0), as the models do; both non-zero masks
+    come from the packed counts, once per call.  Returns (froze_at, cells still active, iterations run) as fold_in."""
+    if ct_new.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    n, m, dev = ct_new.n, ct_new.m, ct_new.device
+    n_iter, check_every, tol = int(n_iter), int(check_every), float(tol)
+    if n_iter < 0 or check_every < 1 or not tol >= 0.0:
+        raise ValueError('fold_in needs n_iter >= 0, check_every >= 1 and tol >= 0')
+    if K > 128:
+        raise ValueError('the zero-inflated fold-in serves K <= 128 (the float32 dense kernels), got K = %d' % K)
+    _check_f32(log_V_hat, (m, K))
+    for name, T, shape in (('a1', a1, (n, K)), ('a2', a2, (n, K)), ('V_hat', V_hat, (m, K)), ('pi_d', pi_d, (m,))):
+        if T.dtype != torch.float64 or tuple(T.shape) != shape or not T.is_contiguous():
+            raise TypeError('%s must be a C-contiguous %s float64 device tensor' % (name, shape))
+    froze_at = torch.full((n,), n_iter, dtype=torch.int32, device=dev)
+    if n == 0:
+        return froze_at, 0, 0
+    if ws is None:
+        ws = ZWorkspace(ct_new, K)
+    lib = _lib.load()
+    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+    mp = (m + 3) // 4 * 4                               # inert genes: no counts, V_hat row 0, pi_d 0 (models/zigap.py _padG)
+    if mp != m:
+        Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
+        Vp[:m].copy_(V_hat)
+        pip[:m].copy_(pi_d)
+    else:
+        Vp, pip = V_hat, pi_d
+    st = stream_ptr()
+    nzmask = torch.zeros(((n + 31) // 32) * mp, dtype=torch.int32, device=dev)
+    call('oriana_nzmask_counts', ptr(nzmask), ct_new.sparse_struct, mp, st)
+    nztiles = torch.zeros(max(int(lib.oriana_nzmask_tiles_words(n, mp)), 4), dtype=torch.int32, device=dev)
+    call('oriana_nzmask_tiles', ptr(nztiles), ptr(nzmask), n, mp, st)
+    scratch = torch.zeros(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), **f32)      # the call's own, never the model's
+    rate, U_hat = torch.empty(n, K, **f64), torch.empty(n, K, **f64)
+    lu, Zi, Zj, active, left = _fold_in_buffers(ws, n_iter)
+    call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), None, None, None, None, None, None, None,
+         None, 1, 0, ptr(ct_new.row_perm), n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
+    n_left, done = n, 0
+    for it in range(n_iter):
+        rate.zero_()
+        ws.fu_pending, ws.fu_source = True, lu.data_ptr()
+        zq_gap(ws, Zi, Zj, lu, log_V_hat, phase='rows', finalize_rows=False)
+        with _span(ws, 'zi_foldin_rate'):
+            call('oriana_zi_foldin_rate', ptr(rate), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(nztiles), ptr(active),
+                 ptr(scratch), int(arithmetic), n, mp, K, st)
+        with _span(ws, 'foldin_update'):
+            call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), ptr(froze_at), ptr(left) + 4 * it,
+                 ptr(alpha1), ptr(alpha2), ptr(rate), ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0,
+                 ptr(ct_new.row_perm), n, K, tol, it, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
         done = it + 1
         if done % check_every == 0 or done == n_iter:
             n_left = int(left[it].item())

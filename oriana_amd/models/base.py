@@ -319,6 +319,29 @@ class FactorModel:
                      'posterior of that unseen cell, and the sparse models evaluate the responsibilities against masked gene '
                      'images; neither fold-in is implemented')
 
+    def _query_counts(self, cmatrix, what='transform()'):
+        """The new cells as CountTiles on the sliced layout (packed here unless they already are), gene count checked first."""
+        if isinstance(cmatrix, engine.CountTiles):
+            ct = cmatrix
+        else:
+            sparse = _is_sparse_input(cmatrix)
+            if sparse:
+                X = cmatrix._sparse if hasattr(cmatrix, '_sparse') else cmatrix
+            else:
+                X = cmatrix.as_array() if hasattr(cmatrix, 'as_array') else cmatrix
+                if not isinstance(X, torch.Tensor):
+                    X = np.asarray(X)
+            if len(X.shape) != 2 or int(X.shape[1]) != self.m:
+                raise ValueError('%s needs an (n\', %d) count matrix: the model was fitted on %d genes, got shape %s'
+                                 % (what, self.m, self.m, tuple(X.shape)))
+            pack = engine.CountTiles.from_scipy if sparse else engine.CountTiles.from_dense
+            ct = pack(X, self.device, dense_density=None)
+        if ct.m != self.m:
+            raise ValueError('%s needs counts over the %d genes the model was fitted on, got %d' % (what, self.m, ct.m))
+        if ct.gd:
+            raise ValueError('%s walks the sliced layout only: pack the new counts without dense_density' % what)
+        return ct
+
     def transform(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False):
         """E[U] of cells the model was not fitted on (GaP); NotImplementedError on the other models."""
         raise NotImplementedError(self._no_transform)

@@ -169,31 +169,6 @@ class GaP(FactorModel):
     # nothing the model or its workspace hold is written ("Folding in new cells").
     transform_unconverged_ = None
 
-    def _query_counts(self, cmatrix):
-        """The new cells as CountTiles on the sliced layout (packed here unless they already are), gene count checked first."""
-        from .base import _is_sparse_input
-        if isinstance(cmatrix, engine.CountTiles):
-            ct = cmatrix
-        else:
-            sparse = _is_sparse_input(cmatrix)
-            if sparse:
-                X = cmatrix._sparse if hasattr(cmatrix, '_sparse') else cmatrix
-            else:
-                X = cmatrix.as_array() if hasattr(cmatrix, 'as_array') else cmatrix
-                if not isinstance(X, torch.Tensor):
-                    import numpy as np
-                    X = np.asarray(X)
-            if len(X.shape) != 2 or int(X.shape[1]) != self.m:
-                raise ValueError('transform() needs an (n\', %d) count matrix: the model was fitted on %d genes, got shape %s'
-                                 % (self.m, self.m, tuple(X.shape)))
-            pack = engine.CountTiles.from_scipy if sparse else engine.CountTiles.from_dense
-            ct = pack(X, self.device, dense_density=None)
-        if ct.m != self.m:
-            raise ValueError('transform() needs counts over the %d genes the model was fitted on, got %d' % (self.m, ct.m))
-        if ct.gd:
-            raise ValueError('transform() walks the sliced layout only: pack the new counts without dense_density')
-        return ct
-
     def transform(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False, check_every=5):
         """Fold new cells into the fitted model: E[U] = a1 / a2_row of `cmatrix` (anything the constructor takes; the same
         genes) as a host (n', K) float64 array, V and the priors as they are.  Each cell iterates its own update until it

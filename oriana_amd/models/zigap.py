@@ -281,6 +281,51 @@ class ZIGaP(_ZIMixin, FactorModel):
         if 'p_d' in st:
             self._refresh_D_hat()
 
+    # ---- folding in new cells ----------------------------------------------------------------------------------------------
+    # With the gene side (V_hat, E[log V], pi_d) and the priors held fixed, the cell side of a ZI sweep (zigap.py:115-136) is a
+    # fixed-point iteration of each new cell's own pair (a1, a2): the rate a2 = alpha2 + sum_j d_ij V_hat_jk reads the cell's own
+    # dropout posterior d_i., which reads U_hat_i = a1 / a2.  engine.fold_in_zi runs it without ever storing d (DESIGN.md,
+    # "Folding in new cells"): nothing the model or its workspace hold is written, no scratch is cached on the model.
+    fold_in_unconverged_ = None
+    _no_transform = ('transform() is defined for pCMF (GaP) only: a new cell of a zero-inflated model carries a dropout posterior of '
+                     'its own; ZIGaP.fold_in() iterates it with the cell (without storing it) -- call fold_in() instead')
+
+    def fold_in(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False, check_every=5):
+        """Fold new cells into the fitted model: E[U] = a1 / a2 of `cmatrix` (anything the constructor takes, or a prebuilt
+        sliced CountTiles; the same genes) as a host (n', K) float64 array; V, pi_d and the priors stay as they are.  Each cell
+        iterates its own update of (a1, a2) until both move by at most tol (relative) in every factor -- then it is frozen and
+        its result does not depend on the other cells -- or `n_iter` is reached; ``fold_in_unconverged_`` counts the cells that
+        never froze.  `init`: (n', K) starting a1 (default alpha1 + rowsum(x) / K); a2 starts at alpha2 + sum_j V_hat, the pCMF
+        rate ("no dropout yet").  return_params=True: (E[U], a1, a2 (n', K), the 0-based iteration each cell froze at -- n_iter
+        for those that did not).  K <= 128.  Under row sharding the call is local to the rank: no collective."""
+        ct = self._query_counts(cmatrix, 'fold_in()')
+        K, dev, nq = self.k, self.device, ct.n
+        if K > 128:
+            raise ValueError('fold_in() serves K <= 128 (the float32 dense kernels of the sweep); the float64 ZI path has no '
+                             'fold-in, got k = %d' % K)
+        alpha1, alpha2 = self.alpha1.tensor, self.alpha2.tensor
+        ws = engine.ZWorkspace(ct, K) if nq > 0 else None
+        if init is not None:
+            a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
+            if tuple(a1.shape) != (nq, K):
+                raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
+            a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
+        elif nq > 0:
+            a1 = alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)
+        else:
+            a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
+        a1 = torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
+        V = self._V_hat.contiguous()
+        a2_row = torch.clamp(torch.nan_to_num(alpha2 + V.sum(dim=0)), min=1e-15)          # zigap.py:116-118 with D_hat = 1
+        a2 = a2_row[None, :].expand(nq, K).contiguous()
+        froze_at, left, _ = engine.fold_in_zi(ct, K, self._log_V_hat, V, self.pi_d.tensor.contiguous(), alpha1, alpha2, a1, a2,
+                                              n_iter, tol, check_every=check_every, ws=ws, arithmetic=self._matrix_arith)
+        self.fold_in_unconverged_ = int(left)
+        E = (a1 / a2).cpu().numpy()
+        if return_params:
+            return E, a1.cpu().numpy(), a2.cpu().numpy(), froze_at.cpu().numpy()
+        return E
+
 
 class SparseGaP(_SparseMixin, FactorModel):
     """Sparse pCMF (reference sparse_gap.py:15-172; the NameError of sparse_gap.py:127 -- a bare

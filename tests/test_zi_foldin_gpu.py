@@ -1,0 +1,431 @@
+# -*- coding: utf-8 -*-
+"""ZIGaP.fold_in() and its three C entries on the GPU against the float64 restatement of tests/zi_foldin_reference.py.
+
+Shapes are those of tests/test_elbo_gpu.py: 805 x 301 -- a partial last cell tile, m % 4 != 0 (so inert genes exist), four
+256-cell work-groups; an all-zero cell, an all-zero gene, a gene expressed everywhere.  K is one per kernel family of the
+rate entry: 20 (bf16 x 3 without tiles), 50 and 100 (tiles, with and without the tail factors), 128 (the float32 instruction).
+The bound on one update is helpers.RTOL, the project's stated bound for variational parameters."""
+import numpy as np
+import pytest
+import torch
+
+import zi_foldin_reference as zr
+from helpers import RTOL, err_colrel
+from test_elbo_gpu import M_COLS, N_ROWS, TINY_ALL, TINY_SOME, _counts, _model, _twin_bound
+from test_transform_gpu import _held_tensors
+
+pytestmark = pytest.mark.gpu
+
+KS = (20, 50, 100, 128)
+ZERO_CELL = 11                    # of _counts
+MP = (M_COLS + 3) // 4 * 4
+DEV = 'cuda'
+
+
+def _fitted(K, sweeps=2):
+    G = _model(_counts(K), K, name='ZIGaP', seed=K)
+    for _ in range(sweeps):
+        G.step()
+    return G
+
+
+def _gene_side(G):
+    st = G.state()
+    return st['log_V_hat'], st['V_hat'], st['pi_d'], st['alpha1'], st['alpha2']
+
+
+def _f64(a):
+    return torch.from_numpy(np.array(a, dtype=np.float64)).to(DEV)          # (a copy: the cached cases are read-only)
+
+
+# ---- 1. the mask straight from the packed counts ------------------------------------------------------------------------------
+
+def _mask_bits(X, mp):
+    """The oriana_nzmask_f32 layout of X != 0: word [(i / 32), j] bit i % 32."""
+    n, m = X.shape
+    nw = (n + 31) // 32
+    bits = np.zeros((nw * 32, mp), dtype=np.uint32)
+    bits[:n, :m] = X != 0
+    return np.bitwise_or.reduce(bits.reshape(nw, 32, mp) << np.arange(32, dtype=np.uint32)[None, :, None], axis=1)
+
+
+def _masks(X, sort_rows=False):
+    from oriana_amd import _lib, engine
+    from oriana_amd._lib import call, ptr, stream_ptr
+    n = X.shape[0]
+    ct = engine.CountTiles.from_dense(X, DEV, sort_rows=sort_rows)
+    mask = torch.zeros(((n + 31) // 32) * MP, dtype=torch.int32, device=DEV)
+    call('oriana_nzmask_counts', ptr(mask), ct.sparse_struct, MP, stream_ptr())
+    tiles = torch.zeros(max(int(_lib.load().oriana_nzmask_tiles_words(n, MP)), 4), dtype=torch.int32, device=DEV)
+    call('oriana_nzmask_tiles', ptr(tiles), ptr(mask), n, MP, stream_ptr())
+    return ct, mask, tiles
+
+
+@pytest.mark.parametrize('sort_rows', [False, True], ids=['rows-as-given', 'rows-sorted'])
+@pytest.mark.parametrize('nq', [N_ROWS, 1, 255])
+def test_mask_from_counts(nq, sort_rows):
+    X = _counts(31)[12:12 + nq] if nq < N_ROWS else _counts(31)
+    ct, mask, _ = _masks(X, sort_rows)
+    assert ct.sort_rows == sort_rows
+    got = mask.cpu().numpy().view(np.uint32).reshape(-1, MP)
+    assert np.array_equal(got, _mask_bits(X, MP))
+
+
+# ---- 2. the rate entry against float64 ----------------------------------------------------------------------------------------
+
+PI_ZERO, PI_ONE = 7, 9            # genes whose pi_d is put at 0 and at 1 (the column overrides of zigap.py:133-134)
+
+
+@pytest.fixture(scope='module')
+def rate_case():
+    """Per K: the query, a U_hat with Lambda = U_hat . V_hat of order 1, the gene side of a fitted model with one pi_d at 0 and one
+    at 1, and d.astype(f32) @ V of the reference -- computed once, only read."""
+    cache = {}
+
+    def get(K):
+        if K not in cache:
+            G = _fitted(K)
+            _, V, pi_d, _, _ = _gene_side(G)
+            pi_d = pi_d.copy()
+            pi_d[PI_ZERO], pi_d[PI_ONE] = 0.0, 1.0
+            X = _counts(K + 50)
+            U = np.random.default_rng(90 + K).gamma(1.0, 1.0, size=(N_ROWS, K))
+            U /= (U @ V.T).mean()
+            d = zr.dropout_f32(X, V, pi_d, U)
+            assert (d[:, PI_ZERO][X[:, PI_ZERO] == 0] == np.float32(1e-10)).all() and (d[:, PI_ONE] == 1).all()
+            assert ((d > 0.01) & (d < 0.99)).mean() > 0.2, 'the case does not exercise the sigmoid'
+            ref = d.astype(np.float64) @ V
+            for a in (U, V, pi_d, ref):               # (X goes through torch.from_numpy in the packer: left writable, never written)
+                a.setflags(write=False)
+            cache[K] = (X, U, V, pi_d, ref)
+        return cache[K]
+    return get
+
+
+def _padded(V, pi_d):
+    K = V.shape[1]
+    Vp, pip = torch.zeros(MP, K, dtype=torch.float64, device=DEV), torch.zeros(MP, dtype=torch.float64, device=DEV)
+    Vp[:M_COLS].copy_(_f64(V))
+    pip[:M_COLS].copy_(_f64(pi_d))
+    return Vp, pip
+
+
+def _scratch(K):
+    from oriana_amd import _lib
+    return torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(MP, K)), dtype=torch.float32, device=DEV)
+
+
+def _rate(X, U, V, pi_d, arithmetic, active=None, DV=None):
+    from oriana_amd._lib import call, ptr, stream_ptr
+    n, K = U.shape
+    _, mask, tiles = _masks(X)
+    Vp, pip = _padded(V, pi_d)
+    Ud = _f64(U)
+    DV = torch.zeros(n, K, dtype=torch.float64, device=DEV) if DV is None else DV
+    call('oriana_zi_foldin_rate', ptr(DV), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(active), ptr(_scratch(K)),
+         arithmetic, n, MP, K, stream_ptr())
+    torch.cuda.synchronize()
+    return DV.cpu().numpy()
+
+
+def _storing(X, U, V, pi_d, arithmetic):
+    """DV_next of oriana_dropout_sweep_fused_tiles on a scratch D_hat, and that D_hat."""
+    from oriana_amd._lib import call, ptr, stream_ptr
+    n, K = U.shape
+    _, mask, tiles = _masks(X)
+    Vp, pip = _padded(V, pi_d)
+    Ud = _f64(U)
+    D = torch.empty(n, MP, dtype=torch.float32, device=DEV)
+    cs = torch.zeros(MP, dtype=torch.float64, device=DEV)
+    DV = torch.zeros(n, K, dtype=torch.float64, device=DEV)
+    call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(cs), ptr(Vp), ptr(DV),
+         ptr(_scratch(K)), arithmetic, n, MP, K, stream_ptr())
+    torch.cuda.synchronize()
+    return DV.cpu().numpy(), D.cpu().numpy()
+
+
+@pytest.mark.parametrize('K,arithmetic', [(20, 1), (50, 1), (50, 0), (100, 1), (128, 1)],
+                         ids=['K20-b16', 'K50-tiles', 'K50-f32', 'K100-tiles', 'K128-f32'])
+def test_rate_against_float64(rate_case, K, arithmetic):
+    X, U, V, pi_d, ref = rate_case(K)
+    got = _rate(X, U, V, pi_d, arithmetic)
+    e = err_colrel(got, ref)
+    stored, D = _storing(X, U, V, pi_d, arithmetic)
+    e2 = err_colrel(got, stored)
+    print('K=%d arithmetic=%d: rate against float64 %.3e (bound %.1e); against the storing entry %.3e (bound 6e-7)'
+          % (K, arithmetic, e, RTOL, e2))
+    assert np.isfinite(got).all()
+    assert e <= RTOL
+    # the header states the storing entry within 3e-7 relative of float64 on rate terms: two such results agree within 6e-7
+    assert e2 <= 6e-7
+
+
+def test_rate_k_range():
+    from oriana_amd import _lib
+    from oriana_amd._lib import ptr, stream_ptr
+    t = torch.zeros(64, dtype=torch.float64, device=DEV)
+    rc = _lib.load().oriana_zi_foldin_rate(ptr(t), ptr(t), ptr(t), ptr(t), ptr(t), None, None, ptr(t), 1, 4, 4, 129, stream_ptr())
+    assert rc == -2                                                 # ORIANA_EKRANGE
+
+
+# ---- 3. inactive cells are skipped --------------------------------------------------------------------------------------------
+
+SENTINEL = 3.0
+
+
+@pytest.mark.parametrize('K', KS)
+def test_rate_skips_inactive_cells(rate_case, K):
+    """Cells 0..255 (a whole 256-cell work-group, two 128-cell ones) and scattered others are inactive: their DV rows keep the
+    sentinel bit for bit, their U_hat rows (NaN here) reach no active row, and the active rows are those of the all-active
+    run up to the order of the float atomics."""
+    X, U, V, pi_d, _ = rate_case(K)
+    full = _rate(X, U, V, pi_d, 1)
+    act = np.ones(N_ROWS, dtype=np.uint8)
+    act[:256] = 0
+    act[[300, 511, 512, 513, 700, 804]] = 0
+    on = act != 0
+    Un = U.copy()
+    Un[~on] = np.nan
+    DV = torch.full((N_ROWS, K), SENTINEL, dtype=torch.float64, device=DEV)
+    got = _rate(X, Un, V, pi_d, 1, active=torch.from_numpy(act).to(DEV), DV=DV)
+    assert np.array_equal(got[~on], np.full((int((~on).sum()), K), SENTINEL)), 'rows of inactive cells were written'
+    e = err_colrel(got[on] - SENTINEL, full[on])
+    print('K=%d: active rows against the all-active run %.3e (bound %.3e)' % (K, e, _twin_bound(N_ROWS, 1)))
+    assert np.isfinite(got).all() and e <= _twin_bound(N_ROWS, 1)
+
+
+# ---- 4. one iteration against float64 -----------------------------------------------------------------------------------------
+
+def _check_one_update(G, Xq, a1_0, what):
+    lv, V, pi_d, al1, al2 = _gene_side(G)
+    s1 = np.maximum(1e-15, a1_0)
+    _, s2 = zr.default_start(Xq, al1, al2, V)
+    r1, r2 = zr.T64(Xq, lv, V, pi_d, al1, al2, s1, s2)
+    E, a1, a2, froze = G.fold_in(Xq, n_iter=1, tol=0, init=a1_0, return_params=True)
+    e1, e2, e3 = err_colrel(a1, r1), err_colrel(a2, r2), err_colrel(E, r1 / r2)
+    print('%s: a1 %.3e a2 %.3e E[U] %.3e (bound %.1e)' % (what, e1, e2, e3, RTOL))
+    assert E.dtype == a1.dtype == a2.dtype == np.float64
+    assert E.shape == a1.shape == a2.shape == a1_0.shape and froze.shape == (a1_0.shape[0],)
+    assert np.isfinite(a1).all() and np.isfinite(a2).all() and np.isfinite(E).all()
+    assert np.array_equal(E, a1 / a2)
+    assert e1 <= RTOL and e2 <= RTOL and e3 <= RTOL
+    return a1, a2
+
+
+@pytest.mark.parametrize('K', KS)
+def test_one_iteration_against_float64(K):
+    G = _fitted(K)
+    Xq = _counts(K + 50)
+    a1_0 = np.random.default_rng(70 + K).gamma(1.0, 1.0, size=(N_ROWS, K))
+    _check_one_update(G, Xq, a1_0, 'K=%d' % K)
+    assert G.fold_in_unconverged_ == N_ROWS
+
+
+def test_shapes_at_the_clamp():
+    """Cells whose start puts two factors, or every factor, at 1e-15 (E[log U] ~ -1e15 there; U_hat ~ 1e-17)."""
+    K = 20
+    G = _fitted(K)
+    Xq = _counts(3)
+    a1_0 = np.random.default_rng(5).gamma(1.0, 1.0, size=(N_ROWS, K))
+    for i in TINY_SOME:
+        a1_0[i, [2, 11]] = 1e-15
+    a1_0[TINY_ALL, :] = 1e-15
+    assert all((Xq[i] != 0).any() for i in TINY_SOME + (TINY_ALL,))
+    a1, a2 = _check_one_update(G, Xq, a1_0, 'clamped starts')
+    assert (a1[TINY_ALL] > 1e-15).any()
+
+
+@pytest.mark.parametrize('nq', [1, 255])
+def test_short_batches(nq):
+    K = 20
+    G = _fitted(K)
+    Xq = _counts(9)[12:12 + nq]
+    a1_0 = np.random.default_rng(6).gamma(1.0, 1.0, size=(nq, K))
+    _check_one_update(G, Xq, a1_0, 'n\' = %d' % nq)
+    E = G.fold_in(Xq, n_iter=3)
+    assert E.shape == (nq, K) and np.isfinite(E).all()
+
+
+def test_unaligned_buffers_take_the_element_kernel():
+    """engine.fold_in_zi on a1 / a2 that are 8- but not 16-byte aligned: the same update within the same bound, nothing written
+    outside them."""
+    from oriana_amd import engine
+    K = 100
+    G = _fitted(K)
+    Xq = _counts(K + 50)
+    lv, V, pi_d, al1, al2 = _gene_side(G)
+    s1 = np.random.default_rng(70 + K).gamma(1.0, 1.0, size=(N_ROWS, K))
+    _, s2 = zr.default_start(Xq, al1, al2, V)
+    r1, r2 = zr.T64(Xq, lv, V, pi_d, al1, al2, s1, s2)
+    ct = engine.CountTiles.from_dense(Xq, G.device)
+    views, bufs = [], []
+    for start in (s1, s2):
+        buf = torch.zeros(N_ROWS * K + 2, dtype=torch.float64, device=G.device)
+        off = 1 if buf.data_ptr() % 16 == 0 else 0
+        v = buf[off:off + N_ROWS * K].view(N_ROWS, K)
+        assert v.data_ptr() % 16 == 8
+        v.copy_(torch.from_numpy(start))
+        views.append(v)
+        bufs.append((buf, off))
+    froze, left, done = engine.fold_in_zi(ct, K, G._log_V_hat, G._V_hat, G.pi_d.tensor, G.alpha1.tensor, G.alpha2.tensor,
+                                          views[0], views[1], 1, 0.0, arithmetic=G._matrix_arith)
+    e1, e2 = err_colrel(views[0].cpu().numpy(), r1), err_colrel(views[1].cpu().numpy(), r2)
+    print('unaligned pair: a1 %.3e a2 %.3e' % (e1, e2))
+    assert done == 1 and e1 <= RTOL and e2 <= RTOL
+    for buf, off in bufs:
+        assert buf[0 if off else -1] == 0 and buf[-1 if off else -2] == 0, 'the update wrote outside its buffer'
+
+
+# ---- 5. convergence and freezing ----------------------------------------------------------------------------------------------
+
+TOL = 1e-4
+PLANTED_ZERO_CELL = 23
+
+
+@pytest.fixture(scope='module')
+def planted():
+    """The planted case of tests/test_zi_foldin_host.py: the float64 ZI fit loaded into a GPU model, and the fresh cells."""
+    import oriana_amd.models as M
+    (X, a1, b1, K), fit, Xq = zr.planted_case(zero_cell=PLANTED_ZERO_CELL)
+    G = M.ZIGaP(np.array(X), k=K, init=(np.array(a1), np.array(b1)))
+    G.load_state({k: np.array(fit[k]) for k in ('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d')})
+    G.update_expectations()
+    return G, np.array(Xq)
+
+
+def test_every_cell_freezes_at_a_fixed_point(planted):
+    G, Xq = planted
+    E, a1, a2, froze = G.fold_in(Xq, n_iter=300, tol=TOL, return_params=True)
+    print('freeze iterations: min %d median %d max %d; unconverged %d' % (froze.min(), np.median(froze), froze.max(),
+                                                                          G.fold_in_unconverged_))
+    assert G.fold_in_unconverged_ == 0 and froze.max() < 300
+    n1, n2 = zr.T64(Xq, *_gene_side(G), a1, a2)
+    res = max(err_colrel(n1, a1), err_colrel(n2, a2))
+    print('residual %.3e (bound %.3e)' % (res, TOL + RTOL))
+    assert res <= TOL + RTOL
+    assert np.unique(froze).size > 1, 'every cell froze at the same iteration'
+    assert np.array_equal(E, a1 / a2)
+    assert not Xq[PLANTED_ZERO_CELL].any() and np.array_equal(a1[PLANTED_ZERO_CELL], np.maximum(1e-15, G.alpha1[:]))
+    # frozen cells are never rewritten: a longer budget changes nothing, bit for bit
+    E2, a1_2, a2_2, froze2 = G.fold_in(Xq, n_iter=400, tol=TOL, return_params=True)
+    assert np.array_equal(a1_2, a1) and np.array_equal(a2_2, a2) and np.array_equal(froze2, froze) and np.array_equal(E2, E)
+    # ... and a cell that does not freeze within the budget is counted and reported at n_iter
+    _, _, _, froze3 = G.fold_in(Xq, n_iter=3, tol=TOL, return_params=True)
+    assert G.fold_in_unconverged_ == int((froze3 == 3).sum()) == int((froze >= 3).sum())
+
+
+# ---- 6. the call leaves the model alone ---------------------------------------------------------------------------------------
+
+def _flags(G):
+    ws = G._ws
+    kept = G._DV_next
+    return (ws.fu_pending, ws.fu_source, ws.FU.data_ptr(), ws.prep_blocks, getattr(G, '_u_stale', None), G._v_sums_in_acc, G._ver,
+            G.n_sweeps, G._pd_sum_fresh, G.n_kept_products, G.p_d.materialised, sorted(G._padbuf),
+            None if kept is None else (kept[0].data_ptr(), kept[1], kept[0].cpu().numpy().tobytes()))
+
+
+def _fold_in_leaves_state_alone(G, Xq, **kw):
+    before, flags = _held_tensors(G), _flags(G)
+    G.fold_in(Xq, **kw)
+    after = _held_tensors(G)
+    assert _flags(G) == flags
+    changed = [k for k in before if after.get(k) != before[k]]
+    assert not changed and before.keys() == after.keys(), 'fold_in() wrote %s' % changed
+
+
+def _three_sweeps(K, with_fold_in):
+    G = _model(_counts(K + 1), K, name='ZIGaP', seed=K + 1)
+    Xq = _counts(K + 2)[:300]
+    for _ in range(3):
+        if with_fold_in:
+            _fold_in_leaves_state_alone(G, Xq, n_iter=3)
+        G.step()
+    if with_fold_in:
+        assert G._DV_next is not None, 'the case does not cover a kept D_hat V product'
+        _fold_in_leaves_state_alone(G, Xq, n_iter=2, tol=0)
+    torch.cuda.synchronize()
+    return G.state(), G.n, G.n_kept_products
+
+
+def test_fold_in_does_not_disturb_the_sweep():
+    K = 50
+    (b, n, kb), (a, _, ka) = _three_sweeps(K, False), _three_sweeps(K, True)
+    assert ka == kb >= 1, 'the sweeps kept no D_hat V product: the case does not cover _DV_next'
+    tol = _twin_bound(n, 3)
+    for k in b:
+        e = err_colrel(a[k], b[k]) if b[k].size else 0.0
+        assert e <= tol, '%s: the run with fold_in() calls is %.3e from the one without (bound %.3e)' % (k, e, tol)
+
+
+# ---- 7. no (n', m) matrix -----------------------------------------------------------------------------------------------------
+
+def test_footprint_stays_below_one_D_hat():
+    import scipy.sparse as sp
+    import oriana_amd.models as M
+    from oriana_amd import engine
+    nq, m, K = 4096, 8192, 50
+    rng = np.random.default_rng(77)
+
+    def draw(n):
+        A = sp.random(n, m, density=0.02, format='csr', random_state=rng, data_rvs=lambda s: rng.poisson(3.0, size=s) + 1.0)
+        return A.astype(np.float64)
+    G = M.ZIGaP(draw(64), k=K, init=(rng.gamma(1.0, 1.0, size=(64, K)), rng.gamma(1.0, 1.0, size=(m, K))))
+    G.step()
+    ct = engine.CountTiles.from_scipy(draw(nq), G.device)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    E = G.fold_in(ct, n_iter=2)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    one_D_hat = nq * ((m + 3) // 4 * 4) * 4
+    print('peak growth across fold_in: %.1f MB; one D_hat: %.1f MB' % (peak / 1e6, one_D_hat / 1e6))
+    assert E.shape == (nq, K) and np.isfinite(E).all()
+    assert peak < one_D_hat
+
+
+# ---- 8. errors and edges ------------------------------------------------------------------------------------------------------
+
+def test_errors():
+    from oriana_amd import engine
+    G = _fitted(20, sweeps=0)
+    with pytest.raises(ValueError, match='genes'):
+        G.fold_in(np.zeros((4, M_COLS + 1)))
+    with pytest.raises(ValueError, match='genes'):
+        G.fold_in(engine.CountTiles.from_dense(_counts(1)[:40, :200], G.device))
+    with pytest.raises(ValueError, match='init'):
+        G.fold_in(_counts(1)[:40], init=np.ones((41, 20)))
+    with pytest.raises(ValueError, match='dense_density'):
+        G.fold_in(engine.CountTiles.from_dense(_counts(1), G.device, dense_density=0.5))
+    with pytest.raises(NotImplementedError, match='pCMF'):
+        G.transform(_counts(3)[:10])
+    assert 'fold_in' in G._no_transform
+    wide = _model(_counts(2)[:300], 129, name='ZIGaP', seed=2)
+    with pytest.raises(ValueError, match='128'):
+        wide.fold_in(_counts(3)[:10])
+    S = _model(_counts(2)[:300], 5, name='SparseZIGaP', seed=2)
+    assert not hasattr(S, 'fold_in')
+    with pytest.raises(NotImplementedError, match='pCMF'):
+        S.transform(_counts(3)[:10])
+
+
+def test_no_cells():
+    G = _fitted(20, sweeps=1)
+    E, a1, a2, froze = G.fold_in(np.zeros((0, M_COLS)), return_params=True)
+    assert E.shape == a1.shape == a2.shape == (0, 20) and froze.shape == (0,) and G.fold_in_unconverged_ == 0
+
+
+def test_input_variants_agree():
+    import scipy.sparse as sp
+    from oriana_amd import engine
+    K = 20
+    G = _fitted(K)
+    Xq = _counts(8)[:300]
+    a1_0 = np.random.default_rng(8).gamma(1.0, 1.0, size=(300, K))
+    base = G.fold_in(Xq, n_iter=4, tol=0, init=a1_0)
+    variants = {'csr': sp.csr_matrix(Xq), 'tensor': torch.from_numpy(Xq).to(G.device),
+                'tiles': engine.CountTiles.from_scipy(sp.csr_matrix(Xq), G.device)}
+    for name, v in variants.items():
+        e = err_colrel(G.fold_in(v, n_iter=4, tol=0, init=a1_0), base)
+        print('%s: %.3e' % (name, e))
+        assert e <= RTOL, name

@@ -6,6 +6,7 @@ Default: 65,536 x 30,000 new cells, K = 100, 90 % zeros (the benchmark's generat
 the gene side of a model fitted on `--fit-rows` cells of the same generator for `--fit-sweeps` sweeps.  Device events
 around whole loops (after a warm-up loop of each form, the two forms alternating, `--reps` times), then one loop of each
 form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
+`--zi`: the zero-inflated fold-in instead (main_zi below).
 
     python tools/transform_bench.py --out profiles/transform_bench.json
 """
@@ -20,8 +21,118 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def main_zi(args):
+    """--zi: one iteration of ZIGaP.fold_in's loop (engine.fold_in_zi), and its rate launch -- oriana_zi_foldin_rate, which never
+    stores the dropout posterior -- against the storing entry (oriana_dropout_sweep_fused_tiles on a scratch D_hat of the query, whose
+    kernels this build compiles instruction for instruction as before the rate entry existed) on the same operands: the two
+    launches alternate, device events around runs of `--iters` launches, `--reps` times, after a warm-up of both.
+
+        python tools/transform_bench.py --zi --cells 16384 --genes 20000 --k 50 --out profiles/zi_foldin_bench_k50.json
+    """
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
+    from oriana_amd import _lib, engine
+    from oriana_amd._lib import call, ptr, stream_ptr
+    from oriana_amd.models import ZIGaP
+    from oriana_amd.singlecell import SyntheticCounts
+    dev = torch.device('cuda', 0)
+    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
+    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev, dense_density=None)
+    a1, b1 = gen.initial_shapes()
+    model = ZIGaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    del a1, b1
+    model.fit(args.fit_sweeps)
+    torch.cuda.synchronize()
+    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
+    alpha1, alpha2, lv, V = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat, model._V_hat.contiguous()
+    pi_d, arith = model.pi_d.tensor.contiguous(), model._matrix_arith
+    ws = engine.ZWorkspace(ct, K)
+    s1 = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
+    s2 = torch.clamp(alpha2 + V.sum(0), min=1e-15)[None, :].expand(nq, K).contiguous()
+
+    def loop(timer=None):
+        ws.timer = timer
+        p1, p2 = s1.clone(), s2.clone()
+        engine.fold_in_zi(ct, K, lv, V, pi_d, alpha1, alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=arith)
+        ws.timer = None
+        return p1, p2
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    p1, p2 = loop()                                                  # warm-up
+    t_loop = [timed(loop) for _ in range(args.reps)]
+    timer = engine.KernelTimer(prealloc=8 * args.iters)
+    loop(timer)
+    torch.cuda.synchronize()
+    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+
+    # ---- the rate launch alone, both forms on the operands of the loop's last iteration ---------------------------------------
+    mp = (m + 3) // 4 * 4
+    f64 = dict(dtype=torch.float64, device=dev)
+    Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
+    Vp[:m].copy_(V)
+    pip[:m].copy_(pi_d)
+    U = (p1 / p2).contiguous()
+    st = stream_ptr()
+    lib = _lib.load()
+    mask = torch.zeros(((nq + 31) // 32) * mp, dtype=torch.int32, device=dev)
+    call('oriana_nzmask_counts', ptr(mask), ct.sparse_struct, mp, st)
+    tiles = torch.zeros(max(int(lib.oriana_nzmask_tiles_words(nq, mp)), 4), dtype=torch.int32, device=dev)
+    call('oriana_nzmask_tiles', ptr(tiles), ptr(mask), nq, mp, st)
+    scratch = torch.zeros(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), dtype=torch.float32, device=dev)
+    D = torch.empty(nq, mp, dtype=torch.float32, device=dev)
+    cs = torch.zeros(mp, **f64)
+    DV_a, DV_b = torch.zeros(nq, K, **f64), torch.zeros(nq, K, **f64)
+
+    def no_store():
+        for _ in range(args.iters):
+            call('oriana_zi_foldin_rate', ptr(DV_a), ptr(U), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), None, ptr(scratch), arith,
+                 nq, mp, K, st)
+
+    def storing():
+        for _ in range(args.iters):
+            call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(U), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(cs), ptr(Vp),
+                 ptr(DV_b), ptr(scratch), arith, nq, mp, K, st)
+    no_store(); storing()                                            # warm-up; DV_a, DV_b hold `iters` sums each
+    torch.cuda.synchronize()
+    rel = float(((DV_a - DV_b).abs() / (DV_b.abs() + DV_b.abs().max(0, keepdim=True).values)).max())
+    t_a, t_b = [], []
+    for _ in range(args.reps):
+        t_a.append(timed(no_store) / args.iters)
+        t_b.append(timed(storing) / args.iters)
+    out = {
+        'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
+        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps, 'arithmetic': arith,
+        'loop_ms_per_iter': round(float(np.median(t_loop)) / args.iters, 4), 'loop_ms': [round(t, 3) for t in t_loop],
+        'loop_launches': launches,
+        'rate_no_store_ms': round(float(np.median(t_a)), 4), 'rate_storing_ms': round(float(np.median(t_b)), 4),
+        'rate_no_store_all_ms': [round(t, 4) for t in t_a], 'rate_storing_all_ms': [round(t, 4) for t in t_b],
+        'D_hat_bytes_not_allocated_by_fold_in': nq * mp * 4,
+        'rate_no_store_vs_storing_colrel': rel,
+        'note': 'rate_*: `iters` back-to-back launches between two device events, the two forms alternating; the storing form '
+                'writes a scratch D_hat of the query and its column sums besides the same DV',
+    }
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out, indent=1) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--zi', action='store_true', help='time ZIGaP.fold_in\'s iteration and its rate launch (see main_zi)')
     ap.add_argument('--cells', type=int, default=65536)
     ap.add_argument('--genes', type=int, default=30000)
     ap.add_argument('--k', type=int, default=100)
@@ -33,6 +144,8 @@ def main():
     ap.add_argument('--chunk-rows', type=int, default=8192)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.zi:
+        return main_zi(args)
 
     import numpy as np
     import torch
