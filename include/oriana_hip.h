@@ -406,6 +406,22 @@ int oriana_dense_elbo(const oriana_dense *d, const float *logU, const float *log
 int oriana_gamma_kl(double *out, const double *s1, const double *s2, int s2_is_row, const double *p1, const double *p2,
                     int64_t r, int64_t K, void *stream);
 
+/* ---- the bound per cell (oriana_amd/models/gap.py: score_samples; engine.cell_bounds) ------------------------
+ * A cell's share of the bound above: sum_j [x_ij log den_ij - lgamma(x_ij + 1)] - sum_k U_hat_ik sum_j V_hat_jk - KL_i.
+ *   oriana_cell_bound_nnz : out2 (n, 2) float64, caller's row order, = { sum_j x_ij log den_ij, sum_j lgamma(x_ij + 1) } per
+ *                           cell over the stored entries of the sliced layout; arguments and per-entry arithmetic of
+ *                           oriana_elbo_nnz (float64 log-sum-exp fall-back included).  One work-group per row block walks
+ *                           its gene tiles in order: a cell's entries are added in a fixed order and every cell's pair is
+ *                           WRITTEN (0, 0 for a cell without entries) -- no atomics, out2 need not be zeroed, reruns are
+ *                           bit-identical.
+ *   oriana_gamma_kl_rows  : out[i] = sum_k KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)), the pieces and arguments of
+ *                           oriana_gamma_kl, one value WRITTEN per row, summed in a fixed order.
+ * Both check their arguments before any HIP call: ORIANA_EINVAL on a missing pointer or K <= 0, 0 on an empty input. */
+int oriana_cell_bound_nnz(const oriana_counts *cm, const float *s_rs, const float *mu_u, const float *mu_v,
+                          const float *logU, const float *logV, int64_t K, double *out2, void *stream);
+int oriana_gamma_kl_rows(double *out, const double *s1, const double *s2, int s2_is_row, const double *p1, const double *p2,
+                         int64_t r, int64_t K, void *stream);
+
 /* ---- stateless drop-ins with the reference's exact signatures (outputs first) ------------------
  * One entry per loop nest, arguments in the reference's order, all matrices dense C-contiguous f32
  * on the device: X, D_hat (n, m); log_U_hat and the row-side output (n, K); log_V_hat, S_tilde, S_hat

@@ -130,6 +130,8 @@ _SIGS = {
     'oriana_elbo_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _I, _P, _P]),
     'oriana_dense_elbo': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _I, _P]),
     'oriana_gamma_kl': (c_int, [_P, _P, _P, c_int, _P, _P, _I, _I, _P]),
+    'oriana_cell_bound_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _I, _P, _P]),
+    'oriana_gamma_kl_rows': (c_int, [_P, _P, _P, c_int, _P, _P, _I, _I, _P]),
     'oriana_dropout_metric': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'oriana_nzmask_f32': (c_int, [_P, _P, _I, _I, _P]),
     'oriana_dropout_fix_nz_ld': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, c_double, _I, _P]),

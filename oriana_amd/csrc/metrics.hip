@@ -159,6 +159,69 @@ __global__ __launch_bounds__(256) void k_elbo_nnz(oriana_counts cm, const float 
     if (threadIdx.x == 0) { atomicAdd(&out[0], a0); atomicAdd(&out[1], a1); }
 }
 
+// out[i] = { sum_j x_ij log den_ij, sum_j lgamma(x_ij + 1) } over the stored entries of cell i (caller's row order): the two
+// sums of k_elbo_nnz per cell (models/gap.py: score_samples), entry for entry the same arithmetic.  One work-group owns a
+// row block and walks its gene tiles in order.  Slot s0 + t of a slice belongs to row sl * 16 + ((t & 63) >> 2) and slice
+// lengths are multiples of 64 (pack.hip: k_pack_fill, slice_offsets), so a thread striding by 256 stays with ONE row per
+// slice: a row's entries are spread over 4 lanes x 4 waves.  The work-group is four such groups of 256 threads, group g taking
+// the slices sl = g, g + 4, .. of every tile (a row belongs to one group: 16 waves per CU where one group alone leaves the
+// float64 log / lgamma chains of a single wave per SIMD exposed).  Each thread adds its entries of a (tile, slice) in slot
+// order, the 4 lanes of a row are combined by a butterfly (both partners form the same sum) and the (wave, row) partial in
+// LDS, which that lane group alone touches, takes the result: tile after tile, a fixed order.  The 4 waves are added at the
+// end and every row of the block is WRITTEN (0 for a cell without entries): no atomics, nothing to zero first, reruns are
+// bit-identical.  (The lane reduction runs per slice, not once at the end: sixteen per-slice accumulators in registers need
+// the slice loop unrolled, sixteen copies of the lgamma / log / log-sum-exp bodies.)
+__global__ __launch_bounds__(1024) void k_cell_bound_nnz(oriana_counts cm, const float *__restrict__ s_rs,
+                                                         const float *__restrict__ mu_u, const float *__restrict__ mu_v,
+                                                         const float *__restrict__ logU, const float *__restrict__ logV,
+                                                         int K, double *__restrict__ out) {
+    __shared__ double sh[2][4][TILE];
+    const int tid = threadIdx.x & 255, grp = threadIdx.x >> 8, w = tid >> 6, rl = (tid & 63) >> 2;
+    const int64_t rb = blockIdx.x;
+    sh[0][grp][tid] = 0.0;
+    sh[1][grp][tid] = 0.0;
+    __syncthreads();
+    for (int64_t cb = 0; cb < cm.ncb; ++cb) {
+        const int64_t t = rb * cm.ncb + cb;
+        const int64_t rbase = cm.roff[t];
+        for (int sl = grp; sl < 16; sl += 4) {
+            const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+            if (s0 == s1) continue;                              // (uniform over the group)
+            const int r = sl * 16 + rl;
+            const int64_t ip = rb * TILE + r;
+            double a0 = 0.0, a1 = 0.0;
+            for (uint32_t slot = s0 + tid; slot < s1; slot += 256) {
+                const oriana_rowrec rec = cm.rowrec[rbase + slot];
+                if (rec.x == 0.f) continue;
+                const float s = s_rs[rbase + slot];
+                const double x = (double)rec.x;
+                const int64_t jp = cb * TILE + rec.col;
+                if (ip >= cm.n || jp >= cm.m) continue;          // (no stored entry lies there: mu_u, mu_v end at n, m)
+                double ld = NAN;
+                if (s > 0.f && s < INFINITY) ld = (double)mu_u[ip] + (double)mu_v[jp] + log(x / (double)s);
+                if (!(fabs(ld) < INFINITY)) {
+                    const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+                    const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+                    ld = logsumexp_f64(logU + i * K, logV + j * K, K);
+                }
+                a0 += x * ld;
+                a1 += lgamma(x + 1.0);
+            }
+            // (a slice's length is a multiple of 64: the lanes of a wave leave the loop together)
+            a0 += __shfl_xor(a0, 1, 64); a0 += __shfl_xor(a0, 2, 64);
+            a1 += __shfl_xor(a1, 1, 64); a1 += __shfl_xor(a1, 2, 64);
+            if ((tid & 3) == 0) { sh[0][w][r] += a0; sh[1][w][r] += a1; }
+        }
+    }
+    __syncthreads();
+    const int64_t ip = rb * TILE + tid;
+    if (grp == 0 && ip < cm.n) {
+        const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+        out[2 * i] = ((sh[0][0][tid] + sh[0][1][tid]) + sh[0][2][tid]) + sh[0][3][tid];
+        out[2 * i + 1] = ((sh[1][0][tid] + sh[1][1][tid]) + sh[1][2][tid]) + sh[1][3][tid];
+    }
+}
+
 }  // namespace oriana
 
 using namespace oriana;
@@ -207,6 +270,18 @@ extern "C" int oriana_elbo_nnz(const oriana_counts *cm, const float *s_rs, const
     if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
     hipLaunchKernelGGL(k_elbo_nnz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, mu_u, mu_v, logU, logV,
                        (int)K, out2);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_cell_bound_nnz(const oriana_counts *cm, const float *s_rs, const float *mu_u, const float *mu_v,
+                                     const float *logU, const float *logV, int64_t K, double *out2, void *stream) {
+    if (!cm || !s_rs || !mu_u || !mu_v || !logU || !logV || !out2 || K <= 0) return ORIANA_EINVAL;
+    if (cm->nrb == 0 || cm->n == 0) return 0;
+    if (cm->nrb < 0 || cm->nrb > 0x7fffffffLL || cm->ncb < 0) return ORIANA_EINVAL;
+    // (a layout without a stored entry is still launched: every cell's pair is written, here as 0)
+    hipLaunchKernelGGL(k_cell_bound_nnz, dim3((unsigned)cm->nrb), dim3(1024), 0, (hipStream_t)stream, *cm, s_rs, mu_u, mu_v, logU,
+                       logV, (int)K, out2);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

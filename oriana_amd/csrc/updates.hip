@@ -649,6 +649,42 @@ __global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, cons
     if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
 }
 
+// out[i] = sum_k KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)): k_gamma_kl per row instead of in total (models/gap.py:
+// score_samples) -- the same five pieces per element, the same K-vector cache.  `lpr` lanes (a power of two, 4 .. 64) share a
+// row: a lane adds its factors k = c, c + lpr, .. in that order, a butterfly over the lane group combines them (both partners
+// form the same sum) and the group's first lane WRITES the row's value: a fixed order, no atomics, nothing to zero first.
+__global__ __launch_bounds__(256) void k_gamma_kl_rows(double *__restrict__ out, const double *__restrict__ s1,
+                                                       const double *__restrict__ s2, int s2_row, const double *__restrict__ p1,
+                                                       const double *__restrict__ p2, int64_t r, int K, int lpr) {
+    extern __shared__ double kc[];                 // [K] p1 | p2 | lgamma(p1) - p1 log p2 | s2 (vector form) | its log
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const double a = p1[k], b = p2[k];
+        kc[k] = a;
+        kc[K + k] = b;
+        kc[2 * K + k] = lgamma_pos(a) - a * log(b);
+        kc[3 * K + k] = s2_row ? s2[k] : 0.0;
+        kc[4 * K + k] = s2_row ? log(s2[k]) : 0.0;
+    }
+    __syncthreads();
+    const int rpb = 256 / lpr, c = threadIdx.x & (lpr - 1);
+    // (g0 is uniform over the work-group: every lane takes part in every butterfly, the groups beyond r with 0)
+    for (int64_t g0 = (int64_t)blockIdx.x * rpb; g0 < r; g0 += (int64_t)gridDim.x * rpb) {
+        const int64_t i = g0 + threadIdx.x / lpr;
+        double acc = 0.0;
+        if (i < r) {
+            for (int k = c; k < K; k += lpr) {
+                const double a = s1[i * K + k];
+                const double b = s2_row ? kc[3 * K + k] : s2[i * K + k];
+                const double lb = s2_row ? kc[4 * K + k] : log(b);
+                const double pa = kc[k], pb = kc[K + k];
+                acc += (a - pa) * digamma_f64(a) - lgamma_pos(a) + kc[2 * K + k] + pa * lb + a * (pb - b) / b;
+            }
+        }
+        for (int o = lpr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (c == 0 && i < r) out[i] = acc;
+    }
+}
+
 enum { OP_DIGAMMA = 0, OP_TRIGAMMA, OP_INVDIGAMMA, OP_SIGMOID, OP_LOGIT };
 template <int OP>
 __global__ void k_map_f64(double *__restrict__ y, const double *__restrict__ x, int64_t len) {
@@ -991,6 +1027,24 @@ extern "C" int oriana_gamma_kl(double *out, const double *s1, const double *s2, 
     if (nblk < 1) nblk = 1;
     hipLaunchKernelGGL(k_gamma_kl, dim3((unsigned)nblk), dim3(256), (size_t)5 * K * sizeof(double), (hipStream_t)stream, out, s1,
                        s2, s2_is_row ? 1 : 0, p1, p2, r, (int)K);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_gamma_kl_rows(double *out, const double *s1, const double *s2, int s2_is_row, const double *p1,
+                                    const double *p2, int64_t r, int64_t K, void *stream) {
+    if (r < 0 || K <= 0 || K > 1024) return ORIANA_EINVAL;
+    if (r == 0) return 0;
+    if (!out || !s1 || !s2 || !p1 || !p2) return ORIANA_EINVAL;
+    int lpr = 4;                                   // the smallest lane group that covers K, a wave at the most
+    while (lpr < 64 && lpr < K) lpr *= 2;
+    const int64_t rpb = 256 / lpr;
+    int64_t nblk = (r + rpb - 1) / rpb;
+    const int64_t cap = 8 * oriana_device_cus();   // (at most eight work-groups per CU, as oriana_gamma_kl)
+    if (nblk > cap) nblk = cap;
+    if (nblk < 1) nblk = 1;
+    hipLaunchKernelGGL(k_gamma_kl_rows, dim3((unsigned)nblk), dim3(256), (size_t)5 * K * sizeof(double), (hipStream_t)stream, out,
+                       s1, s2, s2_is_row ? 1 : 0, p1, p2, r, (int)K, lpr);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

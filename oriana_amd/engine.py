@@ -863,6 +863,58 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
     return froze_at, n_left, done
 
 
+def cell_bounds(ct, K, a1, a2_row, log_U, log_V_hat, sum_v, alpha1, alpha2, ws=None):
+    """Each cell's share of pCMF's collapsed variational bound with the gene side as given: a device (n', 4) float64 tensor
+    [data, lgamma, product, kl] per cell of `ct` (CountTiles, sliced layout), caller's row order --
+      data_i    = sum_{j: x_ij != 0} x_ij logsumexp_k(log_U_ik + log_V_hat_jk)         lgamma_i = sum_{j: x_ij != 0} lgamma(x_ij + 1)
+      product_i = sum_k (a1_ik / a2_row_k) sum_v_k                                    kl_i = sum_k KL(Gamma(a1_ik, a2_row_k) || Gamma(alpha1_k, alpha2_k))
+    and the cell's score is data - lgamma - product - kl.  a1 (n', K) float64, log_U (n', K) float32 (the E[log U] the data
+    term is evaluated at, unshifted), log_V_hat (m, K) float32, a2_row / sum_v / alpha1 / alpha2 [K] float64: all only read.
+    The data term is GaP._elbo_terms' per cell: both factors prepared with their row maxima into buffers of this call's own,
+    one oriana_row_pass that leaves s in the row-side slots, and oriana_cell_bound_nnz, which reads that stream once and
+    writes every cell's two sums in a fixed order (no atomics: two calls agree bit for bit); the Kullback-Leibler term is
+    oriana_gamma_kl_rows.  `ws`: a ZWorkspace over `ct` of the caller's own (its row-pass scratch is overwritten); None
+    makes one."""
+    if ct.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    n, m, dev = ct.n, ct.m, ct.device
+    _check_f32(log_V_hat, (m, K))
+    _check_f32(log_U, (n, K))
+    if a1.dtype != torch.float64 or tuple(a1.shape) != (n, K) or not a1.is_contiguous():
+        raise TypeError('a1 must be a C-contiguous (n\', K) float64 device tensor')
+    for name, v in (('a2_row', a2_row), ('sum_v', sum_v), ('alpha1', alpha1), ('alpha2', alpha2)):
+        if v.dtype != torch.float64 or tuple(v.shape) != (K,) or not v.is_contiguous():
+            raise TypeError('%s must be a contiguous [K] float64 device tensor' % name)
+    out = torch.empty(n, 4, dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    if ws is None:
+        ws = ZWorkspace(ct, K)
+    f32 = dict(dtype=torch.float32, device=dev)
+    FU, FV = torch.zeros(n, ws.Kp, **f32), torch.zeros(max(m, 1), ws.Kp, **f32)
+    mu_u, mu_v = torch.zeros(n, **f32), torch.zeros(max(m, 1), **f32)
+    factor_prep(FU, log_U, mu=mu_u, row_index=ct.row_perm)
+    factor_prep(FV, log_V_hat, mu=mu_v, row_index=ct.col_perm)
+    if ws.s_rs is None:
+        ws.s_rs = torch.zeros(max(ct.rslots, 1), **f32)
+    ws.tile_flag.zero_()
+    st = stream_ptr()
+    with _span(ws, 'row_pass'):
+        call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV), None, ptr(ws.R), ptr(ws.s_cs), None, ptr(ws.s_rs),
+             ptr(ws.tile_flag), K, st)
+    pair = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    with _span(ws, 'cell_bound_nnz'):
+        call('oriana_cell_bound_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(mu_u), ptr(mu_v), ptr(log_U), ptr(log_V_hat), K,
+             ptr(pair), st)
+    kl = torch.empty(n, dtype=torch.float64, device=dev)
+    with _span(ws, 'gamma_kl_rows'):
+        call('oriana_gamma_kl_rows', ptr(kl), ptr(a1), ptr(a2_row), 1, ptr(alpha1), ptr(alpha2), n, K, st)
+    out[:, :2] = pair
+    out[:, 2] = ((a1 / a2_row) * sum_v).sum(dim=1)
+    out[:, 3] = kl
+    return out
+
+
 def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter, tol, check_every=5, ws=None, arithmetic=1):
     """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted ZI-pCMF model whose gene side stays as it is: per
     cell the fixed point of the pair (a1, a2) under zigap.py:115-136 with V_hat, E[log V] and pi_d frozen --

@@ -346,6 +346,20 @@ class FactorModel:
         """E[U] of cells the model was not fitted on (GaP); NotImplementedError on the other models."""
         raise NotImplementedError(self._no_transform)
 
+    # The per-cell bound of held-out cells exists for pCMF only (models/gap.py): it is a cell's share of the bound of elbo(),
+    # reached by the fold-in of transform(), and the other models have no such bound (see _no_elbo above).
+    _no_score = ('score_samples() / score() are defined for pCMF (GaP) only: the score is a cell\'s share of the variational bound '
+                 'of elbo() after the fold-in of transform(), and the zero-inflated and sparse updates of the reference are not '
+                 'coordinate ascent on one stated bound, so there is no such value to evaluate for them')
+
+    def score_samples(self, cmatrix, n_iter=200, tol=1e-4, init=None, check_every=5, return_terms=False):
+        """The per-cell variational bound of cells the model was not fitted on (GaP); NotImplementedError on the other models."""
+        raise NotImplementedError(self._no_score)
+
+    def score(self, cmatrix, **kw):
+        """The mean of score_samples() (GaP); NotImplementedError on the other models."""
+        raise NotImplementedError(self._no_score)
+
     def factors(self):
         """base.py:97-98: (U[:], V[:]) as host arrays."""
         return self.U[:], self.V[:]

@@ -177,6 +177,16 @@ class GaP(FactorModel):
         (default alpha1 + rowsum(x) / K: uniform responsibilities, no RNG).  return_params=True: (E[U], a1, a2_row, the
         0-based iteration each cell froze at -- n_iter for those that did not).  Under row sharding the call is local to the
         rank (V is replicated): no collective."""
+        ct, ws, a1, a2_row, sum_v, froze_at = self._fold_in_cells(cmatrix, n_iter, tol, init, check_every)
+        E = (a1 / a2_row).cpu().numpy()
+        if return_params:
+            return E, a1.cpu().numpy(), a2_row.cpu().numpy(), froze_at.cpu().numpy()
+        return E
+
+    def _fold_in_cells(self, cmatrix, n_iter, tol, init, check_every):
+        """The fold-in of transform() and score_samples(): (the packed cells, the call's workspace -- None for no cells --, the
+        final a1 (n', K), a2_row [K], sum_j V_hat [K] as the sweep reads it, froze_at), all on the device; sets
+        ``transform_unconverged_``."""
         import numpy as np
         ct = self._query_counts(cmatrix)
         K, dev, nq = self.k, self.device, ct.n
@@ -196,10 +206,48 @@ class GaP(FactorModel):
         a1 = torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
         froze_at, left, _ = engine.fold_in(ct, K, self._log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=check_every, ws=ws)
         self.transform_unconverged_ = int(left)
-        E = (a1 / a2_row).cpu().numpy()
-        if return_params:
-            return E, a1.cpu().numpy(), a2_row.cpu().numpy(), froze_at.cpu().numpy()
-        return E
+        return ct, ws, a1, a2_row, sum_v, froze_at
+
+    # ---- scoring held-out cells --------------------------------------------------------------------------------------------
+    # The bound of elbo() is a sum over the cells minus the gene side's KL: with the gene side frozen, cell i contributes
+    #   score_i = sum_{j: x_ij != 0} [x_ij log den_ij - lgamma(x_ij + 1)] - sum_k (a1_ik / a2_row_k) sum_j V_hat_jk - KL_i,
+    # log den_ij = logsumexp_k(lu_ik + E[log V]_jk), lu = float32(psi(a1) - log a2_row) UNSHIFTED (what the cell would carry into
+    # a sweep), KL_i = sum_k KL(Gamma(a1_ik, a2_row_k) || Gamma(alpha1_k, alpha2_k)).  One fold-in iteration is exact coordinate
+    # ascent on score_i (the rate a2_row is already the optimal one), so the value does not decrease along the fold-in beyond
+    # its evaluation error and the float32 cast of lu.  Held-out cells' mean score answers "how many factors?": unlike elbo()
+    # on the training cells it does not keep rising with k ("Scoring held-out cells").
+
+    def score_samples(self, cmatrix, n_iter=200, tol=1e-4, init=None, check_every=5, return_terms=False):
+        """The per-cell variational bound of new cells with the gene side frozen: `cmatrix` is folded in exactly as transform()
+        does (same arguments, same result, ``transform_unconverged_`` set) and each cell's share of the bound of elbo() is
+        evaluated at its final a1: a host (n',) float64 array, higher = better explained.  return_terms=True: a dict with
+        score = data - lgamma - product - kl and those four terms (each (n',)), a1, a2_row, froze_at and log_U_hat, the float32
+        E[log U] = psi(a1) - log a2_row the data term was evaluated at.  The model and its workspace are not written; under row
+        sharding the call is local to the rank."""
+        ct, ws, a1, a2_row, sum_v, froze_at = self._fold_in_cells(cmatrix, n_iter, tol, init, check_every)
+        K, dev, nq = self.k, self.device, ct.n
+        lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
+        if nq > 0:
+            # E[log U] of the final shapes by the Gamma node's own kernel (nodes.Gamma.meanlog): Z = NULL, parameters as they are
+            a2 = a2_row.expand(nq, K).contiguous()
+            call('oriana_gamma_update', ptr(a1), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None,
+                 None, None, None, nq, K, stream_ptr())
+        terms = engine.cell_bounds(ct, K, a1, a2_row, lu, self._log_V_hat, sum_v.contiguous(), self.alpha1.tensor,
+                                   self.alpha2.tensor, ws=ws)
+        t = terms.cpu().numpy()
+        score = t[:, 0] - t[:, 1] - t[:, 2] - t[:, 3]
+        if not return_terms:
+            return score
+        return dict(score=score, data=t[:, 0].copy(), lgamma=t[:, 1].copy(), product=t[:, 2].copy(), kl=t[:, 3].copy(),
+                    a1=a1.cpu().numpy(), a2_row=a2_row.cpu().numpy(), froze_at=froze_at.cpu().numpy(), log_U_hat=lu.cpu().numpy())
+
+    def score(self, cmatrix, **kw):
+        """The mean of score_samples(cmatrix, **kw) as a Python float (nan for no cells): compare it across fits with
+        different k on cells none of them was fitted on."""
+        s = self.score_samples(cmatrix, **kw)
+        if isinstance(s, dict):
+            s = s['score']
+        return float(s.mean()) if s.size else float('nan')
 
     def _init_extra(self):
         if os.environ.get('ORIANA_LAZY_U', '1') != '0':

@@ -6,7 +6,8 @@ Default: 65,536 x 30,000 new cells, K = 100, 90 % zeros (the benchmark's generat
 the gene side of a model fitted on `--fit-rows` cells of the same generator for `--fit-sweeps` sweeps.  Device events
 around whole loops (after a warm-up loop of each form, the two forms alternating, `--reps` times), then one loop of each
 form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
-`--zi`: the zero-inflated fold-in instead (main_zi below).
+`--zi`: the zero-inflated fold-in instead (main_zi below).  `--score`: one engine.cell_bounds call beside one fold-in iteration
+(main_score below).
 
     python tools/transform_bench.py --out profiles/transform_bench.json
 """
@@ -130,9 +131,99 @@ def main_zi(args):
             f.write(json.dumps(out, indent=1) + '\n')
 
 
+def main_score(args):
+    """--score: what scoring adds to a fold-in -- one engine.cell_bounds call (two factor preparations, the row pass that leaves
+    s in the row-side slots, oriana_cell_bound_nnz, oriana_gamma_kl_rows, the float64 product) beside one iteration of
+    engine.fold_in on the same new cells and the same fitted gene side as the default mode.  Device events around the whole
+    call / loop, `--reps` times after a warm-up of both, then one call with per-launch events.
+
+        python tools/transform_bench.py --score --fit-rows 131072 --fit-sweeps 5 --out profiles/score_bench.json
+    """
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
+    from oriana_amd import engine
+    from oriana_amd._lib import call, ptr, stream_ptr
+    from oriana_amd.models import GaP
+    from oriana_amd.singlecell import SyntheticCounts
+    dev = torch.device('cuda', 0)
+    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
+    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
+                                           dense_density=engine.auto_dense_density(args.fit_rows, m, K))
+    a1, b1 = gen.initial_shapes()
+    model = GaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    del a1, b1
+    model.fit(args.fit_sweeps)
+    torch.cuda.synchronize()
+    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
+    alpha1, alpha2, lv = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat
+    sum_v = (model._accV[0] if model._v_sums_in_acc else model._sumV[0]).clone()
+    a2_row = torch.clamp(alpha2 + sum_v, min=1e-15)
+    ws = engine.ZWorkspace(ct, K)
+    start = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
+    a1q = start.clone()
+
+    def loop():
+        a1q.copy_(start)
+        engine.fold_in(ct, K, lv, alpha1, a2_row, a1q, args.iters, 0.0, ws=ws)
+
+    lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
+    a2 = a2_row.expand(nq, K).contiguous()
+
+    def score(timer=None):
+        ws.timer = timer
+        call('oriana_gamma_update', ptr(a1q), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None, None,
+             None, None, nq, K, stream_ptr())
+        t = engine.cell_bounds(ct, K, a1q, a2_row, lu, lv, sum_v, alpha1, alpha2, ws=ws)
+        ws.timer = None
+        return t
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    loop()
+    t0 = score()                                                     # warm-up of both
+    t_l, t_s = [], []
+    for _ in range(args.reps):
+        t_l.append(timed(loop))
+        t_s.append(timed(score))
+    same = bool(torch.equal(score(), t0))                            # (the loop ends at the same a1 every time)
+    timer = engine.KernelTimer(prealloc=16)
+    t = score(timer)
+    torch.cuda.synchronize()
+    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    per_iter, sc = float(np.median(t_l)) / args.iters, float(np.median(t_s))
+    out = {
+        'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
+        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps,
+        'fold_in_ms_per_iter': round(per_iter, 4), 'fold_in_loop_ms': [round(x, 3) for x in t_l],
+        'score_ms': round(sc, 4), 'score_all_ms': [round(x, 3) for x in t_s],
+        'score_over_one_iteration': round(sc / per_iter, 3), 'score_launches': launches,
+        'reruns_bit_identical': same, 'mean_score': float((t[:, 0] - t[:, 1] - t[:, 2] - t[:, 3]).mean()),
+        'note': 'score_ms: device events around E[log U] of the final shapes + engine.cell_bounds (allocations of the call\'s '
+                'own buffers included); score_launches: per-launch events of one further call (the factor preparations, the '
+                'E[log U] launch and the float64 product are not among them)',
+    }
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out, indent=1) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--zi', action='store_true', help='time ZIGaP.fold_in\'s iteration and its rate launch (see main_zi)')
+    ap.add_argument('--score', action='store_true', help='time one engine.cell_bounds call beside a fold-in iteration (see main_score)')
     ap.add_argument('--cells', type=int, default=65536)
     ap.add_argument('--genes', type=int, default=30000)
     ap.add_argument('--k', type=int, default=100)
@@ -146,6 +237,8 @@ def main():
     args = ap.parse_args()
     if args.zi:
         return main_zi(args)
+    if args.score:
+        return main_score(args)
 
     import numpy as np
     import torch
