@@ -652,6 +652,22 @@ int oriana_nzmask_counts(uint32_t *mask, const oriana_counts *cm, int64_t ld, vo
 int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
                           const uint32_t *nztiles, const uint8_t *active, float *scratch, int arithmetic, int64_t n, int64_t m,
                           int64_t K, void *stream);
+/* The dropout term of a held-out cell's bound under a ZI model with the gene side frozen (ZIGaP.fold_in_score_samples,
+ * engine.zi_cell_bounds), the dropout posterior collapsed at its optimum and never stored:
+ *   out[i] = sum_{j < m_real, x_ij != 0} z_ij + sum_{j < m_real, x_ij == 0} softplus(z_ij),   z_ij = logit(pi~_j) - U_i . V_j,
+ *   pi~_j = min(max(pi_d_j, 1e-10), 1 - 1e-10)   (the two override values of zigap.py:133-134: every logit is finite).
+ * The caller adds the cell-independent sum_j log(1 - pi~_j).  U (n, K), V (m, K), pi_d [m] float64; nzmask in the
+ * oriana_nzmask_f32 layout with ld = m (oriana_nzmask_counts).  m counts the inert padding genes [m_real, m) (V row 0, pi_d 0)
+ * too: they are left out of the sums.  K <= 128 (else ORIANA_EKRANGE): the float32 matrix instruction's kernel of the D update
+ * (csrc/dense_f32.hip, k_dropout_sweep) with this epilogue in place of the sigmoid, softplus as max(z, 0) + log1p(exp(-|z|)).
+ * Per tile of 32 genes a cell's values are added in float32, the tiles in float64; the gene axis is cut into S ranges (a
+ * function of n, m and the device's compute units), every range WRITES its partial to scratch and a second launch adds the S
+ * partials in order: no atomics, out [n] need not be zeroed, every out[i] is written, reruns are bit-identical.
+ * scratch: oriana_zi_cell_bound_scratch_doubles(n, m, K) = S n + 32 ceil(m / 64) doubles (the partials, then the float32 logits).
+ * ORIANA_EINVAL on a missing pointer, K <= 0 or m_real outside [0, m]; 0 for n == 0 before any HIP call. */
+int64_t oriana_zi_cell_bound_scratch_doubles(int64_t n, int64_t m, int64_t K);
+int oriana_zi_cell_bound(double *out, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
+                         double *scratch, int64_t n, int64_t m, int64_t m_real, int64_t K, void *stream);
 /* out[m, K] += D_hat^T W[n, K] (zigap.py:124), D_hat streamed once; `out` must be initialised.  arithmetic as above;
  * scratch: oriana_dense_t_scratch_floats(n, K) floats (16-byte aligned; the bf16 operand images of W), may be NULL
  * with ORIANA_MATRIX_F32. */

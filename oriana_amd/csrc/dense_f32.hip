@@ -8,6 +8,8 @@
 //                                rates (zigap.py:116) from the tile of D_hat still in registers -- one 4 n m byte write,
 //                                no read of D_hat.
 //   oriana_dense_t_times_factor_f32   out[m, K] += D_hat^T W[n, K]  (zigap.py:124), D_hat streamed once.
+//   oriana_zi_cell_bound         the dropout term of a held-out cell's bound: the sweep kernel's Lambda^T = V U^T with the epilogue
+//                                z or softplus(z), z = logit(pi~) - Lambda, summed per cell in a fixed order (float32 instruction, K <= 128).
 //
 // Numerics.  v_mfma_f32_32x32x2_f32 is a chain of single-rounding FMAs in k order, round-to-nearest-even
 // (tools/ubench/mfma_f32.hip: bit-identical to a host fmaf() chain): a sum of T positive terms carries an unbiased
@@ -71,7 +73,13 @@ struct SweepLds {
 //   the tile's column sums.
 // RATE (oriana_zi_foldin_rate): DV alone -- the transpose, the D_hat store and the column sums are compiled out; a work-group
 // none of whose 128 cells is active returns at its top, U_hat rows of inactive cells are not read, their DV rows not written.
-template <int NT, bool RATE = false>
+// BOUND (oriana_zi_cell_bound): no second product either -- the epilogue of a tile is g(z) = z at a non-zero count, softplus(z)
+// at a zero, z = lgit - Lambda, with `lgit` the CLAMPED image of k_logit_clamped_f32 (finite; -inf marks a gene that is left out).
+// All 16 accumulator registers of a lane belong to one cell (c = lane & 31; the lane halves hold different genes of it): their
+// float32 sum joins a float64 running sum per tile, the halves meet in one cross-lane step at the end, and the work-group WRITES
+// its range's partial to partial[blockIdx.y * n + cell] (the `colsum` argument) -- no atomics; k_cell_bound_combine adds the
+// ranges in order.
+template <int NT, bool RATE = false, bool BOUND = false>
 __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float *__restrict__ D_hat, const double *__restrict__ U,
                                                        const double *__restrict__ V, const float *__restrict__ lgit,
                                                        const uint32_t *__restrict__ nzmask, double *__restrict__ colsum,
@@ -79,6 +87,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
                                                        int64_t n, int64_t m, int K, int KP2, int64_t j_per_split,
                                                        const uint8_t *__restrict__ active) {
     extern __shared__ float lds[];
+    constexpr bool STORE = !RATE && !BOUND;                      // D_hat and the column sums leave the kernel
     const SweepLds L(KP2, NT);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
     const int64_t i0w = (int64_t)blockIdx.x * 128 + w * 32;
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
             const int kk = sk + 8 * u;
             sreg[u] = V[jc * K + (kk < K ? kk : K - 1)];
         }
-        if (Vn && !same_v) {
+        if (!BOUND && Vn && !same_v) {
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const int kk = sk + 8 * u;
@@ -135,7 +144,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
             const int kk = sk + 8 * u;
             const bool ok = sok && kk < K;
             (kk < KP2 ? vt + kk * 32 : lds + L.dm)[sg] = ok ? (float)sreg[u] : 0.f;
-            if (Vn) v2[sg * L.v2s + kk] = ok ? (float)(same_v ? sreg[u] : nreg[u]) : 0.f;
+            if (!BOUND && Vn) v2[sg * L.v2s + kk] = ok ? (float)(same_v ? sreg[u] : nreg[u]) : 0.f;
         }
     };
     // per gene and wave: {logit(pi_d), the mask word of the wave's 32 cells}; threads 0..127, one (wave, gene) each
@@ -168,6 +177,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
     }
     const bool rowok = i0w + c < n;
     const bool vec_ok = (m & 3) == 0;
+    double bsum = 0.0;                                           // BOUND: the cell's running sum over this lane half's genes
 
     if (jb < je) {
         stage_load(jb);
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
     for (int64_t j0 = jb; j0 < je; j0 += 32) {
         const bool more = j0 + 32 < je;
         { const int64_t jn = more ? j0 + 32 : j0; stage_load(jn); meta_load(jn); }   // (the last tile again: unused)
-        if constexpr (!RATE) { if (j0 > jb) colsum_flush(j0 - 32, par ^ 1); }
+        if constexpr (STORE) { if (j0 > jb) colsum_flush(j0 - 32, par ^ 1); }
         ORIANA_VMEM_FENCE();
         // ---- Lambda^T = V U^T: four steps per turn, the operands of the next turn requested before the matrix
         // instructions of this one (an LDS round trip is longer than one 16-pass instruction)
@@ -232,6 +242,14 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
             const float2 mt = mts[acc_row(v, h)];
             if ((v & 3) == 0) __builtin_amdgcn_sched_barrier(0);     // four entries at a time: bounded register use
             const float x = mt.x - l0[v];
+            if constexpr (BOUND) {
+                // softplus, safe at both ends: exp of a non-positive number, log1p of a number in [0, 1]
+                float g = fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
+                if ((__float_as_uint(mt.y) >> c) & 1u) g = x;    // X != 0: log pi - Lambda
+                if (mt.x == -INFINITY) g = 0.0f;                 // a gene that is left out (inert padding)
+                l0[v] = g;
+                continue;
+            }
             float p = __builtin_amdgcn_rcpf(1.0f + __expf(-x));
             if (mt.x == -INFINITY) p = 1e-10f;                   // pi_d <= 0                         zigap.py:133
             if ((__float_as_uint(mt.y) >> c) & 1u) p = 1.0f;     // X != 0: f32(1 - 1e-10) == 1       zigap.py:135
@@ -241,16 +259,22 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
 #pragma unroll
             for (int v = 0; v < 16; ++v) if (!rowok || acc_row(v, h) >= jrem) l0[v] = 0.f;
         }
-        if constexpr (!RATE) {
+        if constexpr (STORE) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) T[c * TS + acc_row(v, h)] = l0[v];
+        }
+        if constexpr (BOUND) {                                   // 16 genes of the cell in float32, then the float64 carry
+            float t = l0[0];
+#pragma unroll
+            for (int v = 1; v < 16; ++v) t += l0[v];
+            bsum += (double)t;
         }
         __builtin_amdgcn_wave_barrier();
         stage_store(buf ^ 1);
         meta_store(buf ^ 1);
         ORIANA_VMEM_FENCE();
         // ---- D_hat rows out, column sums of the tile
-        if constexpr (!RATE) {
+        if constexpr (STORE) {
             const int gq = (lane & 7) * 4;
             const bool full = vec_ok && jrem == 32;              // uniform: whole 16-byte pieces
             f4v csum = {0.f, 0.f, 0.f, 0.f};
@@ -277,7 +301,7 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
             }
         }
         // ---- DV += D V_next
-        if (Vn) {
+        if (!BOUND && Vn) {
             const float *v2 = lds + L.v2 + buf * 32 * L.v2s + c;
             float bc[NT], bn[NT];
 #pragma unroll
@@ -306,8 +330,12 @@ __global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_dropout_sweep(float 
         buf ^= 1;
         par ^= 1;
     }
-    if constexpr (!RATE) { if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1); }
-    if (Vn && DV) {
+    if constexpr (STORE) { if (jb < je) colsum_flush(jb + ((je - jb - 1) / 32) * 32, par ^ 1); }
+    if constexpr (BOUND) {
+        bsum += __shfl_xor(bsum, 32);                            // the other half of the cell's genes
+        if (h == 0 && rowok) colsum[(int64_t)blockIdx.y * n + i0w + c] = bsum;
+    }
+    if (!BOUND && Vn && DV) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -1047,9 +1075,87 @@ static int launch_dt(double *out, const float *D, const double *W, int64_t n, in
     return launch(k_dt_times_factor_f32<NT, GQ>, dim3((unsigned)jb, (unsigned)splits), dim3(256), 0, st, out, D, W, n, m, K, ips);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// oriana_zi_cell_bound: the dropout term of a held-out cell's bound by k_dropout_sweep<NT, false, true>.
+// logit(pi~) in float32, pi~ = min(max(pi_d, 1e-10), 1 - 1e-10) -- the two override VALUES of zigap.py:133-134 instead of
+// k_logit_f32's +-inf flags: every logit is finite (|.| <= 23.03).  Genes [m_real, m) are the inert padding: -inf = left out.
+__global__ void k_logit_clamped_f32(float *__restrict__ lg, const double *__restrict__ pi_d, int64_t m, int64_t m_real) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const double pt = fmin(fmax(pi_d[j], 1e-10), 1.0 - 1e-10);
+    lg[j] = (j < m_real) ? (float)(log(pt) - log1p(-pt)) : -INFINITY;
+}
+
+// out[i] = the partials of the gene ranges, added in the order of the ranges: every i < n is written
+__global__ void k_cell_bound_combine(double *__restrict__ out, const double *__restrict__ partial, int64_t n, int64_t splits) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int64_t sp = 0; sp < splits; ++sp) s += partial[sp * n + i];
+    out[i] = s;
+}
+
+// Gene ranges of the bound: the entry runs ONCE per call (not once per iteration), so a small batch is cut until the
+// work-groups fill the chip's slots once -- in whole tiles, at least two per range (a range stages the U strip of its own);
+// from 512 row blocks on, one range.
+struct BoundCut { int64_t jps, splits; };
+static BoundCut bound_cut(int64_t n, int64_t m) {
+    const int64_t rb = (n + 127) / 128, slots = 2 * oriana_device_cus();
+    int64_t sp = slots / rb;
+    if (sp > (m + 63) / 64) sp = (m + 63) / 64;
+    if (sp > 65535) sp = 65535;
+    if (sp < 1) sp = 1;
+    int64_t jps = (m + sp - 1) / sp;
+    jps = (jps + 31) / 32 * 32;
+    return BoundCut{jps, (m + jps - 1) / jps};
+}
+static inline int64_t bound_logit_doubles(int64_t m) { return (m + 63) / 64 * 32; }      // m floats, rounded up to 64
+
+template <int NT>
+static int launch_bound(double *partial, const double *U, const double *V, const float *lg, const uint32_t *nzmask, int64_t n,
+                        int64_t m, int K, BoundCut cut, hipStream_t st) {
+    const int KP2 = (K + 1) & ~1;
+    const SweepLds L(KP2, NT);
+    const size_t lds = (size_t)L.total * sizeof(float);
+    const int64_t rb = (n + 127) / 128;
+    if (cut.splits > 65535 || rb > 0x7fffffffLL) return ORIANA_EINVAL;
+    return launch(k_dropout_sweep<NT, false, true>, dim3((unsigned)rb, (unsigned)cut.splits), dim3(256), lds, st, nullptr, U, V, lg,
+                  nzmask, partial, nullptr, nullptr, n, m, K, KP2, cut.jps, nullptr);
+}
+
 }  // namespace oriana
 
 using namespace oriana;
+
+extern "C" int64_t oriana_zi_cell_bound_scratch_doubles(int64_t n, int64_t m, int64_t K) {
+    if (n <= 0 || m <= 0 || K <= 0 || K > 128) return 0;
+    return bound_cut(n, m).splits * n + bound_logit_doubles(m);       // the ranges' partials [splits][n] | the clamped logits
+}
+
+extern "C" int oriana_zi_cell_bound(double *out, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
+                                    double *scratch, int64_t n, int64_t m, int64_t m_real, int64_t K, void *stream) {
+    if (n < 0 || m < 0 || m_real < 0 || m_real > m || K <= 0) return ORIANA_EINVAL;
+    if (K > 128) return ORIANA_EKRANGE;
+    if (n == 0) return 0;
+    if (!out) return ORIANA_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (m == 0) {                                                    // no genes: the empty sum, written
+        if (hipMemsetAsync(out, 0, (size_t)n * sizeof(double), st) != hipSuccess) return -1000 - (int)hipGetLastError();
+        return 0;
+    }
+    if (!U || !V || !pi_d || !nzmask || !scratch) return ORIANA_EINVAL;
+    const BoundCut cut = bound_cut(n, m);
+    double *partial = scratch;
+    float *lg = reinterpret_cast<float *>(scratch + cut.splits * n);
+    hipLaunchKernelGGL(k_logit_clamped_f32, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, lg, pi_d, m, m_real);
+    const int rc = with_variant<1, 2, 3, 4>((int)((oriana_kpad(K) + 31) / 32), [&](auto nt) {
+        return launch_bound<decltype(nt)::value>(partial, U, V, lg, nzmask, n, m, (int)K, cut, st);
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cell_bound_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, partial, n, cut.splits);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int64_t oriana_dropout_sweep_scratch_floats(int64_t m, int64_t K) {
     if (m < 0 || K < 0) return 0;

@@ -863,6 +863,31 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
     return froze_at, n_left, done
 
 
+def _cell_data_terms(ws, K, log_U, log_V_hat):
+    """{sum_j x_ij log den_ij, sum_j lgamma(x_ij + 1)} per cell of ws.ct as a device (n', 2) float64 tensor: both factors prepared
+    with their row maxima into buffers of this call's own, one oriana_row_pass that leaves s in the row-side slots, and
+    oriana_cell_bound_nnz (the data term of cell_bounds and of zi_cell_bounds)."""
+    ct = ws.ct
+    n, m, dev = ct.n, ct.m, ct.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    FU, FV = torch.zeros(n, ws.Kp, **f32), torch.zeros(max(m, 1), ws.Kp, **f32)
+    mu_u, mu_v = torch.zeros(n, **f32), torch.zeros(max(m, 1), **f32)
+    factor_prep(FU, log_U, mu=mu_u, row_index=ct.row_perm)
+    factor_prep(FV, log_V_hat, mu=mu_v, row_index=ct.col_perm)
+    if ws.s_rs is None:
+        ws.s_rs = torch.zeros(max(ct.rslots, 1), **f32)
+    ws.tile_flag.zero_()
+    st = stream_ptr()
+    with _span(ws, 'row_pass'):
+        call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV), None, ptr(ws.R), ptr(ws.s_cs), None, ptr(ws.s_rs),
+             ptr(ws.tile_flag), K, st)
+    pair = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    with _span(ws, 'cell_bound_nnz'):
+        call('oriana_cell_bound_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(mu_u), ptr(mu_v), ptr(log_U), ptr(log_V_hat), K,
+             ptr(pair), st)
+    return pair
+
+
 def cell_bounds(ct, K, a1, a2_row, log_U, log_V_hat, sum_v, alpha1, alpha2, ws=None):
     """Each cell's share of pCMF's collapsed variational bound with the gene side as given: a device (n', 4) float64 tensor
     [data, lgamma, product, kl] per cell of `ct` (CountTiles, sliced layout), caller's row order --
@@ -890,27 +915,69 @@ def cell_bounds(ct, K, a1, a2_row, log_U, log_V_hat, sum_v, alpha1, alpha2, ws=N
         return out
     if ws is None:
         ws = ZWorkspace(ct, K)
-    f32 = dict(dtype=torch.float32, device=dev)
-    FU, FV = torch.zeros(n, ws.Kp, **f32), torch.zeros(max(m, 1), ws.Kp, **f32)
-    mu_u, mu_v = torch.zeros(n, **f32), torch.zeros(max(m, 1), **f32)
-    factor_prep(FU, log_U, mu=mu_u, row_index=ct.row_perm)
-    factor_prep(FV, log_V_hat, mu=mu_v, row_index=ct.col_perm)
-    if ws.s_rs is None:
-        ws.s_rs = torch.zeros(max(ct.rslots, 1), **f32)
-    ws.tile_flag.zero_()
+    pair = _cell_data_terms(ws, K, log_U, log_V_hat)
     st = stream_ptr()
-    with _span(ws, 'row_pass'):
-        call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV), None, ptr(ws.R), ptr(ws.s_cs), None, ptr(ws.s_rs),
-             ptr(ws.tile_flag), K, st)
-    pair = torch.empty(n, 2, dtype=torch.float64, device=dev)
-    with _span(ws, 'cell_bound_nnz'):
-        call('oriana_cell_bound_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(mu_u), ptr(mu_v), ptr(log_U), ptr(log_V_hat), K,
-             ptr(pair), st)
     kl = torch.empty(n, dtype=torch.float64, device=dev)
     with _span(ws, 'gamma_kl_rows'):
         call('oriana_gamma_kl_rows', ptr(kl), ptr(a1), ptr(a2_row), 1, ptr(alpha1), ptr(alpha2), n, K, st)
     out[:, :2] = pair
     out[:, 2] = ((a1 / a2_row) * sum_v).sum(dim=1)
+    out[:, 3] = kl
+    return out
+
+
+PI_D_FLOOR = 1e-10                # the override values of zigap.py:133-134: pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)
+
+
+def zi_cell_bounds(ct, K, a1, a2, log_U, log_V_hat, V_hat, pi_d, alpha1, alpha2, ws=None):
+    """Each cell's share of ZI-pCMF's variational bound with the gene side as given and q(Z), q(d) collapsed at their optima: a
+    device (n', 4) float64 tensor [data, lgamma, dropout, kl] per cell of `ct` (CountTiles, sliced layout), caller's row order --
+      data_i, lgamma_i as cell_bounds;    kl_i = sum_k KL(Gamma(a1_ik, a2_ik) || Gamma(alpha1_k, alpha2_k))
+      dropout_i = sum_j log(1 - pi~_j) + sum_{x_ij != 0} z_ij + sum_{x_ij = 0} softplus(z_ij),
+      z_ij = logit(pi~_j) - (a1_i / a2_i) . V_hat_j,    pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)
+    and the cell's score is data - lgamma + dropout - kl.  a1, a2 (n', K), V_hat (m, K), pi_d [m], alpha1 / alpha2 [K] float64,
+    log_U (n', K) float32 (the E[log U] the data term is evaluated at, unshifted), log_V_hat (m, K) float32: all only read.
+    The dropout term is ONE oriana_zi_cell_bound launch sequence over the query's own non-zero mask (oriana_nzmask_counts, as
+    fold_in_zi builds it) with the per-gene operands padded to a multiple of 4 genes; the cell-independent sum is added here in
+    float64.  No (n', m) matrix exists at any point; every term is written in a fixed order (two calls agree bit for bit).
+    `ws`: a ZWorkspace over `ct` of the caller's own (its row-pass scratch is overwritten); None makes one."""
+    if ct.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    n, m, dev = ct.n, ct.m, ct.device
+    if K > 128:
+        raise ValueError('the zero-inflated bound serves K <= 128 (the float32 dense kernels), got K = %d' % K)
+    _check_f32(log_V_hat, (m, K))
+    _check_f32(log_U, (n, K))
+    for name, T, shape in (('a1', a1, (n, K)), ('a2', a2, (n, K)), ('V_hat', V_hat, (m, K)), ('pi_d', pi_d, (m,)),
+                           ('alpha1', alpha1, (K,)), ('alpha2', alpha2, (K,))):
+        if T.dtype != torch.float64 or tuple(T.shape) != shape or not T.is_contiguous():
+            raise TypeError('%s must be a C-contiguous %s float64 device tensor' % (name, shape))
+    out = torch.empty(n, 4, dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    if ws is None:
+        ws = ZWorkspace(ct, K)
+    out[:, :2] = _cell_data_terms(ws, K, log_U, log_V_hat)
+    f64 = dict(dtype=torch.float64, device=dev)
+    mp = (m + 3) // 4 * 4                               # inert genes: no counts, V_hat row 0, pi_d 0 (models/zigap.py _padG)
+    if mp != m:
+        Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
+        Vp[:m].copy_(V_hat)
+        pip[:m].copy_(pi_d)
+    else:
+        Vp, pip = V_hat, pi_d
+    st = stream_ptr()
+    nzmask = torch.zeros(((n + 31) // 32) * mp, dtype=torch.int32, device=dev)
+    call('oriana_nzmask_counts', ptr(nzmask), ct.sparse_struct, mp, st)
+    U_hat = a1 / a2
+    scratch = torch.empty(max(int(_lib.load().oriana_zi_cell_bound_scratch_doubles(n, mp, K)), 1), **f64)   # the call's own
+    drop = torch.empty(n, **f64)
+    with _span(ws, 'zi_cell_bound'):
+        call('oriana_zi_cell_bound', ptr(drop), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(scratch), n, mp, m, K, st)
+    out[:, 2] = drop + torch.log1p(-torch.clamp(pi_d, PI_D_FLOOR, 1.0 - PI_D_FLOOR)).sum()
+    kl = torch.empty(n, **f64)
+    with _span(ws, 'gamma_kl_rows'):
+        call('oriana_gamma_kl_rows', ptr(kl), ptr(a1), ptr(a2), 0, ptr(alpha1), ptr(alpha2), n, K, st)
     out[:, 3] = kl
     return out
 

@@ -298,11 +298,20 @@ class ZIGaP(_ZIMixin, FactorModel):
         never froze.  `init`: (n', K) starting a1 (default alpha1 + rowsum(x) / K); a2 starts at alpha2 + sum_j V_hat, the pCMF
         rate ("no dropout yet").  return_params=True: (E[U], a1, a2 (n', K), the 0-based iteration each cell froze at -- n_iter
         for those that did not).  K <= 128.  Under row sharding the call is local to the rank: no collective."""
-        ct = self._query_counts(cmatrix, 'fold_in()')
+        ct, ws, a1, a2, froze_at = self._fold_in_pairs(cmatrix, n_iter, tol, init, check_every, 'fold_in()')
+        E = (a1 / a2).cpu().numpy()
+        if return_params:
+            return E, a1.cpu().numpy(), a2.cpu().numpy(), froze_at.cpu().numpy()
+        return E
+
+    def _fold_in_pairs(self, cmatrix, n_iter, tol, init, check_every, what):
+        """The fold-in of fold_in() and fold_in_score_samples(): (the packed cells, the call's workspace -- None for no cells --,
+        the final a1, a2 (n', K), froze_at), all on the device; sets ``fold_in_unconverged_``."""
+        ct = self._query_counts(cmatrix, what)
         K, dev, nq = self.k, self.device, ct.n
         if K > 128:
-            raise ValueError('fold_in() serves K <= 128 (the float32 dense kernels of the sweep); the float64 ZI path has no '
-                             'fold-in, got k = %d' % K)
+            raise ValueError('%s serves K <= 128 (the float32 dense kernels of the sweep); the float64 ZI path has no '
+                             'fold-in, got k = %d' % (what, K))
         alpha1, alpha2 = self.alpha1.tensor, self.alpha2.tensor
         ws = engine.ZWorkspace(ct, K) if nq > 0 else None
         if init is not None:
@@ -321,10 +330,53 @@ class ZIGaP(_ZIMixin, FactorModel):
         froze_at, left, _ = engine.fold_in_zi(ct, K, self._log_V_hat, V, self.pi_d.tensor.contiguous(), alpha1, alpha2, a1, a2,
                                               n_iter, tol, check_every=check_every, ws=ws, arithmetic=self._matrix_arith)
         self.fold_in_unconverged_ = int(left)
-        E = (a1 / a2).cpu().numpy()
-        if return_params:
-            return E, a1.cpu().numpy(), a2.cpu().numpy(), froze_at.cpu().numpy()
-        return E
+        return ct, ws, a1, a2, froze_at
+
+    # ---- scoring held-out cells --------------------------------------------------------------------------------------------
+    # elbo() and score_samples() stay undefined here: the training SWEEP is not coordinate ascent on one stated bound (base.py).
+    # A new cell with the gene side frozen is another matter: the map of fold_in() takes q(Z_i.) and q(d_i.) at their optimum for
+    # the pair that enters and moves (a1_i, a2_i) to their joint optimum under those, so the cell's bound with q(Z) and q(d)
+    # collapsed,
+    #   score_i = sum_{x_ij != 0} [x_ij log den_ij - lgamma(x_ij + 1)] + dropout_i - KL_i,
+    #   dropout_i = sum_j log(1 - pi~_j) + sum_{x_ij != 0} z_ij + sum_{x_ij = 0} softplus(z_ij),  z_ij = logit(pi~_j) - U_hat_i . V_hat_j,
+    # does not decrease along the fold-in beyond its evaluation error and the map's own float32 casts of E[log U] and d; the
+    # D_hat[i, k] index never touches the cell side ("Scoring held-out cells, ZI-pCMF").  pi~ = pi_d clipped to the two
+    # override values [1e-10, 1 - 1e-10] of zigap.py:133-134; with every pi~ -> 1 the value is GaP.score_samples' at the same pair.
+    _no_score = ('score_samples() / score() are defined for pCMF (GaP) only: the zero-inflated SWEEP of the reference is not '
+                 'coordinate ascent on one stated bound, so the training cells have no such value.  Held-out cells do: '
+                 'ZIGaP.fold_in_score_samples() / fold_in_score() fold them in as fold_in() does and evaluate each cell\'s bound')
+
+    def fold_in_score_samples(self, cmatrix, n_iter=200, tol=1e-4, init=None, check_every=5, return_terms=False):
+        """The per-cell variational bound of new cells with the gene side frozen: `cmatrix` is folded in exactly as fold_in()
+        does (same arguments, same result, ``fold_in_unconverged_`` set) and each cell's bound, its responsibilities and its
+        dropout posterior at their optima, is evaluated at its final pair: a host (n',) float64 array, higher = better explained;
+        comparable with GaP.score_samples() on the same cells.  return_terms=True: a dict with score = data - lgamma + dropout - kl
+        and those four terms (each (n',)), a1, a2 (n', K), froze_at and log_U_hat, the float32 E[log U] = psi(a1) - log a2 the
+        data term was evaluated at.  K <= 128.  The model and its workspace are not written; under row sharding the call is
+        local to the rank."""
+        ct, ws, a1, a2, froze_at = self._fold_in_pairs(cmatrix, n_iter, tol, init, check_every, 'fold_in_score_samples()')
+        K, dev, nq = self.k, self.device, ct.n
+        lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
+        if nq > 0:
+            # E[log U] of the final pair by the Gamma node's own kernel (nodes.Gamma.meanlog): Z = NULL, parameters as they are
+            call('oriana_gamma_update', ptr(a1), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None,
+                 None, None, None, nq, K, stream_ptr())
+        terms = engine.zi_cell_bounds(ct, K, a1, a2, lu, self._log_V_hat, self._V_hat.contiguous(), self.pi_d.tensor.contiguous(),
+                                      self.alpha1.tensor, self.alpha2.tensor, ws=ws)
+        t = terms.cpu().numpy()
+        score = t[:, 0] - t[:, 1] + t[:, 2] - t[:, 3]
+        if not return_terms:
+            return score
+        return dict(score=score, data=t[:, 0].copy(), lgamma=t[:, 1].copy(), dropout=t[:, 2].copy(), kl=t[:, 3].copy(),
+                    a1=a1.cpu().numpy(), a2=a2.cpu().numpy(), froze_at=froze_at.cpu().numpy(), log_U_hat=lu.cpu().numpy())
+
+    def fold_in_score(self, cmatrix, **kw):
+        """The mean of fold_in_score_samples(cmatrix, **kw) as a Python float (nan for no cells): compare it across ZI fits with
+        different k, or with GaP.score() of a pCMF fit, on cells none of them was fitted on."""
+        s = self.fold_in_score_samples(cmatrix, **kw)
+        if isinstance(s, dict):
+            s = s['score']
+        return float(s.mean()) if s.size else float('nan')
 
 
 class SparseGaP(_SparseMixin, FactorModel):

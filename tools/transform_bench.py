@@ -7,7 +7,7 @@ the gene side of a model fitted on `--fit-rows` cells of the same generator for 
 around whole loops (after a warm-up loop of each form, the two forms alternating, `--reps` times), then one loop of each
 form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
 `--zi`: the zero-inflated fold-in instead (main_zi below).  `--score`: one engine.cell_bounds call beside one fold-in iteration
-(main_score below).
+(main_score below).  `--zi --score`: one engine.zi_cell_bounds call beside one ZI fold-in iteration (main_zi_score below).
 
     python tools/transform_bench.py --out profiles/transform_bench.json
 """
@@ -131,6 +131,100 @@ def main_zi(args):
             f.write(json.dumps(out, indent=1) + '\n')
 
 
+def main_zi_score(args):
+    """--zi --score: what scoring adds to a ZI fold-in -- E[log U] of the final pair + one engine.zi_cell_bounds call (the data
+    path of --score, the query's non-zero mask, oriana_zi_cell_bound, oriana_gamma_kl_rows) beside one iteration of
+    engine.fold_in_zi and its rate launch, on the operands of --zi.  Device events around the whole call / loop, `--reps` times
+    after a warm-up of both, then one call and one loop with per-launch events.
+
+        python tools/transform_bench.py --zi --score --cells 16384 --genes 20000 --k 50 --fit-rows 16384 --fit-sweeps 3 --iters 10
+    """
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
+    from oriana_amd import engine
+    from oriana_amd._lib import call, ptr, stream_ptr
+    from oriana_amd.models import ZIGaP
+    from oriana_amd.singlecell import SyntheticCounts
+    dev = torch.device('cuda', 0)
+    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
+    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev, dense_density=None)
+    a1, b1 = gen.initial_shapes()
+    model = ZIGaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    del a1, b1
+    model.fit(args.fit_sweeps)
+    torch.cuda.synchronize()
+    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
+    alpha1, alpha2, lv, V = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat, model._V_hat.contiguous()
+    pi_d, arith = model.pi_d.tensor.contiguous(), model._matrix_arith
+    ws = engine.ZWorkspace(ct, K)
+    s1 = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
+    s2 = torch.clamp(alpha2 + V.sum(0), min=1e-15)[None, :].expand(nq, K).contiguous()
+    p1, p2 = s1.clone(), s2.clone()
+
+    def loop(timer=None):
+        ws.timer = timer
+        p1.copy_(s1)
+        p2.copy_(s2)
+        engine.fold_in_zi(ct, K, lv, V, pi_d, alpha1, alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=arith)
+        ws.timer = None
+
+    lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
+
+    def score(timer=None):
+        ws.timer = timer
+        call('oriana_gamma_update', ptr(p1), ptr(p2), ptr(torch.empty_like(p2)), ptr(lu), None, None, None, None, None, None, None,
+             None, None, nq, K, stream_ptr())
+        t = engine.zi_cell_bounds(ct, K, p1, p2, lu, lv, V, pi_d, alpha1, alpha2, ws=ws)
+        ws.timer = None
+        return t
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    loop()
+    t0 = score()                                                     # warm-up of both
+    t_l, t_s = [], []
+    for _ in range(args.reps):
+        t_l.append(timed(loop))
+        t_s.append(timed(score))
+    same = bool(torch.equal(score(), t0))                            # (within one process the loop ends at one pair or reorders atomics)
+    timer = engine.KernelTimer(prealloc=16)
+    t = score(timer)
+    torch.cuda.synchronize()
+    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    timer = engine.KernelTimer(prealloc=8 * args.iters)
+    loop(timer)
+    torch.cuda.synchronize()
+    loop_launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    per_iter, sc = float(np.median(t_l)) / args.iters, float(np.median(t_s))
+    out = {
+        'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
+        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps, 'arithmetic': arith,
+        'fold_in_ms_per_iter': round(per_iter, 4), 'fold_in_loop_ms': [round(x, 3) for x in t_l],
+        'score_ms': round(sc, 4), 'score_all_ms': [round(x, 3) for x in t_s],
+        'score_over_one_iteration': round(sc / per_iter, 3), 'score_launches': launches, 'loop_launches': loop_launches,
+        'reruns_bit_identical': same, 'mean_score': float((t[:, 0] - t[:, 1] + t[:, 2] - t[:, 3]).mean()),
+        'note': 'score_ms: device events around E[log U] of the final pair + engine.zi_cell_bounds (the mask from the packed counts '
+                'and the allocations of the call\'s own buffers included); zi_cell_bound in score_launches: the logit, sweep and '
+                'combine launches of the entry together; zi_foldin_rate in loop_launches: the rate launch of an iteration',
+    }
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out, indent=1) + '\n')
+
+
 def main_score(args):
     """--score: what scoring adds to a fold-in -- one engine.cell_bounds call (two factor preparations, the row pass that leaves
     s in the row-side slots, oriana_cell_bound_nnz, oriana_gamma_kl_rows, the float64 product) beside one iteration of
@@ -235,6 +329,8 @@ def main():
     ap.add_argument('--chunk-rows', type=int, default=8192)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.zi and args.score:
+        return main_zi_score(args)
     if args.zi:
         return main_zi(args)
     if args.score:
