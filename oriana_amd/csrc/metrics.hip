@@ -119,11 +119,29 @@ __global__ __launch_bounds__(256) void k_metric_nnz(oriana_counts cm, const floa
     }
 }
 
+// One stored entry of the data term, count x != 0 at the packed position (ip, jp), s its row-pass value: a0 += x log den,
+// a1 += lgamma(x + 1).  log den_ij = mu_u[i] + mu_v[j] + log(x / s); what the shifted form could not represent (NaN sentinel or
+// 0 in s, a rejected row's NaN maximum) is a float64 log-sum-exp over the K factors.  THE arithmetic of k_elbo_nnz and
+// k_cell_bound_nnz: the sum over the cells of the second is the first up to the order of additions.
+__device__ __forceinline__ void bound_entry(const oriana_counts &cm, const float s, const double x, const int64_t ip,
+                                            const int64_t jp, const float *mu_u, const float *mu_v, const float *logU,
+                                            const float *logV, int K, double &a0, double &a1) {
+    if (ip >= cm.n || jp >= cm.m) return;                    // (no stored entry lies there: mu_u, mu_v end at n, m)
+    double ld = NAN;
+    if (s > 0.f && s < INFINITY) ld = (double)mu_u[ip] + (double)mu_v[jp] + log(x / (double)s);
+    if (!(fabs(ld) < INFINITY)) {
+        const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+        const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+        ld = logsumexp_f64(logU + i * K, logV + j * K, K);
+    }
+    a0 += x * ld;
+    a1 += lgamma(x + 1.0);
+}
+
 // out[0] += sum x log den, out[1] += sum lgamma(x + 1) over the stored entries: the data term of the variational bound
 // (models/gap.py: elbo).  log den_ij = log sum_k exp(lu_ik + lv_jk) = mu_u[i] + mu_v[j] + log(x / s), s from the row pass
-// over the shifted factors exp(l - mu) of oriana_factor_prep (mu_u, mu_v: its row maxima, packed order).  Entries the
-// shifted form could not represent (NaN sentinel or 0 in s, a rejected row's NaN maximum) are a float64 log-sum-exp over
-// the K factors here: the bound lives in the log domain and stays finite where den itself underflows.
+// over the shifted factors exp(l - mu) of oriana_factor_prep (mu_u, mu_v: its row maxima, packed order); per entry
+// bound_entry: the bound lives in the log domain and stays finite where den itself underflows.
 __global__ __launch_bounds__(256) void k_elbo_nnz(oriana_counts cm, const float *__restrict__ s_rs,
                                                   const float *__restrict__ mu_u, const float *__restrict__ mu_v,
                                                   const float *__restrict__ logU, const float *__restrict__ logV,
@@ -138,20 +156,8 @@ __global__ __launch_bounds__(256) void k_elbo_nnz(oriana_counts cm, const float 
         for (uint32_t slot = s0 + threadIdx.x; slot < s1; slot += 256) {
             const oriana_rowrec rec = cm.rowrec[rbase + slot];
             if (rec.x == 0.f) continue;
-            const float s = s_rs[rbase + slot];
-            const double x = (double)rec.x;
-            const int64_t ip = rb * TILE + sl * 16 + (int)(((slot - s0) & 63u) >> 2);
-            const int64_t jp = cb * TILE + rec.col;
-            if (ip >= cm.n || jp >= cm.m) continue;          // (no stored entry lies there: mu_u, mu_v end at n, m)
-            double ld = NAN;
-            if (s > 0.f && s < INFINITY) ld = (double)mu_u[ip] + (double)mu_v[jp] + log(x / (double)s);
-            if (!(fabs(ld) < INFINITY)) {
-                const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
-                const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
-                ld = logsumexp_f64(logU + i * K, logV + j * K, K);
-            }
-            a0 += x * ld;
-            a1 += lgamma(x + 1.0);
+            bound_entry(cm, s_rs[rbase + slot], (double)rec.x, rb * TILE + sl * 16 + (int)(((slot - s0) & 63u) >> 2),
+                        cb * TILE + rec.col, mu_u, mu_v, logU, logV, K, a0, a1);
         }
     }
     a0 = block_sum(a0, sh);
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void k_elbo_nnz(oriana_counts cm, const float 
 }
 
 // out[i] = { sum_j x_ij log den_ij, sum_j lgamma(x_ij + 1) } over the stored entries of cell i (caller's row order): the two
-// sums of k_elbo_nnz per cell (models/gap.py: score_samples), entry for entry the same arithmetic.  One work-group owns a
+// sums of k_elbo_nnz per cell (models/gap.py: score_samples), entry for entry by bound_entry.  One work-group owns a
 // row block and walks its gene tiles in order.  Slot s0 + t of a slice belongs to row sl * 16 + ((t & 63) >> 2) and slice
 // lengths are multiples of 64 (pack.hip: k_pack_fill, slice_offsets), so a thread striding by 256 stays with ONE row per
 // slice: a row's entries are spread over 4 lanes x 4 waves.  The work-group is four such groups of 256 threads, group g taking
@@ -193,19 +199,7 @@ __global__ __launch_bounds__(1024) void k_cell_bound_nnz(oriana_counts cm, const
             for (uint32_t slot = s0 + tid; slot < s1; slot += 256) {
                 const oriana_rowrec rec = cm.rowrec[rbase + slot];
                 if (rec.x == 0.f) continue;
-                const float s = s_rs[rbase + slot];
-                const double x = (double)rec.x;
-                const int64_t jp = cb * TILE + rec.col;
-                if (ip >= cm.n || jp >= cm.m) continue;          // (no stored entry lies there: mu_u, mu_v end at n, m)
-                double ld = NAN;
-                if (s > 0.f && s < INFINITY) ld = (double)mu_u[ip] + (double)mu_v[jp] + log(x / (double)s);
-                if (!(fabs(ld) < INFINITY)) {
-                    const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
-                    const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
-                    ld = logsumexp_f64(logU + i * K, logV + j * K, K);
-                }
-                a0 += x * ld;
-                a1 += lgamma(x + 1.0);
+                bound_entry(cm, s_rs[rbase + slot], (double)rec.x, ip, cb * TILE + rec.col, mu_u, mu_v, logU, logV, K, a0, a1);
             }
             // (a slice's length is a multiple of 64: the lanes of a wave leave the loop together)
             a0 += __shfl_xor(a0, 1, 64); a0 += __shfl_xor(a0, 2, 64);

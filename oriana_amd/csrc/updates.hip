@@ -615,15 +615,10 @@ __device__ __forceinline__ double lgamma_pos(double x) {
     return lgamma(x);
 }
 
-// out[0] += sum_{i,k} KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)), shape / rate, float64:
-//   (s1 - p1) psi(s1) - lgamma(s1) + lgamma(p1) + p1 (log s2 - log p2) + s1 (p2 - s2) / s2
-// s2_row != 0: s2 is a K-vector, the same rate in every row (pCMF's cell side, oriana_gamma_update_finalize_lazy).
-// Grid-stride over the r K elements; the per-factor constants in LDS (5 K doubles); one atomic per work-group.
-__global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, const double *__restrict__ s1,
-                                                  const double *__restrict__ s2, int s2_row, const double *__restrict__ p1,
-                                                  const double *__restrict__ p2, int64_t r, int K) {
-    extern __shared__ double kc[];                 // [K] p1 | p2 | lgamma(p1) - p1 log p2 | s2 (vector form) | its log
-    __shared__ double red[4];
+// The per-factor constants of the Kullback-Leibler kernels, the launch's dynamic LDS (5 K doubles), [K] each: p1 | p2 |
+// lgamma(p1) - p1 log p2 | s2 (vector form, s2_row != 0) | its log.  The 256 threads fill it; the caller's barrier follows.
+extern __shared__ double kc[];
+__device__ __forceinline__ void gamma_kl_fill(const double *s2, int s2_row, const double *p1, const double *p2, int K) {
     for (int k = threadIdx.x; k < K; k += 256) {
         const double a = p1[k], b = p2[k];
         kc[k] = a;
@@ -632,16 +627,32 @@ __global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, cons
         kc[3 * K + k] = s2_row ? s2[k] : 0.0;
         kc[4 * K + k] = s2_row ? log(s2[k]) : 0.0;
     }
+}
+
+// KL(Gamma(s1_e, s2) || Gamma(p1_k, p2_k)) of element e, factor k, shape / rate, float64, five pieces in this order:
+//   (s1 - p1) psi(s1) - lgamma(s1) + lgamma(p1) + p1 (log s2 - log p2) + s1 (p2 - s2) / s2
+__device__ __forceinline__ double gamma_kl_term(const double *s1, const double *s2, int s2_row, int64_t e, int k, int K) {
+    const double a = s1[e];
+    const double b = s2_row ? kc[3 * K + k] : s2[e];
+    const double lb = s2_row ? kc[4 * K + k] : log(b);
+    const double pa = kc[k], pb = kc[K + k];
+    return (a - pa) * digamma_f64(a) - lgamma_pos(a) + kc[2 * K + k] + pa * lb + a * (pb - b) / b;
+}
+
+// out[0] += sum_{i,k} KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)) (gamma_kl_term).
+// s2_row != 0: s2 is a K-vector, the same rate in every row (pCMF's cell side, oriana_gamma_update_finalize_lazy).
+// Grid-stride over the r K elements; the per-factor constants in LDS (5 K doubles); one atomic per work-group.
+__global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, const double *__restrict__ s1,
+                                                  const double *__restrict__ s2, int s2_row, const double *__restrict__ p1,
+                                                  const double *__restrict__ p2, int64_t r, int K) {
+    __shared__ double red[4];
+    gamma_kl_fill(s2, s2_row, p1, p2, K);
     __syncthreads();
     const int64_t tot = r * K;
     double acc = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (int64_t)gridDim.x * 256) {
         const int k = (int)(e % K);
-        const double a = s1[e];
-        const double b = s2_row ? kc[3 * K + k] : s2[e];
-        const double lb = s2_row ? kc[4 * K + k] : log(b);
-        const double pa = kc[k], pb = kc[K + k];
-        acc += (a - pa) * digamma_f64(a) - lgamma_pos(a) + kc[2 * K + k] + pa * lb + a * (pb - b) / b;
+        acc += gamma_kl_term(s1, s2, s2_row, e, k, K);
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -650,21 +661,13 @@ __global__ __launch_bounds__(256) void k_gamma_kl(double *__restrict__ out, cons
 }
 
 // out[i] = sum_k KL(Gamma(s1_ik, s2_ik) || Gamma(p1_k, p2_k)): k_gamma_kl per row instead of in total (models/gap.py:
-// score_samples) -- the same five pieces per element, the same K-vector cache.  `lpr` lanes (a power of two, 4 .. 64) share a
+// score_samples) -- gamma_kl_term per element over the cache of gamma_kl_fill.  `lpr` lanes (a power of two, 4 .. 64) share a
 // row: a lane adds its factors k = c, c + lpr, .. in that order, a butterfly over the lane group combines them (both partners
 // form the same sum) and the group's first lane WRITES the row's value: a fixed order, no atomics, nothing to zero first.
 __global__ __launch_bounds__(256) void k_gamma_kl_rows(double *__restrict__ out, const double *__restrict__ s1,
                                                        const double *__restrict__ s2, int s2_row, const double *__restrict__ p1,
                                                        const double *__restrict__ p2, int64_t r, int K, int lpr) {
-    extern __shared__ double kc[];                 // [K] p1 | p2 | lgamma(p1) - p1 log p2 | s2 (vector form) | its log
-    for (int k = threadIdx.x; k < K; k += 256) {
-        const double a = p1[k], b = p2[k];
-        kc[k] = a;
-        kc[K + k] = b;
-        kc[2 * K + k] = lgamma_pos(a) - a * log(b);
-        kc[3 * K + k] = s2_row ? s2[k] : 0.0;
-        kc[4 * K + k] = s2_row ? log(s2[k]) : 0.0;
-    }
+    gamma_kl_fill(s2, s2_row, p1, p2, K);
     __syncthreads();
     const int rpb = 256 / lpr, c = threadIdx.x & (lpr - 1);
     // (g0 is uniform over the work-group: every lane takes part in every butterfly, the groups beyond r with 0)
@@ -673,11 +676,7 @@ __global__ __launch_bounds__(256) void k_gamma_kl_rows(double *__restrict__ out,
         double acc = 0.0;
         if (i < r) {
             for (int k = c; k < K; k += lpr) {
-                const double a = s1[i * K + k];
-                const double b = s2_row ? kc[3 * K + k] : s2[i * K + k];
-                const double lb = s2_row ? kc[4 * K + k] : log(b);
-                const double pa = kc[k], pb = kc[K + k];
-                acc += (a - pa) * digamma_f64(a) - lgamma_pos(a) + kc[2 * K + k] + pa * lb + a * (pb - b) / b;
+                acc += gamma_kl_term(s1, s2, s2_row, i * K + k, k, K);
             }
         }
         for (int o = lpr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);

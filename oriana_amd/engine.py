@@ -783,276 +783,6 @@ def zq_gap(ws, Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, **kw):
     zq(ws, Z_hat_i, Z_hat_j, None, log_U_hat, log_V_hat, **kw)
 
 
-def row_sums_over_k(ws, K):
-    """rowsum(x) / K per cell and factor, (n, K) float32 in the caller's row order: the row pass against all-ones factors
-    (uniform responsibilities: s = x / K, R = sum_j s), completed as the sweeps complete Z_i."""
-    ct = ws.ct
-    ones_u, ones_v = ws.extra('ONE_U', ct.n), ws.extra('ONE_V', ct.m)
-    ones_u[:, :K] = 1.0
-    ones_v[:, :K] = 1.0
-    Z = torch.zeros(max(ct.n, 1), K, dtype=torch.float32, device=ct.device)
-    ws.tile_flag.zero_()
-    st = stream_ptr()
-    call('oriana_row_pass', ct.sparse_struct, ptr(ones_u), ptr(ones_v), None, ptr(ws.R), ptr(ws.s_cs), None, None,
-         ptr(ws.tile_flag), K, st)
-    call('oriana_finalize_slabs_from', ptr(Z), ptr(ones_u), ptr(ws.R), 1, 0, ptr(ct.row_perm), ct.n, K, st)
-    return Z[:ct.n]
-
-
-def _fold_in_buffers(ws, n_iter):
-    """What both fold-in loops keep beside the pair: the workspace set up for in-place factor preparation, and (E[log U], Z_i,
-    Z_j, the active bytes, one counter of active cells per iteration)."""
-    ct, K = ws.ct, ws.K
-    n, m, dev = ct.n, ct.m, ct.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    # the cell side of every factor preparation comes from oriana_foldin_update (the fused form of factor_prep_pair), in
-    # place: no kernel reads FU while it is rewritten, so the double buffer of the sweeps is one buffer here
-    ws.prep_blocks = int(_lib.load().oriana_foldin_update_blocks(n))
-    ws.FU_alt = ws.FU
-    ws.mu_u = torch.zeros(n, **f32)
-    ws.upart = torch.zeros(4 * ws.prep_blocks, **f32)
-    lu = torch.empty(n, K, **f32)
-    Zi, Zj = torch.empty(n, K, **f32), torch.empty(max(m, 1), K, **f32)       # (Z_j: the slow path adds into it; never read)
-    active = torch.ones(n, dtype=torch.uint8, device=dev)
-    left = torch.zeros(max(n_iter, 1), dtype=torch.int32, device=dev)        # one counter per iteration: no clearing launch
-    return lu, Zi, Zj, active, left
-
-
-def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5, ws=None):
-    """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted pCMF model whose gene side stays as it is: the
-    per-cell fixed point of  a1 <- max(1e-15, alpha1 + sum_j x_ij r_ijk),  r_ij. = softmax_k(E[log U]_ik + E[log V]_jk),
-    E[log U] = psi(a1) - log a2_row  (gap.py:97-102 with sum_j V_hat frozen).  `a1` (n', K) float64 device tensor: the start,
-    updated in place; log_V_hat (m, K) float32, alpha1 / a2_row [K] float64: the model's, only read.
-    Each iteration is the row phase of a sweep on a workspace of this call's own (zq_gap(phase='rows', finalize_rows=False):
-    validity test + gene-side factor from log_V_hat through the new tiles' gene order, row pass, slow path) and ONE launch of
-    oriana_foldin_update, which completes Z_i, updates a1 / E[log U], freezes the cells that moved by at most tol * a1 and
-    prepares the next row pass's FU in place.  The host reads the number of active cells every `check_every` iterations
-    and stops at zero.  Returns (froze_at int32 [n'] -- the 0-based iteration a cell froze at, n_iter if never --, the number
-    of cells still active, the iterations run)."""
-    if ct_new.gd:
-        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
-    n, m, dev = ct_new.n, ct_new.m, ct_new.device
-    n_iter, check_every, tol = int(n_iter), int(check_every), float(tol)
-    if n_iter < 0 or check_every < 1 or not tol >= 0.0:
-        raise ValueError('fold_in needs n_iter >= 0, check_every >= 1 and tol >= 0')
-    _check_f32(log_V_hat, (m, K))
-    if a1.dtype != torch.float64 or tuple(a1.shape) != (n, K) or not a1.is_contiguous():
-        raise TypeError('a1 must be a C-contiguous (n\', K) float64 device tensor')
-    froze_at = torch.full((n,), n_iter, dtype=torch.int32, device=dev)
-    if n == 0:
-        return froze_at, 0, 0
-    if ws is None:
-        ws = ZWorkspace(ct_new, K)
-    lu, Zi, Zj, active, left = _fold_in_buffers(ws, n_iter)
-    st = stream_ptr()
-    call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), None, None, None, ptr(a2_row), None, None, None, 1, 0,
-         ptr(ct_new.row_perm), n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
-    n_left, done = n, 0
-    for it in range(n_iter):
-        ws.fu_pending, ws.fu_source = True, lu.data_ptr()
-        zq_gap(ws, Zi, Zj, lu, log_V_hat, phase='rows', finalize_rows=False)
-        with _span(ws, 'foldin_update'):
-            call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), ptr(froze_at), ptr(left) + 4 * it, ptr(alpha1), ptr(a2_row),
-                 ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0, ptr(ct_new.row_perm), n, K, tol, it,
-                 ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
-        done = it + 1
-        if done % check_every == 0 or done == n_iter:
-            n_left = int(left[it].item())
-            if n_left == 0:
-                break
-    return froze_at, n_left, done
-
-
-def _cell_data_terms(ws, K, log_U, log_V_hat):
-    """{sum_j x_ij log den_ij, sum_j lgamma(x_ij + 1)} per cell of ws.ct as a device (n', 2) float64 tensor: both factors prepared
-    with their row maxima into buffers of this call's own, one oriana_row_pass that leaves s in the row-side slots, and
-    oriana_cell_bound_nnz (the data term of cell_bounds and of zi_cell_bounds)."""
-    ct = ws.ct
-    n, m, dev = ct.n, ct.m, ct.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    FU, FV = torch.zeros(n, ws.Kp, **f32), torch.zeros(max(m, 1), ws.Kp, **f32)
-    mu_u, mu_v = torch.zeros(n, **f32), torch.zeros(max(m, 1), **f32)
-    factor_prep(FU, log_U, mu=mu_u, row_index=ct.row_perm)
-    factor_prep(FV, log_V_hat, mu=mu_v, row_index=ct.col_perm)
-    if ws.s_rs is None:
-        ws.s_rs = torch.zeros(max(ct.rslots, 1), **f32)
-    ws.tile_flag.zero_()
-    st = stream_ptr()
-    with _span(ws, 'row_pass'):
-        call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV), None, ptr(ws.R), ptr(ws.s_cs), None, ptr(ws.s_rs),
-             ptr(ws.tile_flag), K, st)
-    pair = torch.empty(n, 2, dtype=torch.float64, device=dev)
-    with _span(ws, 'cell_bound_nnz'):
-        call('oriana_cell_bound_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(mu_u), ptr(mu_v), ptr(log_U), ptr(log_V_hat), K,
-             ptr(pair), st)
-    return pair
-
-
-def cell_bounds(ct, K, a1, a2_row, log_U, log_V_hat, sum_v, alpha1, alpha2, ws=None):
-    """Each cell's share of pCMF's collapsed variational bound with the gene side as given: a device (n', 4) float64 tensor
-    [data, lgamma, product, kl] per cell of `ct` (CountTiles, sliced layout), caller's row order --
-      data_i    = sum_{j: x_ij != 0} x_ij logsumexp_k(log_U_ik + log_V_hat_jk)         lgamma_i = sum_{j: x_ij != 0} lgamma(x_ij + 1)
-      product_i = sum_k (a1_ik / a2_row_k) sum_v_k                                    kl_i = sum_k KL(Gamma(a1_ik, a2_row_k) || Gamma(alpha1_k, alpha2_k))
-    and the cell's score is data - lgamma - product - kl.  a1 (n', K) float64, log_U (n', K) float32 (the E[log U] the data
-    term is evaluated at, unshifted), log_V_hat (m, K) float32, a2_row / sum_v / alpha1 / alpha2 [K] float64: all only read.
-    The data term is GaP._elbo_terms' per cell: both factors prepared with their row maxima into buffers of this call's own,
-    one oriana_row_pass that leaves s in the row-side slots, and oriana_cell_bound_nnz, which reads that stream once and
-    writes every cell's two sums in a fixed order (no atomics: two calls agree bit for bit); the Kullback-Leibler term is
-    oriana_gamma_kl_rows.  `ws`: a ZWorkspace over `ct` of the caller's own (its row-pass scratch is overwritten); None
-    makes one."""
-    if ct.gd:
-        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
-    n, m, dev = ct.n, ct.m, ct.device
-    _check_f32(log_V_hat, (m, K))
-    _check_f32(log_U, (n, K))
-    if a1.dtype != torch.float64 or tuple(a1.shape) != (n, K) or not a1.is_contiguous():
-        raise TypeError('a1 must be a C-contiguous (n\', K) float64 device tensor')
-    for name, v in (('a2_row', a2_row), ('sum_v', sum_v), ('alpha1', alpha1), ('alpha2', alpha2)):
-        if v.dtype != torch.float64 or tuple(v.shape) != (K,) or not v.is_contiguous():
-            raise TypeError('%s must be a contiguous [K] float64 device tensor' % name)
-    out = torch.empty(n, 4, dtype=torch.float64, device=dev)
-    if n == 0:
-        return out
-    if ws is None:
-        ws = ZWorkspace(ct, K)
-    pair = _cell_data_terms(ws, K, log_U, log_V_hat)
-    st = stream_ptr()
-    kl = torch.empty(n, dtype=torch.float64, device=dev)
-    with _span(ws, 'gamma_kl_rows'):
-        call('oriana_gamma_kl_rows', ptr(kl), ptr(a1), ptr(a2_row), 1, ptr(alpha1), ptr(alpha2), n, K, st)
-    out[:, :2] = pair
-    out[:, 2] = ((a1 / a2_row) * sum_v).sum(dim=1)
-    out[:, 3] = kl
-    return out
-
-
-PI_D_FLOOR = 1e-10                # the override values of zigap.py:133-134: pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)
-
-
-def zi_cell_bounds(ct, K, a1, a2, log_U, log_V_hat, V_hat, pi_d, alpha1, alpha2, ws=None):
-    """Each cell's share of ZI-pCMF's variational bound with the gene side as given and q(Z), q(d) collapsed at their optima: a
-    device (n', 4) float64 tensor [data, lgamma, dropout, kl] per cell of `ct` (CountTiles, sliced layout), caller's row order --
-      data_i, lgamma_i as cell_bounds;    kl_i = sum_k KL(Gamma(a1_ik, a2_ik) || Gamma(alpha1_k, alpha2_k))
-      dropout_i = sum_j log(1 - pi~_j) + sum_{x_ij != 0} z_ij + sum_{x_ij = 0} softplus(z_ij),
-      z_ij = logit(pi~_j) - (a1_i / a2_i) . V_hat_j,    pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)
-    and the cell's score is data - lgamma + dropout - kl.  a1, a2 (n', K), V_hat (m, K), pi_d [m], alpha1 / alpha2 [K] float64,
-    log_U (n', K) float32 (the E[log U] the data term is evaluated at, unshifted), log_V_hat (m, K) float32: all only read.
-    The dropout term is ONE oriana_zi_cell_bound launch sequence over the query's own non-zero mask (oriana_nzmask_counts, as
-    fold_in_zi builds it) with the per-gene operands padded to a multiple of 4 genes; the cell-independent sum is added here in
-    float64.  No (n', m) matrix exists at any point; every term is written in a fixed order (two calls agree bit for bit).
-    `ws`: a ZWorkspace over `ct` of the caller's own (its row-pass scratch is overwritten); None makes one."""
-    if ct.gd:
-        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
-    n, m, dev = ct.n, ct.m, ct.device
-    if K > 128:
-        raise ValueError('the zero-inflated bound serves K <= 128 (the float32 dense kernels), got K = %d' % K)
-    _check_f32(log_V_hat, (m, K))
-    _check_f32(log_U, (n, K))
-    for name, T, shape in (('a1', a1, (n, K)), ('a2', a2, (n, K)), ('V_hat', V_hat, (m, K)), ('pi_d', pi_d, (m,)),
-                           ('alpha1', alpha1, (K,)), ('alpha2', alpha2, (K,))):
-        if T.dtype != torch.float64 or tuple(T.shape) != shape or not T.is_contiguous():
-            raise TypeError('%s must be a C-contiguous %s float64 device tensor' % (name, shape))
-    out = torch.empty(n, 4, dtype=torch.float64, device=dev)
-    if n == 0:
-        return out
-    if ws is None:
-        ws = ZWorkspace(ct, K)
-    out[:, :2] = _cell_data_terms(ws, K, log_U, log_V_hat)
-    f64 = dict(dtype=torch.float64, device=dev)
-    mp = (m + 3) // 4 * 4                               # inert genes: no counts, V_hat row 0, pi_d 0 (models/zigap.py _padG)
-    if mp != m:
-        Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
-        Vp[:m].copy_(V_hat)
-        pip[:m].copy_(pi_d)
-    else:
-        Vp, pip = V_hat, pi_d
-    st = stream_ptr()
-    nzmask = torch.zeros(((n + 31) // 32) * mp, dtype=torch.int32, device=dev)
-    call('oriana_nzmask_counts', ptr(nzmask), ct.sparse_struct, mp, st)
-    U_hat = a1 / a2
-    scratch = torch.empty(max(int(_lib.load().oriana_zi_cell_bound_scratch_doubles(n, mp, K)), 1), **f64)   # the call's own
-    drop = torch.empty(n, **f64)
-    with _span(ws, 'zi_cell_bound'):
-        call('oriana_zi_cell_bound', ptr(drop), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(scratch), n, mp, m, K, st)
-    out[:, 2] = drop + torch.log1p(-torch.clamp(pi_d, PI_D_FLOOR, 1.0 - PI_D_FLOOR)).sum()
-    kl = torch.empty(n, **f64)
-    with _span(ws, 'gamma_kl_rows'):
-        call('oriana_gamma_kl_rows', ptr(kl), ptr(a1), ptr(a2), 0, ptr(alpha1), ptr(alpha2), n, K, st)
-    out[:, 3] = kl
-    return out
-
-
-def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter, tol, check_every=5, ws=None, arithmetic=1):
-    """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted ZI-pCMF model whose gene side stays as it is: per
-    cell the fixed point of the pair (a1, a2) under zigap.py:115-136 with V_hat, E[log V] and pi_d frozen --
-      a1' = max(1e-15, alpha1 + sum_j x_ij r_ijk)        (the pCMF row pass: D_hat = f32(1 - 1e-10) = 1 at the non-zeros)
-      a2' = max(1e-15, alpha2 + sum_j d_ij V_hat_jk),    d_ij = 1 at x_ij != 0, the column overrides of zigap.py:133-134, else
-                                                         f32(sigmoid(logit(pi_d_j) - U_hat_i . V_hat_j)),  U_hat = a1 / a2
-    both from the OLD pair (the reference's sweep order: the rate reads the D_hat formed from the U_hat that enters the sweep).
-    `a1`, `a2` (n', K) float64 device tensors: the start, updated in place; log_V_hat (m, K) float32, V_hat (m, K) float64,
-    pi_d [m], alpha1 / alpha2 [K] float64: the model's, only read.
-    Each iteration: the rate buffer is zeroed, the row phase of a sweep runs on a workspace of this call's own (as fold_in),
-    ONE oriana_zi_foldin_rate launch forms sum_j d_ij V_hat_jk from the call's own U_hat over the cells still active -- d is never
-    stored: no (n', m) matrix exists at any point -- and ONE oriana_foldin_update_zi launch updates the pair, U_hat, E[log U],
-    freezes the cells that moved by at most tol in both halves and prepares the next row pass's FU in place.  The per-gene
-    operands are padded to a multiple of 4 genes with inert ones (V_hat row 0, pi_d 0), as the models do; both non-zero masks
-    come from the packed counts, once per call.  Returns (froze_at, cells still active, iterations run) as fold_in."""
-    if ct_new.gd:
-        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
-    n, m, dev = ct_new.n, ct_new.m, ct_new.device
-    n_iter, check_every, tol = int(n_iter), int(check_every), float(tol)
-    if n_iter < 0 or check_every < 1 or not tol >= 0.0:
-        raise ValueError('fold_in needs n_iter >= 0, check_every >= 1 and tol >= 0')
-    if K > 128:
-        raise ValueError('the zero-inflated fold-in serves K <= 128 (the float32 dense kernels), got K = %d' % K)
-    _check_f32(log_V_hat, (m, K))
-    for name, T, shape in (('a1', a1, (n, K)), ('a2', a2, (n, K)), ('V_hat', V_hat, (m, K)), ('pi_d', pi_d, (m,))):
-        if T.dtype != torch.float64 or tuple(T.shape) != shape or not T.is_contiguous():
-            raise TypeError('%s must be a C-contiguous %s float64 device tensor' % (name, shape))
-    froze_at = torch.full((n,), n_iter, dtype=torch.int32, device=dev)
-    if n == 0:
-        return froze_at, 0, 0
-    if ws is None:
-        ws = ZWorkspace(ct_new, K)
-    lib = _lib.load()
-    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
-    mp = (m + 3) // 4 * 4                               # inert genes: no counts, V_hat row 0, pi_d 0 (models/zigap.py _padG)
-    if mp != m:
-        Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
-        Vp[:m].copy_(V_hat)
-        pip[:m].copy_(pi_d)
-    else:
-        Vp, pip = V_hat, pi_d
-    st = stream_ptr()
-    nzmask = torch.zeros(((n + 31) // 32) * mp, dtype=torch.int32, device=dev)
-    call('oriana_nzmask_counts', ptr(nzmask), ct_new.sparse_struct, mp, st)
-    nztiles = torch.zeros(max(int(lib.oriana_nzmask_tiles_words(n, mp)), 4), dtype=torch.int32, device=dev)
-    call('oriana_nzmask_tiles', ptr(nztiles), ptr(nzmask), n, mp, st)
-    scratch = torch.zeros(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), **f32)      # the call's own, never the model's
-    rate, U_hat = torch.empty(n, K, **f64), torch.empty(n, K, **f64)
-    lu, Zi, Zj, active, left = _fold_in_buffers(ws, n_iter)
-    call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), None, None, None, None, None, None, None,
-         None, 1, 0, ptr(ct_new.row_perm), n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
-    n_left, done = n, 0
-    for it in range(n_iter):
-        rate.zero_()
-        ws.fu_pending, ws.fu_source = True, lu.data_ptr()
-        zq_gap(ws, Zi, Zj, lu, log_V_hat, phase='rows', finalize_rows=False)
-        with _span(ws, 'zi_foldin_rate'):
-            call('oriana_zi_foldin_rate', ptr(rate), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(nztiles), ptr(active),
-                 ptr(scratch), int(arithmetic), n, mp, K, st)
-        with _span(ws, 'foldin_update'):
-            call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), ptr(froze_at), ptr(left) + 4 * it,
-                 ptr(alpha1), ptr(alpha2), ptr(rate), ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0,
-                 ptr(ct_new.row_perm), n, K, tol, it, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
-        done = it + 1
-        if done % check_every == 0 or done == n_iter:
-            n_left = int(left[it].item())
-            if n_left == 0:
-                break
-    return froze_at, n_left, done
-
-
 def _have_sliced(ct):
     """Do the sliced kernels run?  Not on a hybrid layout whose genes are all dense."""
     return ct.ms > 0 or ct.dense is None

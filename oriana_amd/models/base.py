@@ -12,7 +12,7 @@ materialised (``UV`` is evaluated on demand), X is packed once instead of re-cas
 import numpy as np
 import torch
 
-from .. import engine
+from .. import engine, heldout
 from .._lib import call, ptr, stream_ptr, OrianaHipError
 from ..parameters import Parameter
 from ..dims import Dimensions
@@ -341,6 +341,39 @@ class FactorModel:
         if ct.gd:
             raise ValueError('%s walks the sliced layout only: pack the new counts without dense_density' % what)
         return ct
+
+    def _fold_in_start(self, ct, ws, init):
+        """The a1 (n', K) float64 a fold-in of `ct` starts from: `init` (checked, copied to the device), by default
+        alpha1 + rowsum(x) / K (uniform responsibilities, no RNG; `ws`: the call's workspace); clamped as the sweeps clamp."""
+        K, dev, nq = self.k, self.device, ct.n
+        if init is not None:
+            a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
+            if tuple(a1.shape) != (nq, K):
+                raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
+            a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
+        elif nq > 0:
+            a1 = self.alpha1.tensor[None, :] + heldout.row_sums_over_k(ws, K).to(torch.float64)
+        else:
+            a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
+        return torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
+
+    @staticmethod
+    def _score_result(terms, names, signs, extras, return_terms):
+        """A held-out score from its (n', 4) float64 host terms, added left to right with `signs` ('+' / '-' per term): the
+        array, or with return_terms a dict of score, a copy of each term under its name and the `extras`."""
+        score = terms[:, 0] if signs[0] == '+' else -terms[:, 0]
+        for j in (1, 2, 3):
+            score = score + terms[:, j] if signs[j] == '+' else score - terms[:, j]
+        if not return_terms:
+            return score
+        return dict(score=score, **{name: terms[:, j].copy() for j, name in enumerate(names)}, **extras)
+
+    @staticmethod
+    def _mean_score(s):
+        """The mean of a per-cell score (the array, or the dict of return_terms) as a Python float; nan for no cells."""
+        if isinstance(s, dict):
+            s = s['score']
+        return float(s.mean()) if s.size else float('nan')
 
     def transform(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False):
         """E[U] of cells the model was not fitted on (GaP); NotImplementedError on the other models."""

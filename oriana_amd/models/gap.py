@@ -4,9 +4,10 @@ import os
 
 import torch
 
-from .. import engine
+from .. import engine, heldout
 from .. import dist as odist
 from .._lib import call, ptr, stream_ptr
+from ..nodes import gamma_expectations
 from .base import FactorModel
 
 __all__ = ['GaP']
@@ -165,7 +166,7 @@ class GaP(FactorModel):
     # ---- folding in new cells ----------------------------------------------------------------------------------------------
     # For a cell the model was not fitted on, with the gene side held fixed, the cell-side update of the sweep (lines 97-102 of
     # the reference's gap.py) is a fixed-point iteration of that cell alone: a2 = alpha2 + sum_j V_hat never moves, a1 <- alpha1 +
-    # sum_j x_ij r_ijk with r the softmax of E[log U]_i. + E[log V]_j. .  engine.fold_in runs it on a workspace of its own:
+    # sum_j x_ij r_ijk with r the softmax of E[log U]_i. + E[log V]_j. .  heldout.fold_in runs it on a workspace of its own:
     # nothing the model or its workspace hold is written ("Folding in new cells").
     transform_unconverged_ = None
 
@@ -187,24 +188,14 @@ class GaP(FactorModel):
         """The fold-in of transform() and score_samples(): (the packed cells, the call's workspace -- None for no cells --, the
         final a1 (n', K), a2_row [K], sum_j V_hat [K] as the sweep reads it, froze_at), all on the device; sets
         ``transform_unconverged_``."""
-        import numpy as np
         ct = self._query_counts(cmatrix)
-        K, dev, nq = self.k, self.device, ct.n
+        K = self.k
         sum_v = self._accV[0] if self._v_sums_in_acc else self._sumV[0]          # as the sweep reads sum_j V_hat
         a2_row = torch.clamp(torch.nan_to_num(self.alpha2.tensor + sum_v), min=1e-15)       # gap.py:98, 100
-        alpha1 = self.alpha1.tensor
-        ws = engine.ZWorkspace(ct, K) if nq > 0 else None
-        if init is not None:
-            a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
-            if tuple(a1.shape) != (nq, K):
-                raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
-            a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
-        elif nq > 0:
-            a1 = alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)
-        else:
-            a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
-        a1 = torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
-        froze_at, left, _ = engine.fold_in(ct, K, self._log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=check_every, ws=ws)
+        ws = engine.ZWorkspace(ct, K) if ct.n > 0 else None
+        a1 = self._fold_in_start(ct, ws, init)
+        froze_at, left, _ = heldout.fold_in(ct, K, self._log_V_hat, self.alpha1.tensor, a2_row, a1, n_iter, tol,
+                                            check_every=check_every, ws=ws)
         self.transform_unconverged_ = int(left)
         return ct, ws, a1, a2_row, sum_v, froze_at
 
@@ -225,29 +216,19 @@ class GaP(FactorModel):
         E[log U] = psi(a1) - log a2_row the data term was evaluated at.  The model and its workspace are not written; under row
         sharding the call is local to the rank."""
         ct, ws, a1, a2_row, sum_v, froze_at = self._fold_in_cells(cmatrix, n_iter, tol, init, check_every)
-        K, dev, nq = self.k, self.device, ct.n
-        lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
-        if nq > 0:
-            # E[log U] of the final shapes by the Gamma node's own kernel (nodes.Gamma.meanlog): Z = NULL, parameters as they are
-            a2 = a2_row.expand(nq, K).contiguous()
-            call('oriana_gamma_update', ptr(a1), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None,
-                 None, None, None, nq, K, stream_ptr())
-        terms = engine.cell_bounds(ct, K, a1, a2_row, lu, self._log_V_hat, sum_v.contiguous(), self.alpha1.tensor,
-                                   self.alpha2.tensor, ws=ws)
-        t = terms.cpu().numpy()
-        score = t[:, 0] - t[:, 1] - t[:, 2] - t[:, 3]
-        if not return_terms:
-            return score
-        return dict(score=score, data=t[:, 0].copy(), lgamma=t[:, 1].copy(), product=t[:, 2].copy(), kl=t[:, 3].copy(),
-                    a1=a1.cpu().numpy(), a2_row=a2_row.cpu().numpy(), froze_at=froze_at.cpu().numpy(), log_U_hat=lu.cpu().numpy())
+        K = self.k
+        # E[log U] of the final shapes by the Gamma node's own kernel, against the rate expanded to every cell
+        lu = gamma_expectations(a1, a2_row.expand(ct.n, K).contiguous())[1]
+        terms = heldout.cell_bounds(ct, K, a1, a2_row, lu, self._log_V_hat, sum_v.contiguous(), self.alpha1.tensor,
+                                    self.alpha2.tensor, ws=ws)
+        return self._score_result(terms.cpu().numpy(), ('data', 'lgamma', 'product', 'kl'), '+---',
+                                  dict(a1=a1.cpu().numpy(), a2_row=a2_row.cpu().numpy(), froze_at=froze_at.cpu().numpy(),
+                                       log_U_hat=lu.cpu().numpy()), return_terms)
 
     def score(self, cmatrix, **kw):
         """The mean of score_samples(cmatrix, **kw) as a Python float (nan for no cells): compare it across fits with
         different k on cells none of them was fitted on."""
-        s = self.score_samples(cmatrix, **kw)
-        if isinstance(s, dict):
-            s = s['score']
-        return float(s.mean()) if s.size else float('nan')
+        return self._mean_score(self.score_samples(cmatrix, **kw))
 
     def _init_extra(self):
         if os.environ.get('ORIANA_LAZY_U', '1') != '0':

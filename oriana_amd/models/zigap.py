@@ -17,13 +17,13 @@ ORIANA_ZI_EXACT=1 routes everything through them.
 """
 import os
 
-import numpy as np
 import torch
 
-from .. import engine
+from .. import engine, heldout
 from .. import dist as odist
 from .._lib import call, ptr, stream_ptr
 from ..parameters import Parameter, LazyParameter
+from ..nodes import gamma_expectations
 from .base import FactorModel
 
 __all__ = ['ZIGaP', 'SparseGaP', 'SparseZIGaP']
@@ -284,7 +284,7 @@ class ZIGaP(_ZIMixin, FactorModel):
     # ---- folding in new cells ----------------------------------------------------------------------------------------------
     # With the gene side (V_hat, E[log V], pi_d) and the priors held fixed, the cell side of a ZI sweep (zigap.py:115-136) is a
     # fixed-point iteration of each new cell's own pair (a1, a2): the rate a2 = alpha2 + sum_j d_ij V_hat_jk reads the cell's own
-    # dropout posterior d_i., which reads U_hat_i = a1 / a2.  engine.fold_in_zi runs it without ever storing d (DESIGN.md,
+    # dropout posterior d_i., which reads U_hat_i = a1 / a2.  heldout.fold_in_zi runs it without ever storing d (DESIGN.md,
     # "Folding in new cells"): nothing the model or its workspace hold is written, no scratch is cached on the model.
     fold_in_unconverged_ = None
     _no_transform = ('transform() is defined for pCMF (GaP) only: a new cell of a zero-inflated model carries a dropout posterior of '
@@ -308,27 +308,18 @@ class ZIGaP(_ZIMixin, FactorModel):
         """The fold-in of fold_in() and fold_in_score_samples(): (the packed cells, the call's workspace -- None for no cells --,
         the final a1, a2 (n', K), froze_at), all on the device; sets ``fold_in_unconverged_``."""
         ct = self._query_counts(cmatrix, what)
-        K, dev, nq = self.k, self.device, ct.n
+        K, nq = self.k, ct.n
         if K > 128:
             raise ValueError('%s serves K <= 128 (the float32 dense kernels of the sweep); the float64 ZI path has no '
                              'fold-in, got k = %d' % (what, K))
         alpha1, alpha2 = self.alpha1.tensor, self.alpha2.tensor
         ws = engine.ZWorkspace(ct, K) if nq > 0 else None
-        if init is not None:
-            a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
-            if tuple(a1.shape) != (nq, K):
-                raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
-            a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
-        elif nq > 0:
-            a1 = alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)
-        else:
-            a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
-        a1 = torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()
+        a1 = self._fold_in_start(ct, ws, init)
         V = self._V_hat.contiguous()
         a2_row = torch.clamp(torch.nan_to_num(alpha2 + V.sum(dim=0)), min=1e-15)          # zigap.py:116-118 with D_hat = 1
         a2 = a2_row[None, :].expand(nq, K).contiguous()
-        froze_at, left, _ = engine.fold_in_zi(ct, K, self._log_V_hat, V, self.pi_d.tensor.contiguous(), alpha1, alpha2, a1, a2,
-                                              n_iter, tol, check_every=check_every, ws=ws, arithmetic=self._matrix_arith)
+        froze_at, left, _ = heldout.fold_in_zi(ct, K, self._log_V_hat, V, self.pi_d.tensor.contiguous(), alpha1, alpha2, a1, a2,
+                                               n_iter, tol, check_every=check_every, ws=ws, arithmetic=self._matrix_arith)
         self.fold_in_unconverged_ = int(left)
         return ct, ws, a1, a2, froze_at
 
@@ -355,28 +346,17 @@ class ZIGaP(_ZIMixin, FactorModel):
         data term was evaluated at.  K <= 128.  The model and its workspace are not written; under row sharding the call is
         local to the rank."""
         ct, ws, a1, a2, froze_at = self._fold_in_pairs(cmatrix, n_iter, tol, init, check_every, 'fold_in_score_samples()')
-        K, dev, nq = self.k, self.device, ct.n
-        lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
-        if nq > 0:
-            # E[log U] of the final pair by the Gamma node's own kernel (nodes.Gamma.meanlog): Z = NULL, parameters as they are
-            call('oriana_gamma_update', ptr(a1), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None,
-                 None, None, None, nq, K, stream_ptr())
-        terms = engine.zi_cell_bounds(ct, K, a1, a2, lu, self._log_V_hat, self._V_hat.contiguous(), self.pi_d.tensor.contiguous(),
-                                      self.alpha1.tensor, self.alpha2.tensor, ws=ws)
-        t = terms.cpu().numpy()
-        score = t[:, 0] - t[:, 1] + t[:, 2] - t[:, 3]
-        if not return_terms:
-            return score
-        return dict(score=score, data=t[:, 0].copy(), lgamma=t[:, 1].copy(), dropout=t[:, 2].copy(), kl=t[:, 3].copy(),
-                    a1=a1.cpu().numpy(), a2=a2.cpu().numpy(), froze_at=froze_at.cpu().numpy(), log_U_hat=lu.cpu().numpy())
+        lu = gamma_expectations(a1, a2)[1]           # E[log U] of the final pair by the Gamma node's own kernel
+        terms = heldout.zi_cell_bounds(ct, self.k, a1, a2, lu, self._log_V_hat, self._V_hat.contiguous(),
+                                       self.pi_d.tensor.contiguous(), self.alpha1.tensor, self.alpha2.tensor, ws=ws)
+        return self._score_result(terms.cpu().numpy(), ('data', 'lgamma', 'dropout', 'kl'), '+-+-',
+                                  dict(a1=a1.cpu().numpy(), a2=a2.cpu().numpy(), froze_at=froze_at.cpu().numpy(),
+                                       log_U_hat=lu.cpu().numpy()), return_terms)
 
     def fold_in_score(self, cmatrix, **kw):
         """The mean of fold_in_score_samples(cmatrix, **kw) as a Python float (nan for no cells): compare it across ZI fits with
         different k, or with GaP.score() of a pCMF fit, on cells none of them was fitted on."""
-        s = self.fold_in_score_samples(cmatrix, **kw)
-        if isinstance(s, dict):
-            s = s['score']
-        return float(s.mean()) if s.size else float('nan')
+        return self._mean_score(self.fold_in_score_samples(cmatrix, **kw))
 
 
 class SparseGaP(_SparseMixin, FactorModel):

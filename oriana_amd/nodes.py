@@ -11,7 +11,6 @@ and returns it.  The per-distribution arithmetic runs in the HIP kernel ``oriana
 (float32 cast of the parameters before digamma / log, as gamma.py:56-57).  Sampling and
 log-densities are out of scope (never called from ``step()``).
 """
-import numpy as np
 import torch
 
 from ._lib import call, ptr, stream_ptr
@@ -26,6 +25,18 @@ def _as_tensor(param):
     if isinstance(param, torch.Tensor):
         return param
     return Parameter(param).tensor
+
+
+def gamma_expectations(a, b):
+    """(E[x] float64, E[log x] float32) of Gamma(shape a, rate b), contiguous float64 device tensors of one shape (a vector or
+    (r, K)).  oriana_gamma_update with Z = NULL: the parameters are taken as they are, only the expectations are produced."""
+    r, K = (a.shape[0], a.shape[1]) if a.dim() == 2 else (a.numel(), 1)
+    E = torch.empty_like(a)
+    Elog = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+    if a.numel():
+        call('oriana_gamma_update', ptr(a), ptr(b), ptr(E), ptr(Elog), None, None, None, None, None, None, None, None,
+             None, r, K, stream_ptr())
+    return E, Elog
 
 
 class _Node:
@@ -71,12 +82,7 @@ class Gamma(_Node):
         a = _as_tensor(self.parents[0]).to(device='cuda', dtype=torch.float64).reshape(-1).contiguous().clone()
         b = _as_tensor(self.parents[1]).to(device='cuda', dtype=torch.float64).reshape(-1).contiguous().clone()
         assert a.numel() == self.n_distribs and b.numel() == self.n_distribs
-        E = torch.empty_like(a)
-        Elog = torch.empty(a.numel(), dtype=torch.float32, device='cuda')
-        # Z = NULL: parameters are taken as they are, only the expectations are produced
-        call('oriana_gamma_update', ptr(a), ptr(b), ptr(E), ptr(Elog), None, None, None, None, None, None, None, None,
-             None, a.numel(), 1, stream_ptr())
-        return E, Elog
+        return gamma_expectations(a, b)
 
     def mean(self):
         return self._publish(self._expectations()[0])

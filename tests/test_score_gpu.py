@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""GaP.score_samples() / score() and engine.cell_bounds on the GPU against the float64 reference of tests/score_reference.py.
+"""GaP.score_samples() / score() and heldout.cell_bounds on the GPU against the float64 reference of tests/score_reference.py.
 
 Shapes and models are those of tests/test_elbo_gpu.py (the smallest that cross a partial last row tile and two gene tiles, with
 an all-zero cell, an all-zero gene and a gene expressed everywhere); the bounds are elbo_reference.elbo_bounds per cell
@@ -96,10 +96,10 @@ def test_terms_against_float64(K, dd):
 
 @pytest.mark.parametrize('K,dd', [(20, None), (100, DENSE_DENSITY)], ids=['K20-sliced', 'K100-hybrid'])
 def test_cells_add_up_to_the_elbo_terms(K, dd):
-    """engine.cell_bounds on the model's own cells (packed sliced), at the model's own a1, rate and stored float32 E[log U]:
+    """heldout.cell_bounds on the model's own cells (packed sliced), at the model's own a1, rate and stored float32 E[log U]:
     the column sums are the first four terms of GaP._elbo_terms().  (The rate is `_a2_row` while the lazy cell side is in
     effect, else the row every cell of the stored a2 holds -- what _elbo_terms reads.)"""
-    from oriana_amd import engine
+    from oriana_amd import heldout
     X = _counts(K)
     G = _fitted(K, dd)
     whole = G._elbo_terms().cpu().numpy()
@@ -110,7 +110,7 @@ def test_cells_add_up_to_the_elbo_terms(K, dd):
     ct = G._query_counts(X)
     assert ct.gd == 0 and ct.n == G.n
     sum_v = G._V_hat.sum(0)
-    t = engine.cell_bounds(ct, K, G.a1.tensor, a2_row, G._log_U_hat, G._log_V_hat, sum_v, G.alpha1.tensor, G.alpha2.tensor)
+    t = heldout.cell_bounds(ct, K, G.a1.tensor, a2_row, G._log_U_hat, G._log_V_hat, sum_v, G.alpha1.tensor, G.alpha2.tensor)
     assert t.dtype == torch.float64 and tuple(t.shape) == (G.n, 4)
     got = t.cpu().numpy()
     st = G.state()
@@ -128,7 +128,7 @@ def test_cells_add_up_to_the_elbo_terms(K, dd):
 def test_shapes_at_the_clamp_take_the_fallback():
     """Cells that start with two factors, or every factor, at 1e-15 and are scored there (n_iter=0): E[log U] ~ -1e15, the
     all-clamped cell cannot take the shifted form and its entries are the float64 log-sum-exp inside the kernel."""
-    from oriana_amd import engine
+    from oriana_amd import engine, heldout
     K = 20
     G = _fitted(K, None)
     Xq = _query(3)
@@ -148,7 +148,7 @@ def test_shapes_at_the_clamp_take_the_fallback():
     ws = engine.ZWorkspace(ct, K)
     dev = G.device
     sum_v = G._accV[0] if G._v_sums_in_acc else G._sumV[0]
-    t = engine.cell_bounds(ct, K, torch.from_numpy(out['a1']).to(dev), torch.from_numpy(out['a2_row']).to(dev),
+    t = heldout.cell_bounds(ct, K, torch.from_numpy(out['a1']).to(dev), torch.from_numpy(out['a2_row']).to(dev),
                            torch.from_numpy(out['log_U_hat']).to(dev), G._log_V_hat, sum_v.contiguous(), G.alpha1.tensor,
                            G.alpha2.tensor, ws=ws).cpu().numpy()
     assert torch.isnan(ws.s_rs).any(), 'the row pass left no NaN sentinel: the fall-back was not exercised'

@@ -64,9 +64,9 @@ def test_one_iteration_against_float64(K, dd):
 
 
 def test_unaligned_buffers_take_the_element_kernel():
-    """engine.fold_in on an a1 that is 8- but not 16-byte aligned (where oriana_gamma_update_finalize_lazy answers
+    """heldout.fold_in on an a1 that is 8- but not 16-byte aligned (where oriana_gamma_update_finalize_lazy answers
     ORIANA_EKRANGE): the same update within the same bound."""
-    from oriana_amd import engine
+    from oriana_amd import engine, heldout
     K = 100
     G = _fitted(K, None)
     Xq = _counts(K + 50)
@@ -78,7 +78,7 @@ def test_unaligned_buffers_take_the_element_kernel():
     a1 = buf[off:off + N_ROWS * K].view(N_ROWS, K)
     assert a1.data_ptr() % 16 == 8
     a1.copy_(torch.from_numpy(a1_0))
-    froze, left, done = engine.fold_in(ct, K, G._log_V_hat, G.alpha1.tensor, torch.from_numpy(a2).to(G.device), a1, 1, 0.0)
+    froze, left, done = heldout.fold_in(ct, K, G._log_V_hat, G.alpha1.tensor, torch.from_numpy(a2).to(G.device), a1, 1, 0.0)
     e = err_colrel(a1.cpu().numpy(), ref)
     print('unaligned a1: %.3e' % e)
     assert done == 1 and e <= RTOL

@@ -247,9 +247,9 @@ def test_short_batches(nq):
 
 
 def test_unaligned_buffers_take_the_element_kernel():
-    """engine.fold_in_zi on a1 / a2 that are 8- but not 16-byte aligned: the same update within the same bound, nothing written
+    """heldout.fold_in_zi on a1 / a2 that are 8- but not 16-byte aligned: the same update within the same bound, nothing written
     outside them."""
-    from oriana_amd import engine
+    from oriana_amd import engine, heldout
     K = 100
     G = _fitted(K)
     Xq = _counts(K + 50)
@@ -267,7 +267,7 @@ def test_unaligned_buffers_take_the_element_kernel():
         v.copy_(torch.from_numpy(start))
         views.append(v)
         bufs.append((buf, off))
-    froze, left, done = engine.fold_in_zi(ct, K, G._log_V_hat, G._V_hat, G.pi_d.tensor, G.alpha1.tensor, G.alpha2.tensor,
+    froze, left, done = heldout.fold_in_zi(ct, K, G._log_V_hat, G._V_hat, G.pi_d.tensor, G.alpha1.tensor, G.alpha2.tensor,
                                           views[0], views[1], 1, 0.0, arithmetic=G._matrix_arith)
     e1, e2 = err_colrel(views[0].cpu().numpy(), r1), err_colrel(views[1].cpu().numpy(), r2)
     print('unaligned pair: a1 %.3e a2 %.3e' % (e1, e2))

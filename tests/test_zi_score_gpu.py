@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""ZIGaP.fold_in_score_samples() / fold_in_score(), engine.zi_cell_bounds and the C entry oriana_zi_cell_bound on the GPU against
+"""ZIGaP.fold_in_score_samples() / fold_in_score(), heldout.zi_cell_bounds and the C entry oriana_zi_cell_bound on the GPU against
 the float64 reference of tests/zi_score_reference.py.
 
 Shapes are those of tests/test_zi_foldin_gpu.py: 805 x 301 -- a partial last cell tile, m % 4 != 0 (so inert genes exist), an

@@ -1,13 +1,13 @@
 # -*- coding: utf-8 -*-
-"""Times a fold-in (GaP.transform's loop, engine.fold_in) against the same loop composed from the entries that existed before
+"""Times a fold-in (GaP.transform's loop, heldout.fold_in) against the same loop composed from the entries that existed before
 oriana_foldin_update: row phase + oriana_gamma_update_finalize_prep on throw-away (n', K) buffers.
 
 Default: 65,536 x 30,000 new cells, K = 100, 90 % zeros (the benchmark's generator), 20 forced iterations (tol = 0) against
 the gene side of a model fitted on `--fit-rows` cells of the same generator for `--fit-sweeps` sweeps.  Device events
 around whole loops (after a warm-up loop of each form, the two forms alternating, `--reps` times), then one loop of each
 form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
-`--zi`: the zero-inflated fold-in instead (main_zi below).  `--score`: one engine.cell_bounds call beside one fold-in iteration
-(main_score below).  `--zi --score`: one engine.zi_cell_bounds call beside one ZI fold-in iteration (main_zi_score below).
+`--zi`: the zero-inflated fold-in instead (main_zi below).  `--score`: one heldout.cell_bounds call beside one fold-in iteration
+(main_score below).  `--zi --score`: one heldout.zi_cell_bounds call beside one ZI fold-in iteration (main_score too).
 
     python tools/transform_bench.py --out profiles/transform_bench.json
 """
@@ -17,13 +17,81 @@ import os
 import sys
 import time
 
+from types import SimpleNamespace
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def setup(args, zi):
+    """What every mode times against: a model (ZIGaP if `zi`, else GaP) fitted on `--fit-rows` cells for `--fit-sweeps` sweeps,
+    the new cells packed on the sliced layout (same seed: the same V; their own loadings), a workspace over them and the
+    default start of a fold-in.  Returns a namespace of them and of the model's gene side as the fold-in reads it."""
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
+    from oriana_amd import engine, heldout
+    from oriana_amd.models import GaP, ZIGaP
+    from oriana_amd.singlecell import SyntheticCounts
+    dev = torch.device('cuda', 0)
+    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
+    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
+                                           dense_density=None if zi else engine.auto_dense_density(args.fit_rows, m, K))
+    a1, b1 = gen.initial_shapes()
+    model = (ZIGaP if zi else GaP)(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    del a1, b1
+    model.fit(args.fit_sweeps)
+    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
+    torch.cuda.synchronize()
+    b = SimpleNamespace(dev=dev, nq=nq, m=m, K=K, model=model, ct=ct, pack_ms=(time.perf_counter() - t0) * 1e3,
+                        alpha1=model.alpha1.tensor, alpha2=model.alpha2.tensor, lv=model._log_V_hat, ws=engine.ZWorkspace(ct, K))
+    b.start = (b.alpha1[None, :] + heldout.row_sums_over_k(b.ws, K).to(torch.float64)).contiguous()
+    if zi:
+        b.V, b.pi_d, b.arith = model._V_hat.contiguous(), model.pi_d.tensor.contiguous(), model._matrix_arith
+        b.start2 = torch.clamp(b.alpha2 + b.V.sum(0), min=1e-15)[None, :].expand(nq, K).contiguous()
+    else:
+        b.sum_v = (model._accV[0] if model._v_sums_in_acc else model._sumV[0]).clone()
+        b.a2_row = torch.clamp(b.alpha2 + b.sum_v, min=1e-15)
+    return b
+
+
+def timed(fn):
+    """Milliseconds between two device events around fn()."""
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def launches(fn, prealloc):
+    """Per-launch events of one further fn(timer): {name: {count, mean_ms}}."""
+    import torch
+    from oriana_amd import engine
+    timer = engine.KernelTimer(prealloc=prealloc)
+    fn(timer)
+    torch.cuda.synchronize()
+    return {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+
+
+def emit(out, args):
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(out, indent=1) + '\n')
+
+
 def main_zi(args):
-    """--zi: one iteration of ZIGaP.fold_in's loop (engine.fold_in_zi), and its rate launch -- oriana_zi_foldin_rate, which never
+    """--zi: one iteration of ZIGaP.fold_in's loop (heldout.fold_in_zi), and its rate launch -- oriana_zi_foldin_rate, which never
     stores the dropout posterior -- against the storing entry (oriana_dropout_sweep_fused_tiles on a scratch D_hat of the query, whose
     kernels this build compiles instruction for instruction as before the rate entry existed) on the same operands: the two
     launches alternate, device events around runs of `--iters` launches, `--reps` times, after a warm-up of both.
@@ -32,63 +100,28 @@ def main_zi(args):
     """
     import numpy as np
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
-    from oriana_amd import _lib, engine
+    from oriana_amd import _lib, heldout
     from oriana_amd._lib import call, ptr, stream_ptr
-    from oriana_amd.models import ZIGaP
-    from oriana_amd.singlecell import SyntheticCounts
-    dev = torch.device('cuda', 0)
-    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
-    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev, dense_density=None)
-    a1, b1 = gen.initial_shapes()
-    model = ZIGaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
-    del a1, b1
-    model.fit(args.fit_sweeps)
-    torch.cuda.synchronize()
-    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
-    alpha1, alpha2, lv, V = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat, model._V_hat.contiguous()
-    pi_d, arith = model.pi_d.tensor.contiguous(), model._matrix_arith
-    ws = engine.ZWorkspace(ct, K)
-    s1 = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
-    s2 = torch.clamp(alpha2 + V.sum(0), min=1e-15)[None, :].expand(nq, K).contiguous()
+    b = setup(args, zi=True)
+    nq, m, K, ct, ws, dev, arith = b.nq, b.m, b.K, b.ct, b.ws, b.dev, b.arith
 
     def loop(timer=None):
         ws.timer = timer
-        p1, p2 = s1.clone(), s2.clone()
-        engine.fold_in_zi(ct, K, lv, V, pi_d, alpha1, alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=arith)
+        p1, p2 = b.start.clone(), b.start2.clone()
+        heldout.fold_in_zi(ct, K, b.lv, b.V, b.pi_d, b.alpha1, b.alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=arith)
         ws.timer = None
         return p1, p2
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b)
-
     p1, p2 = loop()                                                  # warm-up
     t_loop = [timed(loop) for _ in range(args.reps)]
-    timer = engine.KernelTimer(prealloc=8 * args.iters)
-    loop(timer)
-    torch.cuda.synchronize()
-    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    loop_launches = launches(loop, 8 * args.iters)
 
     # ---- the rate launch alone, both forms on the operands of the loop's last iteration ---------------------------------------
-    mp = (m + 3) // 4 * 4
     f64 = dict(dtype=torch.float64, device=dev)
-    Vp, pip = torch.zeros(mp, K, **f64), torch.zeros(mp, **f64)
-    Vp[:m].copy_(V)
-    pip[:m].copy_(pi_d)
+    mp, Vp, pip, mask = heldout._padded_genes(ct, K, b.V, b.pi_d)
     U = (p1 / p2).contiguous()
     st = stream_ptr()
     lib = _lib.load()
-    mask = torch.zeros(((nq + 31) // 32) * mp, dtype=torch.int32, device=dev)
-    call('oriana_nzmask_counts', ptr(mask), ct.sparse_struct, mp, st)
     tiles = torch.zeros(max(int(lib.oriana_nzmask_tiles_words(nq, mp)), 4), dtype=torch.int32, device=dev)
     call('oriana_nzmask_tiles', ptr(tiles), ptr(mask), nq, mp, st)
     scratch = torch.zeros(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), dtype=torch.float32, device=dev)
@@ -112,84 +145,59 @@ def main_zi(args):
     for _ in range(args.reps):
         t_a.append(timed(no_store) / args.iters)
         t_b.append(timed(storing) / args.iters)
-    out = {
+    emit({
         'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
         'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps, 'arithmetic': arith,
         'loop_ms_per_iter': round(float(np.median(t_loop)) / args.iters, 4), 'loop_ms': [round(t, 3) for t in t_loop],
-        'loop_launches': launches,
+        'loop_launches': loop_launches,
         'rate_no_store_ms': round(float(np.median(t_a)), 4), 'rate_storing_ms': round(float(np.median(t_b)), 4),
         'rate_no_store_all_ms': [round(t, 4) for t in t_a], 'rate_storing_all_ms': [round(t, 4) for t in t_b],
         'D_hat_bytes_not_allocated_by_fold_in': nq * mp * 4,
         'rate_no_store_vs_storing_colrel': rel,
         'note': 'rate_*: `iters` back-to-back launches between two device events, the two forms alternating; the storing form '
                 'writes a scratch D_hat of the query and its column sums besides the same DV',
-    }
-    print(json.dumps(out))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(json.dumps(out, indent=1) + '\n')
+    }, args)
 
 
-def main_zi_score(args):
-    """--zi --score: what scoring adds to a ZI fold-in -- E[log U] of the final pair + one engine.zi_cell_bounds call (the data
-    path of --score, the query's non-zero mask, oriana_zi_cell_bound, oriana_gamma_kl_rows) beside one iteration of
-    engine.fold_in_zi and its rate launch, on the operands of --zi.  Device events around the whole call / loop, `--reps` times
-    after a warm-up of both, then one call and one loop with per-launch events.
+def main_score(args, zi):
+    """--score: what scoring adds to a fold-in -- E[log U] of the final shapes + one heldout.cell_bounds call (two factor
+    preparations, the row pass that leaves s in the row-side slots, oriana_cell_bound_nnz, oriana_gamma_kl_rows, the float64
+    product) beside one iteration of heldout.fold_in on the same new cells and the same fitted gene side as the default mode.
+    --zi --score: the same for ZI-pCMF -- heldout.zi_cell_bounds (the data path, the query's non-zero mask, oriana_zi_cell_bound,
+    oriana_gamma_kl_rows) beside one iteration of heldout.fold_in_zi and its rate launch, on the operands of --zi.  Device events
+    around the whole call / loop, `--reps` times after a warm-up of both, then one call (--zi: and one loop) with per-launch events.
 
+        python tools/transform_bench.py --score --fit-rows 131072 --fit-sweeps 5 --out profiles/score_bench.json
         python tools/transform_bench.py --zi --score --cells 16384 --genes 20000 --k 50 --fit-rows 16384 --fit-sweeps 3 --iters 10
     """
     import numpy as np
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
-    from oriana_amd import engine
-    from oriana_amd._lib import call, ptr, stream_ptr
-    from oriana_amd.models import ZIGaP
-    from oriana_amd.singlecell import SyntheticCounts
-    dev = torch.device('cuda', 0)
-    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
-    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev, dense_density=None)
-    a1, b1 = gen.initial_shapes()
-    model = ZIGaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
-    del a1, b1
-    model.fit(args.fit_sweeps)
-    torch.cuda.synchronize()
-    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
-    alpha1, alpha2, lv, V = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat, model._V_hat.contiguous()
-    pi_d, arith = model.pi_d.tensor.contiguous(), model._matrix_arith
-    ws = engine.ZWorkspace(ct, K)
-    s1 = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
-    s2 = torch.clamp(alpha2 + V.sum(0), min=1e-15)[None, :].expand(nq, K).contiguous()
-    p1, p2 = s1.clone(), s2.clone()
+    from oriana_amd import heldout
+    from oriana_amd.nodes import gamma_expectations
+    b = setup(args, zi)
+    nq, m, K, ct, ws = b.nq, b.m, b.K, b.ct, b.ws
+    p1 = b.start.clone()
+    p2 = b.start2.clone() if zi else b.a2_row.expand(nq, K).contiguous()
 
     def loop(timer=None):
         ws.timer = timer
-        p1.copy_(s1)
-        p2.copy_(s2)
-        engine.fold_in_zi(ct, K, lv, V, pi_d, alpha1, alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=arith)
+        p1.copy_(b.start)
+        if zi:
+            p2.copy_(b.start2)
+            heldout.fold_in_zi(ct, K, b.lv, b.V, b.pi_d, b.alpha1, b.alpha2, p1, p2, args.iters, 0.0, ws=ws, arithmetic=b.arith)
+        else:
+            heldout.fold_in(ct, K, b.lv, b.alpha1, b.a2_row, p1, args.iters, 0.0, ws=ws)
         ws.timer = None
-
-    lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
 
     def score(timer=None):
         ws.timer = timer
-        call('oriana_gamma_update', ptr(p1), ptr(p2), ptr(torch.empty_like(p2)), ptr(lu), None, None, None, None, None, None, None,
-             None, None, nq, K, stream_ptr())
-        t = engine.zi_cell_bounds(ct, K, p1, p2, lu, lv, V, pi_d, alpha1, alpha2, ws=ws)
+        lu = gamma_expectations(p1, p2)[1]
+        if zi:
+            t = heldout.zi_cell_bounds(ct, K, p1, p2, lu, b.lv, b.V, b.pi_d, b.alpha1, b.alpha2, ws=ws)
+        else:
+            t = heldout.cell_bounds(ct, K, p1, b.a2_row, lu, b.lv, b.sum_v, b.alpha1, b.alpha2, ws=ws)
         ws.timer = None
         return t
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b)
 
     loop()
     t0 = score()                                                     # warm-up of both
@@ -197,127 +205,39 @@ def main_zi_score(args):
     for _ in range(args.reps):
         t_l.append(timed(loop))
         t_s.append(timed(score))
-    same = bool(torch.equal(score(), t0))                            # (within one process the loop ends at one pair or reorders atomics)
-    timer = engine.KernelTimer(prealloc=16)
-    t = score(timer)
-    torch.cuda.synchronize()
-    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
-    timer = engine.KernelTimer(prealloc=8 * args.iters)
-    loop(timer)
-    torch.cuda.synchronize()
-    loop_launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
+    same = bool(torch.equal(score(), t0))                            # (the loop ends at the same shapes every time)
+    t = score()
     per_iter, sc = float(np.median(t_l)) / args.iters, float(np.median(t_s))
     out = {
         'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
-        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps, 'arithmetic': arith,
+        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps}
+    if zi:
+        out['arithmetic'] = b.arith
+    out.update({
         'fold_in_ms_per_iter': round(per_iter, 4), 'fold_in_loop_ms': [round(x, 3) for x in t_l],
         'score_ms': round(sc, 4), 'score_all_ms': [round(x, 3) for x in t_s],
-        'score_over_one_iteration': round(sc / per_iter, 3), 'score_launches': launches, 'loop_launches': loop_launches,
-        'reruns_bit_identical': same, 'mean_score': float((t[:, 0] - t[:, 1] + t[:, 2] - t[:, 3]).mean()),
-        'note': 'score_ms: device events around E[log U] of the final pair + engine.zi_cell_bounds (the mask from the packed counts '
-                'and the allocations of the call\'s own buffers included); zi_cell_bound in score_launches: the logit, sweep and '
-                'combine launches of the entry together; zi_foldin_rate in loop_launches: the rate launch of an iteration',
-    }
-    print(json.dumps(out))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(json.dumps(out, indent=1) + '\n')
-
-
-def main_score(args):
-    """--score: what scoring adds to a fold-in -- one engine.cell_bounds call (two factor preparations, the row pass that leaves
-    s in the row-side slots, oriana_cell_bound_nnz, oriana_gamma_kl_rows, the float64 product) beside one iteration of
-    engine.fold_in on the same new cells and the same fitted gene side as the default mode.  Device events around the whole
-    call / loop, `--reps` times after a warm-up of both, then one call with per-launch events.
-
-        python tools/transform_bench.py --score --fit-rows 131072 --fit-sweeps 5 --out profiles/score_bench.json
-    """
-    import numpy as np
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
-    from oriana_amd import engine
-    from oriana_amd._lib import call, ptr, stream_ptr
-    from oriana_amd.models import GaP
-    from oriana_amd.singlecell import SyntheticCounts
-    dev = torch.device('cuda', 0)
-    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
-    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
-                                           dense_density=engine.auto_dense_density(args.fit_rows, m, K))
-    a1, b1 = gen.initial_shapes()
-    model = GaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
-    del a1, b1
-    model.fit(args.fit_sweeps)
-    torch.cuda.synchronize()
-    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
-    alpha1, alpha2, lv = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat
-    sum_v = (model._accV[0] if model._v_sums_in_acc else model._sumV[0]).clone()
-    a2_row = torch.clamp(alpha2 + sum_v, min=1e-15)
-    ws = engine.ZWorkspace(ct, K)
-    start = (alpha1[None, :] + engine.row_sums_over_k(ws, K).to(torch.float64)).contiguous()
-    a1q = start.clone()
-
-    def loop():
-        a1q.copy_(start)
-        engine.fold_in(ct, K, lv, alpha1, a2_row, a1q, args.iters, 0.0, ws=ws)
-
-    lu = torch.empty(nq, K, dtype=torch.float32, device=dev)
-    a2 = a2_row.expand(nq, K).contiguous()
-
-    def score(timer=None):
-        ws.timer = timer
-        call('oriana_gamma_update', ptr(a1q), ptr(a2), ptr(torch.empty_like(a2)), ptr(lu), None, None, None, None, None, None, None,
-             None, None, nq, K, stream_ptr())
-        t = engine.cell_bounds(ct, K, a1q, a2_row, lu, lv, sum_v, alpha1, alpha2, ws=ws)
-        ws.timer = None
-        return t
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b)
-
-    loop()
-    t0 = score()                                                     # warm-up of both
-    t_l, t_s = [], []
-    for _ in range(args.reps):
-        t_l.append(timed(loop))
-        t_s.append(timed(score))
-    same = bool(torch.equal(score(), t0))                            # (the loop ends at the same a1 every time)
-    timer = engine.KernelTimer(prealloc=16)
-    t = score(timer)
-    torch.cuda.synchronize()
-    launches = {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
-    per_iter, sc = float(np.median(t_l)) / args.iters, float(np.median(t_s))
-    out = {
-        'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
-        'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps,
-        'fold_in_ms_per_iter': round(per_iter, 4), 'fold_in_loop_ms': [round(x, 3) for x in t_l],
-        'score_ms': round(sc, 4), 'score_all_ms': [round(x, 3) for x in t_s],
-        'score_over_one_iteration': round(sc / per_iter, 3), 'score_launches': launches,
-        'reruns_bit_identical': same, 'mean_score': float((t[:, 0] - t[:, 1] - t[:, 2] - t[:, 3]).mean()),
-        'note': 'score_ms: device events around E[log U] of the final shapes + engine.cell_bounds (allocations of the call\'s '
-                'own buffers included); score_launches: per-launch events of one further call (the factor preparations, the '
-                'E[log U] launch and the float64 product are not among them)',
-    }
-    print(json.dumps(out))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(json.dumps(out, indent=1) + '\n')
+        'score_over_one_iteration': round(sc / per_iter, 3), 'score_launches': launches(score, 16)})
+    if zi:
+        out['loop_launches'] = launches(loop, 8 * args.iters)
+    out['reruns_bit_identical'] = same
+    if zi:
+        out['mean_score'] = float((t[:, 0] - t[:, 1] + t[:, 2] - t[:, 3]).mean())
+        out['note'] = ('score_ms: device events around E[log U] of the final pair + heldout.zi_cell_bounds (the mask from the packed '
+                       'counts and the allocations of the call\'s own buffers included); zi_cell_bound in score_launches: the logit, '
+                       'sweep and combine launches of the entry together; zi_foldin_rate in loop_launches: the rate launch of an '
+                       'iteration')
+    else:
+        out['mean_score'] = float((t[:, 0] - t[:, 1] - t[:, 2] - t[:, 3]).mean())
+        out['note'] = ('score_ms: device events around E[log U] of the final shapes + heldout.cell_bounds (allocations of the '
+                       'call\'s own buffers included); score_launches: per-launch events of one further call (the factor '
+                       'preparations, the E[log U] launch and the float64 product are not among them)')
+    emit(out, args)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--zi', action='store_true', help='time ZIGaP.fold_in\'s iteration and its rate launch (see main_zi)')
-    ap.add_argument('--score', action='store_true', help='time one engine.cell_bounds call beside a fold-in iteration (see main_score)')
+    ap.add_argument('--score', action='store_true', help='time one heldout.cell_bounds call beside a fold-in iteration (see main_score)')
     ap.add_argument('--cells', type=int, default=65536)
     ap.add_argument('--genes', type=int, default=30000)
     ap.add_argument('--k', type=int, default=100)
@@ -329,52 +249,23 @@ def main():
     ap.add_argument('--chunk-rows', type=int, default=8192)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if args.zi and args.score:
-        return main_zi_score(args)
+    if args.score:
+        return main_score(args, args.zi)
     if args.zi:
         return main_zi(args)
-    if args.score:
-        return main_score(args)
 
     import numpy as np
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
-    from oriana_amd import engine
+    from oriana_amd import engine, heldout
     from oriana_amd._lib import call, ptr, stream_ptr
-    from oriana_amd.models import GaP
-    from oriana_amd.singlecell import SyntheticCounts
-    dev = torch.device('cuda', 0)
-    nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
-
-    # ---- the fitted gene side -------------------------------------------------------------------------------------------------
-    gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
-                                           dense_density=engine.auto_dense_density(args.fit_rows, m, K))
-    a1, b1 = gen.initial_shapes()
-    model = GaP(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
-    del a1, b1
-    model.fit(args.fit_sweeps)
-    torch.cuda.synchronize()
-
-    # ---- the new cells (same seed: the same V; their own loadings) ------------------------------------------------------------
-    genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    ct = engine.CountTiles.from_chunks(nq, m, genq.chunk, args.chunk_rows, dev, dense_density=None)
-    torch.cuda.synchronize()
-    pack_ms = (time.perf_counter() - t0) * 1e3
-
-    alpha1, alpha2, lv = model.alpha1.tensor, model.alpha2.tensor, model._log_V_hat
-    sum_v = (model._accV[0] if model._v_sums_in_acc else model._sumV[0]).clone()
-    a2_row = torch.clamp(alpha2 + sum_v, min=1e-15)
-    ws_f = engine.ZWorkspace(ct, K)
-    start = (alpha1[None, :] + engine.row_sums_over_k(ws_f, K).to(torch.float64)).contiguous()
+    b = setup(args, zi=False)
+    nq, m, K, ct, dev, ws_f = b.nq, b.m, b.K, b.ct, b.dev, b.ws
+    alpha1, alpha2, lv, sum_v, a2_row, start = b.alpha1, b.alpha2, b.lv, b.sum_v, b.a2_row, b.start
 
     def fused(timer=None):
         ws_f.timer = timer
         a1q = start.clone()
-        engine.fold_in(ct, K, lv, alpha1, a2_row, a1q, args.iters, 0.0, ws=ws_f)
+        heldout.fold_in(ct, K, lv, alpha1, a2_row, a1q, args.iters, 0.0, ws=ws_f)
         ws_f.timer = None
         return a1q
 
@@ -406,15 +297,6 @@ def main():
         ws_c.timer = None
         return a1q
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b)
-
     ra, rb = fused(), composed()                                     # warm-up of every shape the timed loops use
     torch.cuda.synchronize()
     # (from the second iteration on the two loops evaluate the same map: the composed one starts from a2 = 1)
@@ -424,12 +306,7 @@ def main():
         t_f.append(timed(fused))
         t_c.append(timed(composed))
 
-    def breakdown(fn):
-        timer = engine.KernelTimer(prealloc=8 * args.iters)
-        fn(timer)
-        torch.cuda.synchronize()
-        return {k: {'count': c, 'mean_ms': round(ms, 4)} for k, (c, ms) in timer.summary().items()}
-    bf, bc = breakdown(fused), breakdown(composed)
+    bf, bc = launches(fused, 8 * args.iters), launches(composed, 8 * args.iters)
 
     def per_iter(ts):
         return float(np.median(ts)) / args.iters
@@ -443,7 +320,7 @@ def main():
     out = {
         'device': torch.cuda.get_device_name(0), 'cells': nq, 'genes': m, 'k': K, 'nnz': int(ct.nnz), 'iters': args.iters,
         'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps,
-        'pack_ms': round(pack_ms, 2),
+        'pack_ms': round(b.pack_ms, 2),
         'fused_ms_per_iter': round(pf, 4), 'composed_ms_per_iter': round(pc, 4),
         'fused_loop_ms': [round(t, 3) for t in t_f], 'composed_loop_ms': [round(t, 3) for t in t_c],
         'fused_outside_row_pass_ms': round(of, 4), 'composed_outside_row_pass_ms': round(oc, 4),
@@ -454,12 +331,7 @@ def main():
         'note': 'loop times: device events around the whole loop (start launch, host reads of the active counter every 5 '
                 'iterations and the clone of the start included); launches: per-launch events of one further loop',
     }
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(json.dumps(out, indent=1) + '\n')
+    emit(out, args)
 
 
 if __name__ == '__main__':
