@@ -241,6 +241,12 @@ int64_t oriana_prep_den_threshold_offset(void);
 /* R[i,:] = sum_j w_ij s_ij FV[j,:] with s given in row-side slots (sparse models: S_hat-weighted sums). */
 int oriana_row_spmm(const oriana_counts *cm, const float *s_rs, const float *w_nz,
                     const float *FV, float *R, int64_t K, void *stream);
+/* The same product for a fold-in of the sparse models, where most cells are frozen after a few iterations: `active` [n]
+ * bytes in the CALLER's row order (cm->row_perm maps the packed rows onto it).  A work-group none of whose rows (256, 128 or
+ * 64 consecutive packed rows, by K) is active returns at once and leaves its rows of R as they are; the rows of every other
+ * group, active or not, are computed exactly as oriana_row_spmm computes them (bit for bit).  active == NULL is oriana_row_spmm. */
+int oriana_row_spmm_active(const oriana_counts *cm, const float *s_rs, const float *w_nz,
+                           const float *FV, float *R, const uint8_t *active, int64_t K, void *stream);
 
 int oriana_col_pass(const oriana_counts *cm, const float *s_cs,
                     const float *G,         /* (n, Kp) */

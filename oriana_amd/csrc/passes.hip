@@ -160,7 +160,17 @@ static int launch_row_spmm(const oriana_counts *cm, const float *s_rs, const flo
                            float *R, hipStream_t s) {
     return with_variant<0, 1>(w_nz ? 1 : 0, [&](auto HASW) {
         return launch(k_row_spmm<G, T4, TAIL, decltype(HASW)::value != 0>, dim3((unsigned)(cm->nrb * WaveGeo<G>::SPLIT)), dim3(1024),
-                      lds_bytes(KCfg{G, T4, TAIL}), s, *cm, s_rs, w_nz, FV, R);
+                      lds_bytes(KCfg{G, T4, TAIL}), s, *cm, s_rs, w_nz, FV, R, (const uint8_t *)nullptr);
+    });
+}
+
+// the same grid with the skipping mode compiled in (active != NULL)
+template <int G, int T4, int TAIL>
+static int launch_row_spmm_active(const oriana_counts *cm, const float *s_rs, const float *w_nz, const float *FV,
+                                  float *R, const uint8_t *active, hipStream_t s) {
+    return with_variant<0, 1>(w_nz ? 1 : 0, [&](auto HASW) {
+        return launch(k_row_spmm<G, T4, TAIL, decltype(HASW)::value != 0, true>, dim3((unsigned)(cm->nrb * WaveGeo<G>::SPLIT)),
+                      dim3(1024), lds_bytes(KCfg{G, T4, TAIL}), s, *cm, s_rs, w_nz, FV, R, active);
     });
 }
 
@@ -462,6 +472,20 @@ extern "C" int oriana_row_spmm(const oriana_counts *cm, const float *s_rs, const
     if (!R || (cm->m > 0 && !FV) || (cm->rslots > 0 && !s_rs)) return ORIANA_EINVAL;
     hipStream_t s = (hipStream_t)stream;
 #define CALL(G, T, L) return launch_row_spmm<G, T, L>(cm, s_rs, w_nz, FV, R, s)
+    ORIANA_FOR_CFG(cfg, CALL);
+#undef CALL
+}
+
+extern "C" int oriana_row_spmm_active(const oriana_counts *cm, const float *s_rs, const float *w_nz, const float *FV,
+                                      float *R, const uint8_t *active, int64_t K, void *stream) {
+    if (!active) return oriana_row_spmm(cm, s_rs, w_nz, FV, R, K, stream);
+    if (!counts_ok(cm) || K <= 0) return ORIANA_EINVAL;
+    KCfg cfg;
+    if (!pick_cfg(K, &cfg)) return ORIANA_EKRANGE;
+    if (cm->n == 0) return 0;
+    if (!R || (cm->m > 0 && !FV) || (cm->rslots > 0 && !s_rs)) return ORIANA_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(G, T, L) return launch_row_spmm_active<G, T, L>(cm, s_rs, w_nz, FV, R, active, s)
     ORIANA_FOR_CFG(cfg, CALL);
 #undef CALL
 }

@@ -338,11 +338,26 @@ __global__ __launch_bounds__(1024) void k_row_pass(oriana_counts cm, const float
 
 // ------------------------------------------------------------------------------------------
 // row SpMM with given s (row-side slots):  R_i = sum_j w s FV_j
+//   ACT (oriana_row_spmm_active, the fold-in of the sparse models): `active` [n] bytes in the CALLER's row order; a
+//   work-group none of whose WaveGeo<G>::OWN rows is active returns at its top -- the same answer in every lane of every
+//   wave, before any staging or barrier -- and leaves its rows of R as they are.  Every other group runs the code below
+//   unchanged (all of its rows, active or not).  ACT = false compiles the test and the operand out.
 // ------------------------------------------------------------------------------------------
-template <int G, int T4, int TAIL, bool HASW>
+template <int G, int T4, int TAIL, bool HASW, bool ACT = false>
 __global__ __launch_bounds__(1024) void k_row_spmm(oriana_counts cm, const float *__restrict__ s_rs,
                                                    const float *__restrict__ w_nz, const float *__restrict__ FV,
-                                                   float *__restrict__ R) {
+                                                   float *__restrict__ R, const uint8_t *__restrict__ active) {
+    if constexpr (ACT) {
+        constexpr int OWN = WaveGeo<G>::OWN;
+        const int64_t p0 = (int64_t)(blockIdx.x / WaveGeo<G>::SPLIT) * TILE + (int64_t)(blockIdx.x % WaveGeo<G>::SPLIT) * OWN;
+        bool a = false;
+        #pragma unroll
+        for (int o = 0; o < OWN; o += 64) {
+            const int64_t p = p0 + o + (threadIdx.x & 63);
+            if (p < cm.n) a = a || active[cm.row_perm ? (int64_t)cm.row_perm[p] : p] != 0;
+        }
+        if (__ballot(a) == 0ull) return;     // (work-group uniform)
+    }
     constexpr int KP = 4 * G * T4 + G * TAIL;
     constexpr int TOFF = 4 * G * T4;
     constexpr int TREP = (G == 4) ? tail_copies(KP, TAIL) : 1;

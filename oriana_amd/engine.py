@@ -476,6 +476,7 @@ class ZWorkspace:
         self.FU_alt = self.mu_u = self.upart = None
         self.fu_pending = False
         self.fu_source = 0      # data pointer of the E[log U] matrix the pending preparation was made from
+        self.rows_nslab = 1     # slabs of R the last row phase filled (row_gene_splits; 1 after the second row product)
         self._extra = {}
         self._clear_cache = {}
         # gene-range split of the row pass (struct oriana_row_split: short matrices split every row block, long ones the row
@@ -778,6 +779,19 @@ def zq(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, dq=N
         _zq_cols(ws, Z_j, Z_log, log_V_hat, dq, w_nz, finalize_cols, zj_packed, on_segment)
 
 
+def zq_rows_open(ws, Z_i, Z_j, log_U_hat, log_V_hat, S_tilde=None, S_hat=None, active=None):
+    """The row phase of a fold-in (heldout.py): what zq(phase='rows', finalize_rows=False) launches, for the plain nest or --
+    S_tilde, S_hat given -- the sparse one without log sums: factor preparation (masked by S_tilde), FV * S_hat, the two-image
+    row pass where both images fit (Kp <= 64), else the s_rs pass and the second row product, the slow path.  Z_i is left with
+    the slow path's additions only; the caller completes it from the ws.rows_nslab slabs of R (oriana_foldin_update).
+    `active` (uint8 [n], the caller's row order; sparse nest only): the second row product skips the work-groups whose cells are all
+    frozen (oriana_row_spmm_active) -- their rows of R keep whatever they held.  zq() itself keeps refusing finalize_rows = False
+    on every nest but the plain one: a sweep of the sparse models has no consumer of unfinished row sums."""
+    if (S_hat is None) != (S_tilde is None) or (active is not None and S_hat is None):
+        raise ValueError('the sparse row phase takes S_tilde and S_hat together; active belongs to it')
+    _zq_rows(ws, Z_i, Z_j, None, log_U_hat, log_V_hat, S_tilde, S_hat, None, None, False, (), False, active=active)
+
+
 def zq_gap(ws, Z_hat_i, Z_hat_j, log_U_hat, log_V_hat, **kw):
     """GaP.compute_Z_q_expectations (reference gap.py:67-80) on the resident tiles: the plain nest of zq (its keywords)."""
     zq(ws, Z_hat_i, Z_hat_j, None, log_U_hat, log_V_hat, **kw)
@@ -788,8 +802,9 @@ def _have_sliced(ct):
     return ct.ms > 0 or ct.dense is None
 
 
-def _zq_rows(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde, S_hat, dq, w_nz, finalize, clear, zj_packed):
-    """Everything Z_i needs: preparation, row pass, slow path, [second row product], dense genes, finalize rows."""
+def _zq_rows(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde, S_hat, dq, w_nz, finalize, clear, zj_packed, active=None):
+    """Everything Z_i needs: preparation, row pass, slow path, [second row product], dense genes, finalize rows.  Leaves the
+    number of slabs of R it filled in ws.rows_nslab.  `active`: see zq_rows_open (None inside a sweep)."""
     ct, K = ws.ct, ws.K
     n, m = ct.n, ct.m
     sparse = S_hat is not None
@@ -839,7 +854,11 @@ def _zq_rows(ws, Z_i, Z_j, Z_log, log_U_hat, log_V_hat, S_tilde, S_hat, dq, w_nz
                  (1 if sparse else 0) | (2 if w_nz is not None else 0) | (4 if dq is not None else 0) | (8 if zj_packed else 0), st)
         if sparse and not fused:
             with _span(ws, 'row_spmm'):
-                call('oriana_row_spmm', cst, ptr(ws.s_rs), ptr(w_nz), ptr(F2) + goff, ptr(ws.R), K, st)
+                if active is None:
+                    call('oriana_row_spmm', cst, ptr(ws.s_rs), ptr(w_nz), ptr(F2) + goff, ptr(ws.R), K, st)
+                else:
+                    call('oriana_row_spmm_active', cst, ptr(ws.s_rs), ptr(w_nz), ptr(F2) + goff, ptr(ws.R), ptr(active), K, st)
+    ws.rows_nslab = nslab
     if dn is not None:
         # (after the sliced kernels: the dense row kernel ADDS its sums into R; the sliced slow path and the dense row kernel
         #  touch disjoint buffers)

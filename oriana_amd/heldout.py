@@ -1,12 +1,13 @@
 # -*- coding: utf-8 -*-
 """Cells the model was not fitted on: folding them into a fitted gene side (fold_in, fold_in_zi) and each cell's share of the
 variational bound (cell_bounds, zi_cell_bounds), on a ZWorkspace of the call's own.  This module calls into the sweep sequencer of
-engine.py (the row phase of zq_gap); nothing in a sweep calls back."""
+engine.py (the row phase: zq_rows_open, plain or -- S_tilde, S_hat given: the sparse models' project() -- masked); nothing in a
+sweep calls back."""
 import torch
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
-from .engine import ZWorkspace, _span, factor_prep, zq_gap
+from .engine import ZWorkspace, _span, factor_prep, zq, zq_rows_open
 
 _F32, _F64 = torch.float32, torch.float64
 
@@ -32,6 +33,19 @@ def row_sums_over_k(ws, K):
     call('oriana_row_pass', ct.sparse_struct, ptr(ones_u), ptr(ones_v), None, ptr(ws.R), ptr(ws.s_cs), None, None,
          ptr(ws.tile_flag), K, st)
     call('oriana_finalize_slabs_from', ptr(Z), ptr(ones_u), ptr(ws.R), 1, 0, ptr(ct.row_perm), ct.n, K, st)
+    return Z[:ct.n]
+
+
+def masked_row_sums(ws, K, S_tilde, S_hat):
+    """sum_j x_ij S_hat_jk S_tilde_jk / max(1, sum_k S_tilde_jk) per cell and factor, (n, K) float32 in the caller's row order: the
+    sparse row phase of a sweep against E[log U] = E[log V] = 0 (responsibilities uniform over a gene's unmasked factors; a
+    fully masked gene gives nothing).  rowsum(x) / K -- row_sums_over_k -- when nothing is masked and S_hat = 1."""
+    ct = ws.ct
+    f32 = dict(dtype=_F32, device=ct.device)
+    Z, Zj = torch.zeros(max(ct.n, 1), K, **f32), torch.zeros(max(ct.m, 1), K, **f32)
+    ws.fu_pending = False
+    zq(ws, Z[:ct.n], Zj[:ct.m], None, torch.zeros(ct.n, K, **f32), torch.zeros(ct.m, K, **f32), S_tilde=S_tilde, S_hat=S_hat,
+       phase='rows')
     return Z[:ct.n]
 
 
@@ -73,8 +87,10 @@ def _fold_in_buffers(ws, n_iter):
 def _drive(ct, K, log_V_hat, n_iter, tol, check_every, ws, operands, launches):
     """The fold-in loop of both models.  `operands`: (name, tensor, dtype, shape) beside log_V_hat, checked first.
     `launches(ws, tol)`: the model's own set-up, run once the workspace exists; returns start(lu, active), the launch that forms
-    E[log U] and the first FU from the starting shapes, and step(it, rows, ...), the launches of iteration `it`: it calls rows()
-    where the row phase of the sweep belongs and ends with the update launch that counts the cells still active into n_active."""
+    E[log U] and the first FU from the starting shapes, and step(it, rows, ...), the launches of iteration `it`: it calls
+    rows(), or rows(S_tilde, S_hat, active) for the masked row phase of the sparse models, where the row phase of the sweep
+    belongs (ws.rows_nslab then says how many slabs of R it filled) and ends with the update launch that counts the cells still
+    active into n_active."""
     if ct.gd:
         raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
     n, m, dev = ct.n, ct.m, ct.device
@@ -91,9 +107,9 @@ def _drive(ct, K, log_V_hat, n_iter, tol, check_every, ws, operands, launches):
     start, step = launches(ws, tol)
     lu, Zi, Zj, active, left = _fold_in_buffers(ws, n_iter)
     start(lu, active)
-    def rows():
+    def rows(S_tilde=None, S_hat=None, active=None):
         ws.fu_pending, ws.fu_source = True, lu.data_ptr()
-        zq_gap(ws, Zi, Zj, lu, log_V_hat, phase='rows', finalize_rows=False)
+        zq_rows_open(ws, Zi, Zj, lu, log_V_hat, S_tilde=S_tilde, S_hat=S_hat, active=active)
     n_left, done = n, 0
     for it in range(n_iter):
         step(it, rows, lu, Zi, active, froze_at, ptr(left) + 4 * it)
@@ -105,7 +121,14 @@ def _drive(ct, K, log_V_hat, n_iter, tol, check_every, ws, operands, launches):
     return froze_at, n_left, done
 
 
-def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5, ws=None):
+def _masks(m, K, S_tilde, S_hat):
+    """The operands of the masked row phase as _drive checks them: none, or both (m, K) float32."""
+    if (S_tilde is None) != (S_hat is None):
+        raise ValueError('S_tilde and S_hat go together')
+    return () if S_hat is None else (('S_tilde', S_tilde, _F32, (m, K)), ('S_hat', S_hat, _F32, (m, K)))
+
+
+def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5, ws=None, S_tilde=None, S_hat=None):
     """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted pCMF model whose gene side stays as it is: the
     per-cell fixed point of  a1 <- max(1e-15, alpha1 + sum_j x_ij r_ijk),  r_ij. = softmax_k(E[log U]_ik + E[log V]_jk),
     E[log U] = psi(a1) - log a2_row  (gap.py:97-102 with sum_j V_hat frozen).  `a1` (n', K) float64 device tensor: the start,
@@ -114,7 +137,11 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
     validity test + gene-side factor from log_V_hat through the new tiles' gene order, row pass, slow path) and ONE launch of
     oriana_foldin_update, which completes Z_i, updates a1 / E[log U], freezes the cells that moved by at most tol * a1 and
     prepares the next row pass's FU in place.  The host reads the number of active cells every `check_every` iterations
-    and stops at zero.  Returns (froze_at int32 [n'] -- the 0-based iteration a cell froze at, n_iter if never --, the number
+    and stops at zero.
+    S_tilde, S_hat (m, K) float32 (SparseGaP.project(): log_V_hat is then E[log V'], a2_row = alpha2 + sum_j S_hat V'_hat): the
+    row phase is the sparse models' -- e_ijk = exp(lu + lv) S_tilde_jk, sums weighted with S_hat_jk, sparse_gap.py:81-97 -- the
+    two-image row pass for Kp <= 64, else the s_rs pass and oriana_row_spmm_active over the cells still active; only read.
+    Returns (froze_at int32 [n'] -- the 0-based iteration a cell froze at, n_iter if never --, the number
     of cells still active, the iterations run)."""
     n = ct_new.n
     def launches(ws, tol):
@@ -123,17 +150,19 @@ def fold_in(ct_new, K, log_V_hat, alpha1, a2_row, a1, n_iter, tol, check_every=5
             call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), None, None, None, ptr(a2_row), None, None, None, 1, 0,
                  perm, n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
         def step(it, rows, lu, Zi, active, froze_at, n_active):
-            rows()
+            rows() if S_hat is None else rows(S_tilde, S_hat, active)
             with _span(ws, 'foldin_update'):
                 call('oriana_foldin_update', ptr(a1), ptr(lu), ptr(active), ptr(froze_at), n_active, ptr(alpha1), ptr(a2_row),
-                     ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0, perm, n, K, tol, it,
+                     ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.rows_nslab, ws.row_slab_row0, perm, n, K, tol, it,
                      ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
         return start, step
 
-    return _drive(ct_new, K, log_V_hat, n_iter, tol, check_every, ws, (('a1', a1, _F64, (n, K)),), launches)
+    return _drive(ct_new, K, log_V_hat, n_iter, tol, check_every, ws,
+                  (('a1', a1, _F64, (n, K)),) + _masks(ct_new.m, K, S_tilde, S_hat), launches)
 
 
-def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter, tol, check_every=5, ws=None, arithmetic=1):
+def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter, tol, check_every=5, ws=None, arithmetic=1,
+               S_tilde=None, S_hat=None):
     """Fold the cells of `ct_new` (CountTiles, sliced layout) into a fitted ZI-pCMF model whose gene side stays as it is: per
     cell the fixed point of the pair (a1, a2) under zigap.py:115-136 with V_hat, E[log V] and pi_d frozen --
       a1' = max(1e-15, alpha1 + sum_j x_ij r_ijk)        (the pCMF row pass: D_hat = f32(1 - 1e-10) = 1 at the non-zeros)
@@ -147,7 +176,10 @@ def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter
     stored: no (n', m) matrix exists at any point -- and ONE oriana_foldin_update_zi launch updates the pair, U_hat, E[log U],
     freezes the cells that moved by at most tol in both halves and prepares the next row pass's FU in place.  The per-gene
     operands are padded to a multiple of 4 genes with inert ones (V_hat row 0, pi_d 0), as the models do; both non-zero masks
-    come from the packed counts, once per call.  Returns (froze_at, cells still active, iterations run) as fold_in."""
+    come from the packed counts, once per call.
+    S_tilde, S_hat (m, K) float32 (SparseZIGaP.project(): log_V_hat is then E[log V'] and V_hat the effective S_hat * V'_hat,
+    which both the posterior d and the rate read, sparse_zigap.py:138-140, 163-169): the masked row phase, as fold_in.
+    Returns (froze_at, cells still active, iterations run) as fold_in."""
     n, m, dev = ct_new.n, ct_new.m, ct_new.device
     if K > 128 and not ct_new.gd:
         raise ValueError('the zero-inflated fold-in serves K <= 128 (the float32 dense kernels), got K = %d' % K)
@@ -165,17 +197,18 @@ def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter
                  None, None, 1, 0, perm, n, K, tol, 0, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
         def step(it, rows, lu, Zi, active, froze_at, n_active):
             rate.zero_()
-            rows()
+            rows() if S_hat is None else rows(S_tilde, S_hat, active)
             with _span(ws, 'zi_foldin_rate'):
                 call('oriana_zi_foldin_rate', ptr(rate), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(nztiles), ptr(active),
                      ptr(scratch), int(arithmetic), n, mp, K, st)
             with _span(ws, 'foldin_update'):
                 call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), ptr(froze_at), n_active,
-                     ptr(alpha1), ptr(alpha2), ptr(rate), ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.row_gene_splits, ws.row_slab_row0,
+                     ptr(alpha1), ptr(alpha2), ptr(rate), ptr(Zi), ptr(ws.FU), ptr(ws.R), ws.rows_nslab, ws.row_slab_row0,
                      perm, n, K, tol, it, ptr(ws.FU), ptr(ws.mu_u), ptr(ws.upart), st)
         return start, step
 
     operands = (('a1', a1, _F64, (n, K)), ('a2', a2, _F64, (n, K)), ('V_hat', V_hat, _F64, (m, K)), ('pi_d', pi_d, _F64, (m,)))
+    operands += _masks(m, K, S_tilde, S_hat)
     return _drive(ct_new, K, log_V_hat, n_iter, tol, check_every, ws, operands, launches)
 
 

@@ -313,8 +313,8 @@ class FactorModel:
 
     # Folding new cells into a fitted model exists for pCMF only (models/gap.py).  A new cell of the zero-inflated models needs
     # a dropout posterior of its own (p_d over its zeros, which the cell-side rate then reads through D_hat^T), and the sparse
-    # models' responsibilities run against the masked gene images (S_tilde, S_hat): neither is the frozen-gene-side iteration
-    # of oriana_foldin_update.
+    # models' responsibilities run against the masked gene images (S_tilde, S_hat): neither is transform()'s iteration.  ZIGaP has
+    # fold_in() and the sparse models project() (models/zigap.py), each under a name of its own.
     _no_transform = ('transform() is defined for pCMF (GaP) only: folding a new cell into a zero-inflated model needs the dropout '
                      'posterior of that unseen cell, and the sparse models evaluate the responsibilities against masked gene '
                      'images; neither fold-in is implemented')
@@ -342,9 +342,10 @@ class FactorModel:
             raise ValueError('%s walks the sliced layout only: pack the new counts without dense_density' % what)
         return ct
 
-    def _fold_in_start(self, ct, ws, init):
+    def _fold_in_start(self, ct, ws, init, masks=None):
         """The a1 (n', K) float64 a fold-in of `ct` starts from: `init` (checked, copied to the device), by default
-        alpha1 + rowsum(x) / K (uniform responsibilities, no RNG; `ws`: the call's workspace); clamped as the sweeps clamp."""
+        alpha1 + rowsum(x) / K (uniform responsibilities, no RNG; `ws`: the call's workspace) -- with `masks` = (S_tilde, S_hat)
+        of the sparse models uniform over each gene's unmasked factors (heldout.masked_row_sums); clamped as the sweeps clamp."""
         K, dev, nq = self.k, self.device, ct.n
         if init is not None:
             a1 = init if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init, dtype=np.float64))
@@ -352,7 +353,8 @@ class FactorModel:
                 raise ValueError('init must be an (n\', k) array of starting shapes, got %s' % (tuple(a1.shape),))
             a1 = a1.to(device=dev, dtype=torch.float64, copy=True)
         elif nq > 0:
-            a1 = self.alpha1.tensor[None, :] + heldout.row_sums_over_k(ws, K).to(torch.float64)
+            Z = heldout.row_sums_over_k(ws, K) if masks is None else heldout.masked_row_sums(ws, K, *masks)
+            a1 = self.alpha1.tensor[None, :] + Z.to(torch.float64)
         else:
             a1 = torch.empty(0, K, dtype=torch.float64, device=dev)
         return torch.clamp(torch.nan_to_num(a1), min=1e-15).contiguous()

@@ -233,6 +233,61 @@ class _SparseMixin:
         self._touch()
 
 
+    # ---- folding in new cells ----------------------------------------------------------------------------------------------
+    # With the gene side (E[log V'], V'_hat, p_s, pi_d) and the priors held fixed, the cell side of a sparse sweep
+    # (sparse_gap.py:81-97, 118-122; sparse_zigap.py:100-116, 138-144, 163-169) is a fixed-point iteration of each new cell alone:
+    # the responsibilities run against the masked gene images (S_tilde = p_s > tau in the denominator, S_hat = float32(p_s) on the
+    # sums) and every rate reads the effective factor S_hat * V'_hat.  heldout.fold_in / fold_in_zi run it with those operands,
+    # all formed here at call time into buffers of the call's own: nothing the model or its workspace hold is written -- not
+    # _S_tilde, which the thresholding launch of a sweep owns ("Sparse models: project()").
+    project_unconverged_ = None
+    _no_transform = ('transform() is defined for pCMF (GaP) only: the sparse models evaluate a new cell\'s responsibilities against '
+                     'the masked gene images (S_tilde, S_hat) and its rate against S_hat * Vprime_hat -- call project() instead')
+
+    def project(self, cmatrix, n_iter=200, tol=1e-4, init=None, return_params=False, check_every=5):
+        """Fold new cells into the fitted model: E[U] of `cmatrix` (anything the constructor takes, or a prebuilt sliced
+        CountTiles; the same genes) as a host (n', K) float64 array; V', p_s (and pi_d) and the priors stay as they are.
+        SparseGaP: E[U] = a1 / a2_row with a2_row = alpha2 + sum_j S_hat V'_hat, which never moves; each cell iterates its a1 until
+        it moves by at most tol * a1 in every factor, as GaP.transform().  SparseZIGaP: E[U] = a1 / a2 of the cell's own pair,
+        the rate reading the cell's dropout posterior (never stored), until both halves move by at most tol (relative), as
+        ZIGaP.fold_in(); K <= 128.  A cell that met the criterion is frozen -- its result does not depend on the other cells or
+        on a longer budget -- ``project_unconverged_`` counts those that never did within `n_iter`.  `init`: (n', K) starting a1
+        (default alpha1 + sum_j x_ij S_hat_jk S_tilde_jk / max(1, sum_k S_tilde_jk): responsibilities uniform over each gene's
+        unmasked factors, no RNG); a2 starts at alpha2 + sum_j S_hat V'_hat.  return_params=True: (E[U], a1, a2_row [K] --
+        SparseZIGaP: a2 (n', K) --, the 0-based iteration each cell froze at, n_iter for those that did not).  Under row
+        sharding the call is local to the rank: no collective."""
+        ct = self._query_counts(cmatrix, 'project()')
+        K, nq, m = self.k, ct.n, self.m
+        if self.zi and K > 128:
+            raise ValueError('project() serves K <= 128 on the zero-inflated model (the float32 dense kernels of the sweep), '
+                             'got k = %d' % K)
+        st = stream_ptr()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        p_s = self.p_s.tensor.contiguous()
+        S_tilde = torch.empty(m, K, **f32)                       # (the call's own: _S_tilde belongs to the sweep)
+        call('oriana_threshold_f32', ptr(S_tilde), ptr(p_s), float(self.tau), m * K, st)                # sparse_gap.py:113
+        S_hat = p_s.to(torch.float32)                            # Bernoulli.mean (bernoulli.py:45)
+        Veff = torch.empty(m, K, dtype=torch.float64, device=self.device)
+        call('oriana_mul_f64_f32', ptr(Veff), ptr(self._V_hat.contiguous()), ptr(S_hat), m * K, st)    # sparse_gap.py:118
+        alpha1, alpha2 = self.alpha1.tensor, self.alpha2.tensor
+        a2_row = torch.clamp(torch.nan_to_num(alpha2 + Veff.sum(dim=0)), min=1e-15)
+        ws = engine.ZWorkspace(ct, K) if nq > 0 else None
+        a1 = self._fold_in_start(ct, ws, init, masks=(S_tilde, S_hat))
+        kw = dict(check_every=check_every, ws=ws, S_tilde=S_tilde, S_hat=S_hat)
+        if self.zi:
+            rate = a2_row[None, :].expand(nq, K).contiguous()
+            froze_at, left, _ = heldout.fold_in_zi(ct, K, self._log_V_hat, Veff, self.pi_d.tensor.contiguous(), alpha1, alpha2, a1,
+                                                   rate, n_iter, tol, arithmetic=self._matrix_arith, **kw)
+        else:
+            rate = a2_row
+            froze_at, left, _ = heldout.fold_in(ct, K, self._log_V_hat, alpha1, a2_row, a1, n_iter, tol, **kw)
+        self.project_unconverged_ = int(left)
+        E = (a1 / rate).cpu().numpy()
+        if return_params:
+            return E, a1.cpu().numpy(), rate.cpu().numpy(), froze_at.cpu().numpy()
+        return E
+
+
 class ZIGaP(_ZIMixin, FactorModel):
     """ZI-pCMF (reference zigap.py:15-165)."""
     zi = True

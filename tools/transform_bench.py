@@ -8,6 +8,8 @@ around whole loops (after a warm-up loop of each form, the two forms alternating
 form with per-launch events for the share spent outside the row pass.  Prints one JSON line; `--out` also writes it to a file.
 `--zi`: the zero-inflated fold-in instead (main_zi below).  `--score`: one heldout.cell_bounds call beside one fold-in iteration
 (main_score below).  `--zi --score`: one heldout.zi_cell_bounds call beside one ZI fold-in iteration (main_score too).
+`--sparse [--zi]`: one iteration of SparseGaP / SparseZIGaP.project()'s loop per K of `--sparse-ks`, and the second row product
+with and without the active bytes (main_sparse below).
 
     python tools/transform_bench.py --out profiles/transform_bench.json
 """
@@ -24,23 +26,25 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def setup(args, zi):
-    """What every mode times against: a model (ZIGaP if `zi`, else GaP) fitted on `--fit-rows` cells for `--fit-sweeps` sweeps,
-    the new cells packed on the sliced layout (same seed: the same V; their own loadings), a workspace over them and the
-    default start of a fold-in.  Returns a namespace of them and of the model's gene side as the fold-in reads it."""
+def setup(args, zi, sparse=False):
+    """What every mode times against: a model (ZIGaP if `zi`, else GaP; `sparse`: SparseZIGaP / SparseGaP) fitted on `--fit-rows`
+    cells for `--fit-sweeps` sweeps, the new cells packed on the sliced layout (same seed: the same V; their own loadings), a
+    workspace over them and the default start of a fold-in.  Returns a namespace of them and of the model's gene side as the
+    fold-in reads it."""
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('transform_bench needs a GPU: there is nothing to time without one')
     from oriana_amd import engine, heldout
-    from oriana_amd.models import GaP, ZIGaP
+    from oriana_amd.models import GaP, SparseGaP, SparseZIGaP, ZIGaP
     from oriana_amd.singlecell import SyntheticCounts
     dev = torch.device('cuda', 0)
     nq, m, K, seed = args.cells, args.genes, args.k, 1234 + 1000 * 4
     gen = SyntheticCounts(args.fit_rows, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
     counts = engine.CountTiles.from_chunks(args.fit_rows, m, gen.chunk, args.chunk_rows, dev,
-                                           dense_density=None if zi else engine.auto_dense_density(args.fit_rows, m, K))
+                                           dense_density=None if zi or sparse else engine.auto_dense_density(args.fit_rows, m, K))
     a1, b1 = gen.initial_shapes()
-    model = (ZIGaP if zi else GaP)(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
+    cls = (SparseZIGaP if zi else SparseGaP) if sparse else (ZIGaP if zi else GaP)
+    model = cls(counts, k=K, use_factors=False, init=(a1, b1), device=dev)
     del a1, b1
     model.fit(args.fit_sweeps)
     genq = SyntheticCounts(nq, m, K, seed=seed, device=dev, zero_inflation_level=args.zeros)
@@ -50,6 +54,8 @@ def setup(args, zi):
     torch.cuda.synchronize()
     b = SimpleNamespace(dev=dev, nq=nq, m=m, K=K, model=model, ct=ct, pack_ms=(time.perf_counter() - t0) * 1e3,
                         alpha1=model.alpha1.tensor, alpha2=model.alpha2.tensor, lv=model._log_V_hat, ws=engine.ZWorkspace(ct, K))
+    if sparse:
+        return b
     b.start = (b.alpha1[None, :] + heldout.row_sums_over_k(b.ws, K).to(torch.float64)).contiguous()
     if zi:
         b.V, b.pi_d, b.arith = model._V_hat.contiguous(), model.pi_d.tensor.contiguous(), model._matrix_arith
@@ -234,8 +240,104 @@ def main_score(args, zi):
     emit(out, args)
 
 
+def main_sparse(args, zi):
+    """--sparse [--zi]: a REPORT, no threshold.  Per K of `--sparse-ks` (50: the two-image row pass; 100: the s_rs pass and the
+    second row product): a sparse model fitted as `setup` fits it, then -- a few sweeps from the generator's start leave p_s ~ 1 --
+    a p_s of this tool's own loaded over it (U(0, 1) entries, every third gene at 0.1 in every factor: fully masked); one
+    iteration of project()'s loop (heldout.fold_in / fold_in_zi with the masks, tol = 0, `--iters` iterations, device events
+    around the loop, `--reps` times after a warm-up) and its per-launch events; where the row phase has a second row product,
+    its share of the iteration and the launch alone in three forms on the loop's own operands -- oriana_row_spmm,
+    oriana_row_spmm_active with every cell active, and with every other 256-row block frozen -- alternating, 10 back-to-back
+    launches between two device events, 5 repetitions.  `active_all_not_slower`: the all-active form's median is not above
+    oriana_row_spmm's by more than the spread (max - min) of the repetitions.
+
+        python tools/transform_bench.py --sparse --cells 16384 --genes 20000 --fit-rows 16384 --fit-sweeps 3 \
+            --out profiles/sparse_project_bench.json
+    """
+    import numpy as np
+    import torch
+    from oriana_amd import heldout
+    from oriana_amd._lib import call, ptr, stream_ptr
+    runs = []
+    for K in [int(k) for k in args.sparse_ks.split(',')]:
+        args.k = K
+        b = setup(args, zi, sparse=True)
+        nq, m, ct, ws, dev, model = b.nq, b.m, b.ct, b.ws, b.dev, b.model
+        P = torch.rand(m, K, dtype=torch.float64, device=dev, generator=torch.Generator(device=dev).manual_seed(K))
+        P[::3] = 0.1
+        model.load_state({'p_s': P.cpu().numpy()})
+        model.update_expectations()
+        S_tilde = (P > model.tau).to(torch.float32)
+        S_hat = P.to(torch.float32)
+        Veff = (model._V_hat * S_hat).contiguous()
+        a2_row = torch.clamp(b.alpha2 + Veff.sum(0), min=1e-15)
+        start = (b.alpha1[None, :] + heldout.masked_row_sums(ws, K, S_tilde, S_hat).to(torch.float64)).contiguous()
+        start2 = a2_row[None, :].expand(nq, K).contiguous()
+
+        def loop(timer=None):
+            ws.timer = timer
+            p1 = start.clone()
+            if zi:
+                heldout.fold_in_zi(ct, K, b.lv, Veff, model.pi_d.tensor.contiguous(), b.alpha1, b.alpha2, p1, start2.clone(),
+                                   args.iters, 0.0, ws=ws, arithmetic=model._matrix_arith, S_tilde=S_tilde, S_hat=S_hat)
+            else:
+                heldout.fold_in(ct, K, b.lv, b.alpha1, a2_row, p1, args.iters, 0.0, ws=ws, S_tilde=S_tilde, S_hat=S_hat)
+            ws.timer = None
+
+        loop()                                                           # warm-up
+        t_loop = [timed(loop) for _ in range(args.reps)]
+        ll = launches(loop, 8 * args.iters)
+        per_iter = float(np.median(t_loop)) / args.iters
+        run = {'k': K, 'cells': nq, 'genes': m, 'nnz': int(ct.nnz), 'fully_masked_genes': float((S_tilde.sum(1) == 0).double().mean()),
+               'row_phase': 'two-launch' if 'row_spmm' in ll else 'two-image', 'rows_nslab': ws.rows_nslab,
+               'loop_ms_per_iter': round(per_iter, 4), 'loop_ms': [round(t, 3) for t in t_loop], 'loop_launches': ll}
+        if 'row_spmm' in ll:
+            sp = ll['row_spmm']
+            run['second_product_share'] = round(sp['mean_ms'] * sp['count'] / args.iters / per_iter, 4)
+            st, cs = stream_ptr(), ct.sparse_struct
+            F2 = ws.extra('FVS', m)
+            all_on = torch.ones(nq, dtype=torch.uint8, device=dev)
+            half = torch.ones(nq, dtype=torch.uint8, device=dev)
+            blocks = torch.arange(nq, device=dev) // 256
+            packed_off = (blocks % 2 == 1)
+            # (the bytes are in the caller's row order: the packed rows of every other block, through the row permutation)
+            half[(ct.row_perm.long() if ct.row_perm is not None else torch.arange(nq, device=dev))[packed_off]] = 0
+
+            def plain():
+                for _ in range(10):
+                    call('oriana_row_spmm', cs, ptr(ws.s_rs), None, ptr(F2), ptr(ws.R), K, st)
+
+            def active(a):
+                def run_():
+                    for _ in range(10):
+                        call('oriana_row_spmm_active', cs, ptr(ws.s_rs), None, ptr(F2), ptr(ws.R), ptr(a), K, st)
+                return run_
+            forms = {'row_spmm': plain, 'active_all': active(all_on), 'active_half_blocks_frozen': active(half)}
+            for f in forms.values():
+                f()                                                      # warm-up
+            ts = {name: [] for name in forms}
+            for _ in range(5):
+                for name, f in forms.items():
+                    ts[name].append(timed(f) / 10)
+            med = {name: float(np.median(v)) for name, v in ts.items()}
+            spread = max(max(ts[n]) - min(ts[n]) for n in ('row_spmm', 'active_all'))
+            run['second_product'] = {
+                'ms': {n: round(v, 4) for n, v in med.items()}, 'all_ms': {n: [round(t, 4) for t in v] for n, v in ts.items()},
+                'spread_ms': round(spread, 4), 'active_all_not_slower': bool(med['active_all'] - med['row_spmm'] <= spread),
+                'frozen_share_of_cells': float((half == 0).double().mean())}
+        runs.append(run)
+    emit({'device': torch.cuda.get_device_name(0), 'model': 'SparseZIGaP' if zi else 'SparseGaP', 'iters': args.iters,
+          'fit_rows': args.fit_rows, 'fit_sweeps': args.fit_sweeps, 'reps': args.reps, 'runs': runs,
+          'note': 'loop times: device events around the whole loop (start launch, host reads of the active counter every 5 iterations '
+                  'and the clone of the start included), tol = 0: no cell freezes inside the loop; second_product: 10 back-to-back '
+                  'launches between two device events per figure, the three forms alternating, 5 repetitions; p_s is the tool\'s '
+                  'own (every third gene fully masked), loaded over the fitted model'}, args)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--sparse', action='store_true', help='time project()\'s iteration and the second row product (see main_sparse)')
+    ap.add_argument('--sparse-ks', default='50,100', help='the K of --sparse, comma-separated')
     ap.add_argument('--zi', action='store_true', help='time ZIGaP.fold_in\'s iteration and its rate launch (see main_zi)')
     ap.add_argument('--score', action='store_true', help='time one heldout.cell_bounds call beside a fold-in iteration (see main_score)')
     ap.add_argument('--cells', type=int, default=65536)
@@ -249,6 +351,8 @@ def main():
     ap.add_argument('--chunk-rows', type=int, default=8192)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.sparse:
+        return main_sparse(args, args.zi)
     if args.score:
         return main_score(args, args.zi)
     if args.zi:
