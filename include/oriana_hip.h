@@ -521,6 +521,31 @@ int oriana_gamma_update_finalize_lazy(double *a1, double *a2_row, float *Elog,
                                  const double *rate_vec, int64_t r, int64_t K, float *FU_next, float *mu_out, float *upart,
                                  void *stream);
 
+/* The GLOBAL step of a streaming fit (oriana_amd/models/gap.py: partial_fit; stochastic variational inference, no counterpart
+ * in the reference): the gene side of oriana_gamma_update with the batch's estimate BLENDED into the shapes and rates the model
+ * holds, one launch.  Z (m, K) float32 = sum_{i in batch} x_ij r_ijk at the batch's converged cell side, sum_u [K] float64 =
+ * sum_{i in batch} E[U_ik], scale = n_total / n_batch, rho in [0, 1] the step size:
+ *   b1 = max(1e-15, nan_to_num((1 - rho) * b1 + rho * (beta1[k] + scale * Z[j,k])))
+ *   b2 = max(1e-15, nan_to_num((1 - rho) * b2 + rho * (beta2[k] + scale * sum_u[k])))          (b1, b2 (m, K) float64, in place)
+ *   E = b1 / b2 (f64);  Elog = f32(digamma(f32(b1))) - logf(f32(b2));  colsum_E / colsum_Elog [K] += their column sums (f64;
+ *   zero them first, either may be NULL) -- the arithmetic of oriana_gamma_update on a stored pair, element for element.
+ * The convex form makes rho = 0 leave b1, b2 bit for bit and rho = 1 give the batch estimate bit for bit (at scale = 1:
+ * every output of oriana_gamma_update with rate_vec = sum_u); (1 - rho) is formed once, in float64, on the host.  Each value
+ * takes three float64 roundings, by explicit FMAs -- fma(scale, stat, prior), rho * that, fma(1 - rho, b, it) --, so every
+ * kernel configuration below gives the same bits.
+ * F == NULL: Z is complete and only read.  F != NULL: the finalize form, as oriana_gamma_update_finalize -- rows are walked in
+ * the PACKED gene order p of the batch's tiles, Z[o,k] += F[p,k] * sum_s R[s][p,k] with o = row_index ? row_index[p] : p
+ * (R = (nslab, m, Kp), F (m, Kp); Z is completed in place) and blended at once: the batch's column pass runs without its
+ * finalize launch.  Every K with oriana_kpad(K) != 0 and any pointer alignment is served (odd K above 64 and buffers that are
+ * not 16-byte aligned by an element-per-lane kernel); ORIANA_EKRANGE for K above 256, ORIANA_EINVAL for rho outside [0, 1] or
+ * a scale that is negative or not finite. */
+int oriana_svi_gene_update(double *b1, double *b2, double *E, float *Elog,
+                           double *colsum_E, double *colsum_Elog,
+                           const double *beta1, const double *beta2,
+                           float *Z, const float *F, const float *R, int64_t nslab, const int32_t *row_index,
+                           const double *sum_u, double scale, double rho,
+                           int64_t m, int64_t K, void *stream);
+
 /* The step between two row passes of a FOLD-IN (oriana_amd/models/gap.py: transform; no counterpart in the reference): pCMF's
  * cell-side update for cells the model was not fitted on, the gene side frozen -- per cell a fixed-point iteration of
  *   a1 <- max(1e-15, alpha1 + Z_i),  Z_i = Z + F * sum_slabs R  (as oriana_gamma_update_finalize_lazy: packed rows, nslab, slab_row0,

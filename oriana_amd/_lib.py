@@ -108,6 +108,7 @@ _SIGS = {
     'oriana_gamma_update_prep': (c_int, [_P] * 13 + [_I, _I, _P, _P, _P, _P]),
     'oriana_gamma_update_finalize_prep': (c_int, [_P] * 11 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     'oriana_gamma_update_finalize_lazy': (c_int, [_P] * 10 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    'oriana_svi_gene_update': (c_int, [_P] * 11 + [_I, _P, _P, c_double, c_double, _I, _I, _P]),
     'oriana_foldin_update_blocks': (_I, [_I]),
     'oriana_foldin_update': (c_int, [_P] * 10 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),
     'oriana_foldin_update_zi': (c_int, [_P] * 13 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),

@@ -542,6 +542,184 @@ __global__ __launch_bounds__(256) void k_foldin_update(const FoldinArgs A) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The GLOBAL step of a streaming fit (models/gap.py partial_fit; stochastic variational inference, Hoffman et al. 2013): the
+// gene side of k_gamma_update / k_gamma_update_vec with the shapes and rates BLENDED into what the model holds instead of
+// replaced -- per gene j (FIN: per packed gene p, o = row_index[p], Z[o] += F[p] * sum_slabs R[p] first, as k_finalize) --
+//   b1 = max(1e-15, nan_to_num(omr * b1 + rho * (beta1_k + scale * Z[j,k])))        omr = 1 - rho, formed once on the host
+//   b2 = max(1e-15, nan_to_num(omr * b2 + rho * (beta2_k + scale * sum_u[k])))
+// then E = b1 / b2, Elog = gamma_meanlog_f32(b1, b2) and their column sums exactly as the Z == NULL form of k_gamma_update
+// forms them from a stored pair.  The convex form: rho = 0 multiplies the old value by 1 and adds 0 (b stays bit for bit),
+// rho = 1 multiplies it by 0 (the batch estimate bit for bit, the pair of k_gamma_update at scale = 1).  b2 is a matrix: a loaded state need not hold the same rate in every gene.
+struct SviArgs {
+    double *b1, *b2, *E;
+    float *Elog;
+    double *colsum_E, *colsum_Elog;
+    const double *beta1, *beta2;
+    float *Z;
+    const float *F, *R;
+    const int32_t *row_index;
+    const double *sum_u;
+    double scale, rho, omr;
+    int64_t r;
+    int K, Kp, nslab, rpb;
+};
+
+// (explicit FMAs, three roundings per value -- prior + scale * stat, rho * that, omr * old + it: every instantiation below
+//  then forms the same bits, whatever the compiler would have contracted)
+__device__ __forceinline__ double svi_target(double prior, double scale, double stat) { return fma(scale, stat, prior); }
+__device__ __forceinline__ double svi_blend(double old, double target, double rho, double omr) {
+    return clamp_eps(fma(omr, old, rho * target));
+}
+
+// the element-per-lane form: the mapping and the reduction of k_gamma_update<FIN, 256>
+template <bool FIN>
+__global__ __launch_bounds__(256) void k_svi_gene_update(const SviArgs A) {
+    constexpr int NT = 256;
+    __shared__ double red[2][NT];
+    const int KT = blockDim.x, RY = blockDim.y, K = A.K, Kp = A.Kp;
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int64_t r = A.r;
+    const int64_t r0 = (int64_t)blockIdx.x * A.rpb;
+    const int64_t r1 = (r0 + A.rpb < r) ? r0 + A.rpb : r;
+    double p1[GU_MAXCOLS_PER_THREAD], t2[GU_MAXCOLS_PER_THREAD], sE[GU_MAXCOLS_PER_THREAD], sL[GU_MAXCOLS_PER_THREAD];
+    #pragma unroll
+    for (int c = 0; c < GU_MAXCOLS_PER_THREAD; ++c) {
+        const int k = tx + c * KT;
+        p1[c] = k < K ? A.beta1[k] : 1.0;
+        t2[c] = k < K ? svi_target(A.beta2[k], A.scale, A.sum_u[k]) : 1.0;
+        sE[c] = 0.0; sL[c] = 0.0;
+    }
+    for (int64_t row = r0 + ty; row < r1; row += RY) {
+        const int64_t orow = (FIN && A.row_index) ? (int64_t)A.row_index[row] : row;
+        #pragma unroll
+        for (int c = 0; c < GU_MAXCOLS_PER_THREAD; ++c) {
+            const int k = tx + c * KT;
+            if (k < K) {
+                const int64_t idx = orow * K + k;
+                float z = A.Z[idx];
+                if (FIN) {
+                    float rr = A.R[row * Kp + k];
+                    for (int sl = 1; sl < A.nslab; ++sl) rr += A.R[((int64_t)sl * r + row) * Kp + k];
+                    z = fmaf(A.F[row * Kp + k], rr, z) + 0.0f;                                     // k_finalize (accumulate)
+                    A.Z[idx] = z;
+                }
+                const double s1 = svi_blend(A.b1[idx], svi_target(p1[c], A.scale, (double)z), A.rho, A.omr);
+                const double s2 = svi_blend(A.b2[idx], t2[c], A.rho, A.omr);
+                A.b1[idx] = s1;
+                A.b2[idx] = s2;
+                const double e = s1 / s2;                                // gamma.py:37-46
+                const float el = gamma_meanlog_f32(s1, s2);              // gamma.py:52-61
+                A.E[idx] = e;
+                A.Elog[idx] = el;
+                sE[c] += e;
+                sL[c] += (double)el;
+            }
+        }
+    }
+    const int flat = ty * KT + tx, lane = flat & 63, wv = flat >> 6, NW = NT / 64;
+    const int kw = KT < 64 ? KT : 64;                  // distinct columns inside a wave
+    #pragma unroll
+    for (int c = 0; c < GU_MAXCOLS_PER_THREAD; ++c) {
+        if (c * KT >= K) break;                        // (uniform: no thread holds a column of this round)
+        const int k = tx + c * KT;
+        double vE = sE[c], vL = sL[c];
+        for (int off = kw; off < 64; off <<= 1) { vE += __shfl_xor(vE, off); vL += __shfl_xor(vL, off); }
+        __syncthreads();
+        if (lane < kw) {
+            red[0][wv * kw + lane] = vE;
+            red[1][wv * kw + lane] = vL;
+        }
+        __syncthreads();
+        if (ty == 0 && k < K) {
+            double tE = 0.0, tL = 0.0;
+            if (KT <= 64) {
+                for (int w = 0; w < NW; ++w) { tE += red[0][w * kw + tx]; tL += red[1][w * kw + tx]; }
+            } else {
+                // KT = 128: rows of threads span two waves; wave 2y + (tx >> 6) holds columns (tx & 63) of row y
+                for (int w = (tx >> 6); w < NW; w += 2) { tE += red[0][w * kw + (tx & 63)]; tL += red[1][w * kw + (tx & 63)]; }
+            }
+            if (A.colsum_E) atomicAdd(&A.colsum_E[k], tE);
+            if (A.colsum_Elog) atomicAdd(&A.colsum_Elog[k], tL);
+        }
+    }
+}
+
+// VEC consecutive factors per lane, LPR lanes per row: the mapping and the reduction of k_gamma_update_vec
+template <bool FIN, int VEC, int LPR>
+__global__ __launch_bounds__(256) void k_svi_gene_update_vec(const SviArgs A) {
+    constexpr int RPW = 64 / LPR, NW = 4, NCOL = LPR * VEC;
+    __shared__ double red[2][NW][NCOL];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int cg = lane & (LPR - 1), sr = lane / LPR;
+    const int k0 = cg * VEC, K = A.K, Kp = A.Kp;
+    const bool act = k0 < K;
+    const int64_t r = A.r;
+    const int64_t r0 = (int64_t)blockIdx.x * A.rpb;
+    const int64_t r1 = (r0 + A.rpb < r) ? r0 + A.rpb : r;
+    double p1[VEC], t2[VEC], sE[VEC], sL[VEC];
+    #pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        p1[v] = act ? A.beta1[k0 + v] : 1.0;
+        t2[v] = act ? svi_target(A.beta2[k0 + v], A.scale, A.sum_u[k0 + v]) : 1.0;
+        sE[v] = 0.0; sL[v] = 0.0;
+    }
+    for (int64_t rb = r0 + w * RPW; rb < r1; rb += NW * RPW) {
+        const int64_t row = rb + sr;
+        if (act && row < r1) {
+            const int64_t orow = (FIN && A.row_index) ? (int64_t)A.row_index[row] : row;
+            const int64_t idx = orow * K + k0;
+            float z[VEC], el[VEC];
+            double s1[VEC], s2[VEC], e[VEC];
+            ld_f32<VEC>(z, A.Z + idx);
+            if (FIN) {
+                float rr[VEC], f[VEC];
+                ld_f32<VEC>(rr, A.R + row * Kp + k0);
+                ld_f32<VEC>(f, A.F + row * Kp + k0);
+                for (int sl = 1; sl < A.nslab; ++sl) {
+                    float r2[VEC];
+                    ld_f32<VEC>(r2, A.R + ((int64_t)sl * r + row) * Kp + k0);
+                    #pragma unroll
+                    for (int v = 0; v < VEC; ++v) rr[v] += r2[v];
+                }
+                #pragma unroll
+                for (int v = 0; v < VEC; ++v) z[v] = fmaf(f[v], rr[v], z[v]) + 0.0f;                 // k_finalize (accumulate)
+                st_f32<VEC>(A.Z + idx, z);
+            }
+            ld_f64<VEC>(s1, A.b1 + idx);
+            ld_f64<VEC>(s2, A.b2 + idx);
+            #pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                s1[v] = svi_blend(s1[v], svi_target(p1[v], A.scale, (double)z[v]), A.rho, A.omr);
+                s2[v] = svi_blend(s2[v], t2[v], A.rho, A.omr);
+                e[v] = s1[v] / s2[v];                                                       // gamma.py:37-46
+                el[v] = gamma_meanlog_f32(s1[v], s2[v]);                                    // gamma.py:52-61
+                sE[v] += e[v];
+                sL[v] += (double)el[v];
+            }
+            st_f64<VEC>(A.b1 + idx, s1);
+            st_f64<VEC>(A.b2 + idx, s2);
+            st_f64<VEC>(A.E + idx, e);
+            st_f32<VEC>(A.Elog + idx, el);
+        }
+    }
+    // column sums: lanes holding the same factors inside the wave, then the four waves through LDS
+    #pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        double vE = sE[v], vL = sL[v];
+        #pragma unroll
+        for (int o = LPR; o < 64; o <<= 1) { vE += __shfl_xor(vE, o, 64); vL += __shfl_xor(vL, o, 64); }
+        if (sr == 0) { red[0][w][k0 + v] = vE; red[1][w][k0 + v] = vL; }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const double tE = ((red[0][0][k] + red[0][1][k]) + red[0][2][k]) + red[0][3][k];
+        const double tL = ((red[1][0][k] + red[1][1][k]) + red[1][2][k]) + red[1][3][k];
+        if (A.colsum_E) atomicAdd(&A.colsum_E[k], tE);
+        if (A.colsum_Elog) atomicAdd(&A.colsum_Elog[k], tL);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_colsum_f64(double *__restrict__ out, const double *__restrict__ A,
                                                     const float *__restrict__ mul, int64_t r, int K, int rpb) {
     __shared__ double red[256];
@@ -970,6 +1148,56 @@ extern "C" int oriana_gamma_update_finalize(double *a1, double *a2, double *E, f
                                             const double *rate_vec, int64_t r, int64_t K, void *stream) {
     return oriana_gamma_update_finalize_prep(a1, a2, E, Elog, colsum_E, colsum_Elog, prior1, prior2, Z, F, R, nslab, 0, row_index,
                                              rate_vec, r, K, nullptr, nullptr, nullptr, stream);
+}
+
+template <bool FIN, int VEC>
+static void svi_vec_launch_lpr(const SviArgs &a, int lpr, int64_t nblk, hipStream_t s) {
+    const dim3 g((unsigned)nblk), b(256);
+    switch (lpr) {
+    case 8: hipLaunchKernelGGL((k_svi_gene_update_vec<FIN, VEC, 8>), g, b, 0, s, a); break;
+    case 16: hipLaunchKernelGGL((k_svi_gene_update_vec<FIN, VEC, 16>), g, b, 0, s, a); break;
+    case 32: hipLaunchKernelGGL((k_svi_gene_update_vec<FIN, VEC, 32>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((k_svi_gene_update_vec<FIN, VEC, 64>), g, b, 0, s, a); break;
+    }
+}
+
+// the configuration of gu_vec_cfg for this K and these pointers; the element-per-lane kernel for what it leaves out (odd K
+// above 64, buffers that are not 16-byte aligned at a K above 64).  No gu_small rule: a call sits behind a whole fold-in.
+template <bool FIN>
+static void svi_launch(SviArgs a, hipStream_t s) {
+    const bool wide_ok = aligned_to(a.b1, 16) && aligned_to(a.b2, 16) && aligned_to(a.E, 16) && aligned_to(a.Elog, 16) &&
+                         aligned_to(a.Z, 16) && aligned_to(a.F, 16) && aligned_to(a.R, 16);
+    int vec, lpr;
+    if (gu_vec_cfg(a.K, wide_ok, &vec, &lpr)) {
+        a.rpb = gu_vec_rpb(a.r, lpr);
+        const int64_t nblk = (a.r + a.rpb - 1) / a.rpb;
+        if (vec == 4) svi_vec_launch_lpr<FIN, 4>(a, lpr, nblk, s);
+        else if (vec == 2) svi_vec_launch_lpr<FIN, 2>(a, lpr, nblk, s);
+        else svi_vec_launch_lpr<FIN, 1>(a, lpr, nblk, s);
+        return;
+    }
+    dim3 block;
+    pick_block(a.K, &block, 256);
+    a.rpb = rows_per_block(a.r, (int)block.y);
+    hipLaunchKernelGGL((k_svi_gene_update<FIN>), dim3((unsigned)((a.r + a.rpb - 1) / a.rpb)), block, 0, s, a);
+}
+
+extern "C" int oriana_svi_gene_update(double *b1, double *b2, double *E, float *Elog, double *colsum_E, double *colsum_Elog,
+                                      const double *beta1, const double *beta2, float *Z, const float *F, const float *R,
+                                      int64_t nslab, const int32_t *row_index, const double *sum_u, double scale, double rho,
+                                      int64_t m, int64_t K, void *stream) {
+    if (m < 0 || K <= 0 || !(rho >= 0.0 && rho <= 1.0) || !(scale >= 0.0 && scale < INFINITY)) return ORIANA_EINVAL;
+    if (F && (nslab < 1 || nslab > 65535)) return ORIANA_EINVAL;
+    const int64_t Kp = oriana_kpad(K);
+    if (Kp == 0) return ORIANA_EKRANGE;
+    if (m == 0) return 0;
+    if (!b1 || !b2 || !E || !Elog || !beta1 || !beta2 || !Z || !sum_u || (F && !R)) return ORIANA_EINVAL;
+    const SviArgs a = {b1, b2, E, Elog, colsum_E, colsum_Elog, beta1, beta2, Z, F, F ? R : nullptr, F ? row_index : nullptr, sum_u,
+                       scale, rho, 1.0 - rho, m, (int)K, (int)Kp, F ? (int)nslab : 1, 0};
+    if (F) svi_launch<true>(a, (hipStream_t)stream);
+    else svi_launch<false>(a, (hipStream_t)stream);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int oriana_colsum_f64(double *out, const double *A, const float *mul, int64_t r, int64_t K, void *stream) {

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """Cells the model was not fitted on: folding them into a fitted gene side (fold_in, fold_in_zi) and each cell's share of the
-variational bound (cell_bounds, zi_cell_bounds), on a ZWorkspace of the call's own.  This module calls into the sweep sequencer of
+variational bound (cell_bounds, zi_cell_bounds), and -- a streaming fit's global step, GaP.partial_fit -- a folded-in batch's
+per-gene statistics and their blend into the gene side (gene_statistics, svi_gene_update), on a ZWorkspace of the call's own.  This module calls into the sweep sequencer of
 engine.py (the row phase: zq_rows_open, plain or -- S_tilde, S_hat given: the sparse models' project() -- masked); nothing in a
 sweep calls back."""
 import torch
@@ -8,6 +9,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .engine import ZWorkspace, _span, factor_prep, zq, zq_rows_open
+from .nodes import gamma_expectations
 
 _F32, _F64 = torch.float32, torch.float64
 
@@ -210,6 +212,52 @@ def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter
     operands = (('a1', a1, _F64, (n, K)), ('a2', a2, _F64, (n, K)), ('V_hat', V_hat, _F64, (m, K)), ('pi_d', pi_d, _F64, (m,)))
     operands += _masks(m, K, S_tilde, S_hat)
     return _drive(ct_new, K, log_V_hat, n_iter, tol, check_every, ws, operands, launches)
+
+
+def gene_statistics(ct, K, a1, a2_row, log_V_hat, ws=None, finalize=True):
+    """The per-gene sufficient statistics of a folded-in batch (GaP.partial_fit, the global step of a streaming fit): at the
+    batch's final shapes a1 (n', K) float64 and the rate a2_row [K] every cell shares,
+      Z_j[j,k] = sum_{i in batch} x_ij softmax_k(lu_i. + lv_j.),  lu = float32(psi(a1) - log a2_row) UNSHIFTED, from the Gamma node's
+                 own kernel (nodes.gamma_expectations: what score_samples() evaluates the bound at), lv = log_V_hat (m, K) float32;
+      sum_u[k] = sum_{i in batch} a1_ik / a2_row_k   (float64).
+    ONE full plain responsibility pass (engine.zq_gap: factor preparation, row pass, slow path, column pass) over the batch's
+    own tiles on `ws`, a ZWorkspace over `ct` -- the one the fold-in ran on (its in-place FU arrangement and the pending
+    preparation are reset here: this pass prepares both factors from lu and log_V_hat) or None for a fresh one.  The cell
+    sums of the pass are not completed: nothing reads them.
+    Returns (Z_j (m, K) float32, sum_u); with finalize=False the first is (Z_j, F, C, row_index) instead -- Z_j then holds the
+    slow path's additions only and Z_j[row_index[p]] += F[p] * C[p] is left to the caller (oriana_svi_gene_update folds it
+    into the blend: one launch and one pass over Z_j less).  Nothing in a sweep calls this."""
+    n, m, dev = ct.n, ct.m, ct.device
+    if ct.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    for name, t, dtype, shape in (('log_V_hat', log_V_hat, _F32, (m, K)), ('a1', a1, _F64, (n, K)), ('a2_row', a2_row, _F64, (K,))):
+        _operand(name, t, dtype, shape)
+    sum_u = (a1 / a2_row).sum(dim=0)
+    Zj = torch.zeros(max(m, 1), K, dtype=_F32, device=dev)
+    if n == 0:
+        return (Zj[:m] if finalize else (Zj[:m], None, None, None)), sum_u
+    if ws is None:
+        ws = ZWorkspace(ct, K)
+    else:
+        ws.fu_pending, ws.prep_blocks = False, 0
+        ws.FU_alt = ws.mu_u = ws.upart = None
+    lu = gamma_expectations(a1, a2_row.expand(n, K).contiguous())[1]
+    Zi = torch.empty(n, K, dtype=_F32, device=dev)
+    zq(ws, Zi, Zj[:m], None, lu, log_V_hat, finalize_rows=False, finalize_cols=finalize)
+    return (Zj[:m] if finalize else (Zj[:m], ws.FV, ws.C, ct.col_perm)), sum_u
+
+
+def svi_gene_update(b1, b2, V_hat, log_V_hat, sums, beta1, beta2, stats, sum_u, scale, rho, ws=None):
+    """The blend of a streaming fit's global step, ONE oriana_svi_gene_update launch, everything in place:
+      b1 <- max(1e-15, (1 - rho) b1 + rho (beta1 + scale Z_j)),   b2 <- max(1e-15, (1 - rho) b2 + rho (beta2 + scale sum_u)),
+    V_hat = b1 / b2, log_V_hat = float32 E[log V] and their column sums into `sums` (2, K) float64, zeroed here.
+    `stats`: Z_j complete, or gene_statistics' unfinished (Z_j, F, C, row_index).  `ws`: whose timer the launch reports to."""
+    m, K = b1.shape
+    Zj, F, C, perm = stats if isinstance(stats, tuple) else (stats, None, None, None)
+    sums.zero_()
+    with _span(ws, 'svi_gene_update'):
+        call('oriana_svi_gene_update', ptr(b1), ptr(b2), ptr(V_hat), ptr(log_V_hat), ptr(sums[0]), ptr(sums[1]), ptr(beta1),
+             ptr(beta2), ptr(Zj), ptr(F), ptr(C), 1, ptr(perm), ptr(sum_u), float(scale), float(rho), m, K, stream_ptr())
 
 
 PI_D_FLOOR = 1e-10                # the override values of zigap.py:133-134: pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)

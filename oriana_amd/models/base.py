@@ -395,6 +395,17 @@ class FactorModel:
         """The mean of score_samples() (GaP); NotImplementedError on the other models."""
         raise NotImplementedError(self._no_score)
 
+    # Streaming updates from cell batches exist for pCMF only (models/gap.py): the global step is a natural-gradient step on the
+    # bound of elbo(), and the other models' sweeps ascend no single bound (see _no_elbo above).
+    _no_partial_fit = ('partial_fit() is defined for pCMF (GaP) only: its global step is a natural-gradient step on the variational '
+                       'bound of elbo(), and the zero-inflated and sparse updates of the reference are not coordinate ascent on '
+                       'one stated bound, so there is no such gradient to follow for them')
+
+    def partial_fit(self, cmatrix, n_total, rho=None, tau0=1.0, kappa=0.7, n_iter=200, tol=1e-4, init=None, check_every=5):
+        """One stochastic variational update of the gene side from a batch of cells (GaP); NotImplementedError on the other
+        models."""
+        raise NotImplementedError(self._no_partial_fit)
+
     def factors(self):
         """base.py:97-98: (U[:], V[:]) as host arrays."""
         return self.U[:], self.V[:]

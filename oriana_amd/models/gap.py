@@ -230,6 +230,56 @@ class GaP(FactorModel):
         different k on cells none of them was fitted on."""
         return self._mean_score(self.score_samples(cmatrix, **kw))
 
+    # ---- streaming fits ----------------------------------------------------------------------------------------------------
+    # Stochastic variational inference (Hoffman et al. 2013; for Poisson factorisation Gopalan et al.): a batch of cells the
+    # model does not hold is folded in against the current gene side (the LOCAL step: exactly the fold-in of transform()), its
+    # per-gene sufficient statistics at the converged cell side are scaled to the population, n_total / n_B, and blended into
+    # b1, b2 with a step size rho (the GLOBAL step, a natural-gradient step on the bound of elbo()):
+    #   b1 <- (1 - rho) b1 + rho (beta1 + scale Z_j),   b2 <- (1 - rho) b2 + rho (beta2 + scale sum_{i in B} E[U_i.])
+    # The priors stay where the fit left them and the model's own cells are not touched.  It needs a gene side that already
+    # separates the factors -- fit on what is resident, then stream the rest (DESIGN.md, "Streaming fits: partial_fit()").
+    n_batches_ = 0
+    partial_fit_rho_ = None
+    partial_fit_unconverged_ = None
+
+    def partial_fit(self, cmatrix, n_total, rho=None, tau0=1.0, kappa=0.7, n_iter=200, tol=1e-4, init=None, check_every=5):
+        """One stochastic variational update of the gene side from a batch of cells: `cmatrix` (anything transform() takes, a
+        prebuilt sliced ``engine.CountTiles`` included: epochs need not repack) is a sample of a population of `n_total` cells.
+        The batch is folded in as transform() folds it (`n_iter`, `tol`, `init`, `check_every`; ``partial_fit_unconverged_`` counts
+        the cells that never froze), and b1, b2 move towards the batch's estimate by the step size `rho` in [0, 1] -- default
+        min(1, (tau0 + n_batches_) ** -kappa), tau0 > 0, kappa in (0.5, 1]; the value used is kept in ``partial_fit_rho_`` and
+        ``n_batches_`` counts the non-empty calls.  V_hat, E[log V] and their column sums follow in the same launch, so step(),
+        elbo(), transform() and score() read the streamed gene side; the priors and the model's own cell side stay as they
+        are (a later step() is ordinary CAVI on the construction cells).  An empty batch changes nothing.  Returns self."""
+        if self.sharded:
+            raise NotImplementedError('partial_fit() under row sharding is not implemented: the batch statistics of the ranks '
+                                      'would need a collective of their own')
+        tau0, kappa = float(tau0), float(kappa)
+        if not tau0 > 0.0:
+            raise ValueError('partial_fit needs tau0 > 0, got %r' % (tau0,))
+        if not 0.5 < kappa <= 1.0:
+            raise ValueError('partial_fit needs kappa in (0.5, 1], got %r' % (kappa,))
+        if rho is not None and not 0.0 <= float(rho) <= 1.0:
+            raise ValueError('partial_fit needs rho in [0, 1], got %r' % (rho,))
+        ct = self._query_counts(cmatrix)
+        if not int(n_total) >= ct.n:
+            raise ValueError('partial_fit needs n_total >= the %d cells of the batch, got %r' % (ct.n, n_total))
+        if ct.n == 0:
+            return self
+        rho = min(1.0, (tau0 + self.n_batches_) ** -kappa) if rho is None else float(rho)
+        kept = self.transform_unconverged_
+        ct, ws, a1, a2_row, _, _ = self._fold_in_cells(ct, n_iter, tol, init, check_every)
+        self.partial_fit_unconverged_, self.transform_unconverged_ = self.transform_unconverged_, kept
+        stats, sum_u = heldout.gene_statistics(ct, self.k, a1, a2_row, self._log_V_hat, ws=ws, finalize=False)
+        # what load_state() would leave: the pair, its expectations and their column sums where the next sweep reads them
+        heldout.svi_gene_update(self.b1.tensor, self.b2.tensor, self._V_hat, self._log_V_hat, self._sumV, self.beta1.tensor,
+                                self.beta2.tensor, stats, sum_u, float(int(n_total)) / ct.n, rho, ws=ws)
+        self._v_sums_in_acc = False
+        self._touch()
+        self.n_batches_ += 1
+        self.partial_fit_rho_ = rho
+        return self
+
     def _init_extra(self):
         if os.environ.get('ORIANA_LAZY_U', '1') != '0':
             from ..parameters import LazyParameter
