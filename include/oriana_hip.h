@@ -545,6 +545,17 @@ int oriana_svi_gene_update(double *b1, double *b2, double *E, float *Elog,
                            float *Z, const float *F, const float *R, int64_t nslab, const int32_t *row_index,
                            const double *sum_u, double scale, double rho,
                            int64_t m, int64_t K, void *stream);
+/* oriana_svi_gene_update with the rate statistic as an (m, K) float64 matrix in the caller's gene order (ZI-pCMF: a gene's rate
+ * reads the dropout posterior of its own zeros, oriana_zi_gene_rate):
+ *   b2 = max(1e-15, nan_to_num((1 - rho) * b2 + rho * (beta2[k] + scale * rate[j,k])))
+ * -- one flag through the same kernels, the same three FMAs per value: a matrix whose every row is sum_u gives the bits of the
+ * vector entry.  Everything else as above. */
+int oriana_svi_gene_update_mat(double *b1, double *b2, double *E, float *Elog,
+                               double *colsum_E, double *colsum_Elog,
+                               const double *beta1, const double *beta2,
+                               float *Z, const float *F, const float *R, int64_t nslab, const int32_t *row_index,
+                               const double *rate, double scale, double rho,
+                               int64_t m, int64_t K, void *stream);
 
 /* The step between two row passes of a FOLD-IN (oriana_amd/models/gap.py: transform; no counterpart in the reference): pCMF's
  * cell-side update for cells the model was not fitted on, the gene side frozen -- per cell a fixed-point iteration of
@@ -699,6 +710,26 @@ int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const do
 int64_t oriana_zi_cell_bound_scratch_doubles(int64_t n, int64_t m, int64_t K);
 int oriana_zi_cell_bound(double *out, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
                          double *scratch, int64_t n, int64_t m, int64_t m_real, int64_t K, void *stream);
+/* The gene-side rate statistic of a batch folded into a ZI model (ZIGaP.fold_in_fit, heldout.zi_gene_rate), the
+ * dropout posterior formed tile by tile and never stored:
+ *   G[j, k] = sum_{i < n} d_ij U[i, k]   (m, K) float64,      dsum[j] = sum_{i < n} d_ij   [m] float64,
+ *   d_ij = 1 where x_ij != 0; 1e-10 / 1 in the columns with pi_d <= 0 / >= 1; else f32(sigmoid(logit(pi_d_j) - U_i . V_j))
+ * -- the d of oriana_zi_foldin_rate (k_logit_f32's +-inf flags, not the clamped logits of the bound).  U (n, K), V (m, K),
+ * pi_d [m] float64; nzmask in the oriana_nzmask_f32 layout with ld = m (oriana_nzmask_counts); m a multiple of 4 with inert
+ * padding genes (V row 0, pi_d 0), whose rows of G and dsum the caller drops.  K <= 128 (else ORIANA_EKRANGE): the float32 matrix
+ * instruction (csrc/dense_f32.hip, k_gene_rate -- the transposed twin of k_dropout_sweep).  Sums leave the matrix core every 256
+ * cells and float32 every 4096; a gene's d are added 16 at a time in float32, then in float64, and in a column with pi_d <= 0
+ * dsum is nnz_j + 1e-10 (n - nnz_j) in float64.  The cell axis is cut into S = oriana_zi_gene_rate_ranges(n, m, K) <= 32 ranges
+ * that start on multiples of 32 (S ceil(m / 128) stays within two work-groups per compute unit, so the partials never exceed
+ * 256 rows of K doubles per compute unit whatever n and m);
+ * every range WRITES its partial to scratch and a second launch adds the S partials in order: no atomics, G and dsum need not
+ * be zeroed, every element is written, reruns are bit-identical.
+ * scratch: oriana_zi_gene_rate_scratch_doubles(n, m, K) = S (m K + m) + 32 ceil(m / 64) doubles.
+ * ORIANA_EINVAL on a missing pointer or K <= 0; n == 0 writes zeros; 0 for m == 0 before any HIP call. */
+int64_t oriana_zi_gene_rate_ranges(int64_t n, int64_t m, int64_t K);
+int64_t oriana_zi_gene_rate_scratch_doubles(int64_t n, int64_t m, int64_t K);
+int oriana_zi_gene_rate(double *G, double *dsum, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
+                        double *scratch, int64_t n, int64_t m, int64_t K, void *stream);
 /* out[m, K] += D_hat^T W[n, K] (zigap.py:124), D_hat streamed once; `out` must be initialised.  arithmetic as above;
  * scratch: oriana_dense_t_scratch_floats(n, K) floats (16-byte aligned; the bf16 operand images of W), may be NULL
  * with ORIANA_MATRIX_F32. */

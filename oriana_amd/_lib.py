@@ -109,6 +109,7 @@ _SIGS = {
     'oriana_gamma_update_finalize_prep': (c_int, [_P] * 11 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     'oriana_gamma_update_finalize_lazy': (c_int, [_P] * 10 + [_I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     'oriana_svi_gene_update': (c_int, [_P] * 11 + [_I, _P, _P, c_double, c_double, _I, _I, _P]),
+    'oriana_svi_gene_update_mat': (c_int, [_P] * 11 + [_I, _P, _P, c_double, c_double, _I, _I, _P]),
     'oriana_foldin_update_blocks': (_I, [_I]),
     'oriana_foldin_update': (c_int, [_P] * 10 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),
     'oriana_foldin_update_zi': (c_int, [_P] * 13 + [_I, _I, _P, _I, _I, c_double, _I, _P, _P, _P, _P]),
@@ -126,6 +127,9 @@ _SIGS = {
     'oriana_zi_foldin_rate': (c_int, [_P] * 8 + [c_int, _I, _I, _I, _P]),
     'oriana_zi_cell_bound_scratch_doubles': (_I, [_I, _I, _I]),
     'oriana_zi_cell_bound': (c_int, [_P] * 6 + [_I, _I, _I, _I, _P]),
+    'oriana_zi_gene_rate_ranges': (_I, [_I, _I, _I]),
+    'oriana_zi_gene_rate_scratch_doubles': (_I, [_I, _I, _I]),
+    'oriana_zi_gene_rate': (c_int, [_P] * 7 + [_I, _I, _I, _P]),
     'oriana_dense_t_times_factor_f32': (c_int, [_P, _P, _P, _P, c_int, _I, _I, _I, _P]),
     'oriana_dense_t_scratch_floats': (_I, [_I, _I]),
     'oriana_factor_cast_f32': (c_int, [_P, _P, _P, _P, _I, _I, _P]),

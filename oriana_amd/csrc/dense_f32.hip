@@ -10,6 +10,10 @@
 //   oriana_dense_t_times_factor_f32   out[m, K] += D_hat^T W[n, K]  (zigap.py:124), D_hat streamed once.
 //   oriana_zi_cell_bound         the dropout term of a held-out cell's bound: the sweep kernel's Lambda^T = V U^T with the epilogue
 //                                z or softplus(z), z = logit(pi~) - Lambda, summed per cell in a fixed order (float32 instruction, K <= 128).
+//   oriana_zi_gene_rate          the gene-side rate statistic of a folded-in batch (ZIGaP.fold_in_fit): G = d^T U_hat and the column sums
+//                                of d, d the dropout posterior of the fold-in, never stored -- the sweep kernel transposed (genes resident,
+//                                cell tiles walked: Lambda = U V^T), partials per cell range WRITTEN and combined in order (float32
+//                                instruction, K <= 128; the sums leave float32 every 4096 cells).
 //
 // Numerics.  v_mfma_f32_32x32x2_f32 is a chain of single-rounding FMAs in k order, round-to-nearest-even
 // (tools/ubench/mfma_f32.hip: bit-identical to a host fmaf() chain): a sum of T positive terms carries an unbiased
@@ -1123,9 +1127,310 @@ static int launch_bound(double *partial, const double *U, const double *V, const
                   nzmask, partial, nullptr, nullptr, n, m, K, KP2, cut.jps, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// oriana_zi_gene_rate: the gene-side rate statistic of a folded-in batch (ZIGaP.fold_in_fit),
+//   G[j, k] = sum_i d_ij U[i, k],   dsum[j] = sum_i d_ij,   d the dropout posterior of oriana_zi_foldin_rate, never stored.
+// The transposed twin of k_dropout_sweep<NT, true>: a work-group holds 4 strips of 32 GENES (the V strips resident in LDS,
+// [k][gene]) and walks a range of CELL tiles, each staged in both images ([k][cell] and [cell][k]) by the sweep kernel's
+// staging.  Lambda[cell, gene] = U V^T on the matrix core (A = the U tile, B = the wave's V strip), so a lane's 16 accumulator
+// registers are 16 cells of ONE gene (c = lane & 31): the logit and its two overrides (k_logit_f32's +-inf flags) live in a
+// register, the non-zero bits of the tile's 32 cells are one mask word per lane, and after the sigmoid the registers are the
+// A operand of  G[gene, k] += d[gene, cell] U[cell, k].
+// G stays in registers across the tiles: out of the matrix core every 256 cells (float32, as the sweep kernel), and every 4096
+// cells into the range's own partial in float64 (a plain read-modify-write of memory no other work-group touches), so the
+// float32 part of a sum never holds more than 16 pieces whatever the batch.  dsum: a tile's 16 values per lane in float32,
+// the tiles in float64; cells i >= n have U = 0 (nothing to G) and d zeroed (nothing to dsum).  In a column with pi_d <= 0,
+// float32 cannot hold 1 + 1e-10: its dsum is nnz + 1e-10 (cells - nnz) from the mask's population count, in float64.
+// Every range WRITES its partials, k_gene_rate_combine adds them in order: no atomics, nothing pre-zeroed.
+struct GeneLds {
+    int vs, ut, u2, dm, total;
+    int u2s;                      // row stride of the [cell][k] image (as SweepLds::v2s)
+    __host__ __device__ GeneLds(int KP2, int NT) {
+        u2s = NT * 32 + 8;
+        int o = 0;
+        vs = o; o += 4 * KP2 * 32;           // [wave][k][32 genes], resident
+        ut = o; o += 2 * KP2 * 32;           // [buf][k][32 cells]
+        u2 = o; o += 2 * 32 * u2s;           // [buf][32 cells][k]
+        dm = o; o += 32;                     // where the staging writes of k >= KP2 land
+        total = o;
+    }
+};
+
+template <int NT>
+__global__ __launch_bounds__(256, (NT <= 2) ? 2 : 1) void k_gene_rate(double *__restrict__ Gp, double *__restrict__ dp,
+                                                                      const double *__restrict__ U, const double *__restrict__ V,
+                                                                      const float *__restrict__ lgit,
+                                                                      const uint32_t *__restrict__ nzmask, int64_t n, int64_t m,
+                                                                      int K, int KP2, int64_t i_per_split) {
+    extern __shared__ float lds[];
+    const GeneLds L(KP2, NT);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    const int64_t j0w = (int64_t)blockIdx.x * 128 + w * 32;
+    const int64_t ib = (int64_t)blockIdx.y * i_per_split;        // a multiple of 32: whole mask words
+    const int64_t ie = (ib + i_per_split < n) ? ib + i_per_split : n;
+    const int KS = KP2 >> 1;
+    float *Vs = lds + L.vs + w * KP2 * 32;
+
+    // the wave's strip of V_hat, [k][gene]
+    for (int e = lane; e < KP2 * 32; e += 64) {
+        const int g = e / KP2, kk = e - g * KP2;
+        const int64_t j = j0w + g;
+        Vs[kk * 32 + g] = (j < m && kk < K) ? (float)V[j * K + kk] : 0.f;
+    }
+    // the lane's gene: its logit, and the address of its mask words (clamped: a gene >= m is computed and dropped)
+    const int64_t jl = j0w + c;
+    const bool jok = jl < m;
+    const int64_t jc = jok ? jl : m - 1;
+    const float lg = lgit[jc];
+
+    // staging of one cell tile, 8 threads per cell (k_dropout_sweep's, both images from the same registers)
+    const int sg = tid >> 3, sk = tid & 7;
+    constexpr int NU = NT * 4;
+    double sreg[NU];
+    bool sok = false;
+    auto stage_load = [&](int64_t i0) {
+        const int64_t i = i0 + sg;
+        sok = i < ie;
+        const int64_t ic = sok ? i : ie - 1;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int kk = sk + 8 * u;
+            sreg[u] = U[ic * K + (kk < K ? kk : K - 1)];
+        }
+    };
+    auto stage_store = [&](int buf) {
+        float *ut = lds + L.ut + buf * KP2 * 32;
+        float *u2 = lds + L.u2 + buf * 32 * L.u2s;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int kk = sk + 8 * u;
+            const float x = (sok && kk < K) ? (float)sreg[u] : 0.f;
+            (kk < KP2 ? ut + kk * 32 : lds + L.dm)[sg] = x;
+            u2[sg * L.u2s + kk] = x;
+        }
+    };
+
+    f16v dv[NT], dvs[NT];                                       // matrix-core accumulators; their sums every 256 cells
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) { dv[nt][v] = 0.f; dvs[nt][v] = 0.f; }
+    }
+    // the range's partial of G: written the first time, added to after that
+    bool spilled = false;
+    auto spill = [&]() {
+        int64_t row0 = (int64_t)blockIdx.y * m + j0w;
+        asm volatile("" : "+v"(row0));                           // the 64 addresses are formed here, not kept across the tiles
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int64_t j = j0w + acc_row(v, h);
+                const int k = nt * 32 + c;
+                if (j < m && k < K) {
+                    double *p = Gp + (row0 + acc_row(v, h)) * K + k;
+                    const double s = (double)dvs[nt][v] + (double)dv[nt][v];
+                    *p = spilled ? *p + s : s;
+                }
+                dvs[nt][v] = 0.f; dv[nt][v] = 0.f;
+            }
+        spilled = true;
+    };
+    double bsum = 0.0;                                           // sum of d over this lane half's cells of the lane's gene
+    int64_t nnz = 0;                                             // non-zero counts of the lane's gene in the range
+    uint32_t mk = 0;
+
+    if (ib < ie) {
+        stage_load(ib);
+        mk = nzmask[(ib >> 5) * m + jc];
+        stage_store(0);
+    }
+    __syncthreads();
+    int buf = 0, since_flush = 0, flushes = 0;
+    for (int64_t i0 = ib; i0 < ie; i0 += 32) {
+        const int64_t in = (i0 + 32 < ie) ? i0 + 32 : i0;        // (the last tile again: unused)
+        const uint32_t mkc = mk;
+        stage_load(in);
+        mk = nzmask[(in >> 5) * m + jc];
+        ORIANA_VMEM_FENCE();
+        // ---- Lambda = U V^T: k_dropout_sweep's turns with the operands exchanged
+        const float *ut = lds + L.ut + buf * KP2 * 32;
+        f16v l0;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) l0[v] = 0.f;
+        {
+            const float *pa = ut + h * 32 + c, *pb = Vs + h * 32 + c;
+            float a[4], b[4], an[4], bn[4];
+            int s = 0;
+            if (KS >= 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { a[u] = pa[64 * u]; b[u] = pb[64 * u]; }
+                for (; s + 8 <= KS; s += 4) {
+                    pa += 256; pb += 256;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { an[u] = pa[64 * u]; bn[u] = pb[64 * u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) l0 = mfma32(a[u], b[u], l0);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { a[u] = an[u]; b[u] = bn[u]; }
+                }
+                pa += 256; pb += 256;
+                const int rem = KS - s - 4;
+#pragma unroll
+                for (int u = 0; u < 3; ++u) { const int o = (u < rem) ? 64 * u : 0; an[u] = pa[o]; bn[u] = pb[o]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) l0 = mfma32(a[u], b[u], l0);
+#pragma unroll
+                for (int u = 0; u < 3; ++u) if (u < rem) l0 = mfma32(an[u], bn[u], l0);
+            } else {
+                for (; s < KS; ++s) l0 = mfma32(pa[64 * s], pb[64 * s], l0);
+            }
+        }
+        // ---- sigmoid, overrides: register v of lane half h is cell acc_row(v, h) of the tile
+        const int irem = (ie - i0 < 32) ? (int)(ie - i0) : 32;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            if ((v & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+            const float x = lg - l0[v];
+            float p = __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+            if (lg == -INFINITY) p = 1e-10f;                     // pi_d <= 0                         zigap.py:133
+            if ((mkc >> acc_row(v, h)) & 1u) p = 1.0f;           // X != 0: f32(1 - 1e-10) == 1       zigap.py:135
+            l0[v] = p;
+        }
+        if (irem < 32) {                                         // (uniform) cells past the batch never reach dsum
+#pragma unroll
+            for (int v = 0; v < 16; ++v) if (acc_row(v, h) >= irem) l0[v] = 0.f;
+        }
+        {
+            float t = l0[0];
+#pragma unroll
+            for (int v = 1; v < 16; ++v) t += l0[v];
+            bsum += (double)t;
+            nnz += __popc(mkc);
+        }
+        stage_store(buf ^ 1);
+        ORIANA_VMEM_FENCE();
+        // ---- G += d^T U
+        {
+            const float *u2 = lds + L.u2 + buf * 32 * L.u2s + c;
+            float bc[NT], bn[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bc[nt] = u2[acc_row(0, h) * L.u2s + nt * 32];
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int gn = acc_row(v < 15 ? v + 1 : 15, h);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) bn[nt] = u2[gn * L.u2s + nt * 32];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) dv[nt] = mfma32(l0[v], bc[nt], dv[nt]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) bc[nt] = bn[nt];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (++since_flush == 8) {                            // 256 cells: leave the matrix core
+                since_flush = 0;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) { dvs[nt][v] += dv[nt][v]; dv[nt][v] = 0.f; }
+                if (++flushes == 16) { flushes = 0; spill(); }   // 4096 cells: leave float32
+            }
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+    spill();                                                     // (an empty range writes zeros)
+    bsum += __shfl_xor(bsum, 32);                                // the other half of the tile's cells
+    if (h == 0 && jok) {
+        const double cells = (double)(ie > ib ? ie - ib : 0);
+        dp[(int64_t)blockIdx.y * m + jl] = (lg == -INFINITY) ? (double)nnz + 1e-10 * (cells - (double)nnz) : bsum;
+    }
+}
+
+// G[e] and dsum[j] = the partials of the cell ranges, added in the order of the ranges: every element is written
+__global__ void k_gene_rate_combine(double *__restrict__ G, double *__restrict__ dsum, const double *__restrict__ Gp,
+                                    const double *__restrict__ dp, int64_t mk, int64_t m, int64_t splits) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= mk + m) return;
+    const bool g = e < mk;
+    const double *src = g ? Gp + e : dp + (e - mk);
+    const int64_t stride = g ? mk : m;
+    double s = 0.0;
+    for (int64_t sp = 0; sp < splits; ++sp) s += src[sp * stride];
+    (g ? G + e : dsum + (e - mk))[0] = s;
+}
+
+// Cell ranges of the gene rate, cut as bound_cut cuts gene ranges (the entry runs once per call): until the work-groups fill
+// the chip's slots once, in whole tiles (whole mask words), at least two per range, at most GENE_RATE_MAX_RANGES.  Ranges times
+// blocks of 128 genes never exceed the slots, so the partials hold at most 128 slots (65,536 on MI355X) rows of K doubles
+// whatever n and m (67 MB at K = 128), and never more than 32 times G.
+constexpr int64_t GENE_RATE_MAX_RANGES = 32;
+struct RateCut { int64_t ips, splits; };
+static RateCut gene_rate_cut(int64_t n, int64_t m) {
+    const int64_t gb = (m + 127) / 128, slots = 2 * oriana_device_cus();
+    int64_t sp = slots / gb;
+    if (sp > (n + 63) / 64) sp = (n + 63) / 64;
+    if (sp > GENE_RATE_MAX_RANGES) sp = GENE_RATE_MAX_RANGES;
+    if (sp < 1) sp = 1;
+    int64_t ips = (n + sp - 1) / sp;
+    ips = (ips + 31) / 32 * 32;
+    return RateCut{ips, (n + ips - 1) / ips};
+}
+
+template <int NT>
+static int launch_gene_rate(double *Gp, double *dp, const double *U, const double *V, const float *lg, const uint32_t *nzmask,
+                            int64_t n, int64_t m, int K, RateCut cut, hipStream_t st) {
+    const int KP2 = (K + 1) & ~1;
+    const GeneLds L(KP2, NT);
+    const size_t lds = (size_t)L.total * sizeof(float);
+    const int64_t gb = (m + 127) / 128;
+    if (cut.splits > 65535 || gb > 0x7fffffffLL) return ORIANA_EINVAL;
+    return launch(k_gene_rate<NT>, dim3((unsigned)gb, (unsigned)cut.splits), dim3(256), lds, st, Gp, dp, U, V, lg, nzmask, n, m, K,
+                  KP2, cut.ips);
+}
+
 }  // namespace oriana
 
 using namespace oriana;
+
+extern "C" int64_t oriana_zi_gene_rate_ranges(int64_t n, int64_t m, int64_t K) {
+    if (n <= 0 || m <= 0 || K <= 0 || K > 128) return 0;
+    return gene_rate_cut(n, m).splits;
+}
+
+extern "C" int64_t oriana_zi_gene_rate_scratch_doubles(int64_t n, int64_t m, int64_t K) {
+    if (n <= 0 || m <= 0 || K <= 0 || K > 128) return 0;
+    return gene_rate_cut(n, m).splits * (m * K + m) + bound_logit_doubles(m);     // partials of G | of dsum | the logits
+}
+
+extern "C" int oriana_zi_gene_rate(double *G, double *dsum, const double *U, const double *V, const double *pi_d,
+                                   const uint32_t *nzmask, double *scratch, int64_t n, int64_t m, int64_t K, void *stream) {
+    if (n < 0 || m < 0 || K <= 0) return ORIANA_EINVAL;
+    if (K > 128) return ORIANA_EKRANGE;
+    if (m == 0) return 0;
+    if (!G || !dsum) return ORIANA_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {                                                    // no cells: the empty sums, written
+        if (hipMemsetAsync(G, 0, (size_t)(m * K) * sizeof(double), st) != hipSuccess) return -1000 - (int)hipGetLastError();
+        if (hipMemsetAsync(dsum, 0, (size_t)m * sizeof(double), st) != hipSuccess) return -1000 - (int)hipGetLastError();
+        return 0;
+    }
+    if (!U || !V || !pi_d || !nzmask || !scratch) return ORIANA_EINVAL;
+    const RateCut cut = gene_rate_cut(n, m);
+    double *Gp = scratch, *dp = scratch + cut.splits * m * K;
+    float *lg = reinterpret_cast<float *>(dp + cut.splits * m);
+    hipLaunchKernelGGL(k_logit_f32, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, lg, nullptr, nullptr, pi_d, m);
+    const int rc = with_variant<1, 2, 3, 4>((int)((oriana_kpad(K) + 31) / 32), [&](auto nt) {
+        return launch_gene_rate<decltype(nt)::value>(Gp, dp, U, V, lg, nzmask, n, m, (int)K, cut, st);
+    });
+    if (rc) return rc;
+    const int64_t tot = m * K + m;
+    hipLaunchKernelGGL(k_gene_rate_combine, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, G, dsum, Gp, dp, m * K, m,
+                       cut.splits);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int64_t oriana_zi_cell_bound_scratch_doubles(int64_t n, int64_t m, int64_t K) {
     if (n <= 0 || m <= 0 || K <= 0 || K > 128) return 0;

@@ -563,6 +563,7 @@ struct SviArgs {
     double scale, rho, omr;
     int64_t r;
     int K, Kp, nslab, rpb;
+    int su_mat;                   // sum_u is an (r, K) matrix in the caller's gene order (oriana_svi_gene_update_mat), not a K-vector
 };
 
 // (explicit FMAs, three roundings per value -- prior + scale * stat, rho * that, omr * old + it: every instantiation below
@@ -587,7 +588,8 @@ __global__ __launch_bounds__(256) void k_svi_gene_update(const SviArgs A) {
     for (int c = 0; c < GU_MAXCOLS_PER_THREAD; ++c) {
         const int k = tx + c * KT;
         p1[c] = k < K ? A.beta1[k] : 1.0;
-        t2[c] = k < K ? svi_target(A.beta2[k], A.scale, A.sum_u[k]) : 1.0;
+        // (su_mat: the prior, the target is formed per element below)
+        t2[c] = k < K ? (A.su_mat ? A.beta2[k] : svi_target(A.beta2[k], A.scale, A.sum_u[k])) : 1.0;
         sE[c] = 0.0; sL[c] = 0.0;
     }
     for (int64_t row = r0 + ty; row < r1; row += RY) {
@@ -605,7 +607,7 @@ __global__ __launch_bounds__(256) void k_svi_gene_update(const SviArgs A) {
                     A.Z[idx] = z;
                 }
                 const double s1 = svi_blend(A.b1[idx], svi_target(p1[c], A.scale, (double)z), A.rho, A.omr);
-                const double s2 = svi_blend(A.b2[idx], t2[c], A.rho, A.omr);
+                const double s2 = svi_blend(A.b2[idx], A.su_mat ? svi_target(t2[c], A.scale, A.sum_u[idx]) : t2[c], A.rho, A.omr);
                 A.b1[idx] = s1;
                 A.b2[idx] = s2;
                 const double e = s1 / s2;                                // gamma.py:37-46
@@ -661,7 +663,7 @@ __global__ __launch_bounds__(256) void k_svi_gene_update_vec(const SviArgs A) {
     #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         p1[v] = act ? A.beta1[k0 + v] : 1.0;
-        t2[v] = act ? svi_target(A.beta2[k0 + v], A.scale, A.sum_u[k0 + v]) : 1.0;
+        t2[v] = act ? (A.su_mat ? A.beta2[k0 + v] : svi_target(A.beta2[k0 + v], A.scale, A.sum_u[k0 + v])) : 1.0;      // (su_mat: the prior)
         sE[v] = 0.0; sL[v] = 0.0;
     }
     for (int64_t rb = r0 + w * RPW; rb < r1; rb += NW * RPW) {
@@ -686,12 +688,14 @@ __global__ __launch_bounds__(256) void k_svi_gene_update_vec(const SviArgs A) {
                 for (int v = 0; v < VEC; ++v) z[v] = fmaf(f[v], rr[v], z[v]) + 0.0f;                 // k_finalize (accumulate)
                 st_f32<VEC>(A.Z + idx, z);
             }
+            double tg[VEC];
             ld_f64<VEC>(s1, A.b1 + idx);
             ld_f64<VEC>(s2, A.b2 + idx);
+            if (A.su_mat) ld_f64<VEC>(tg, A.sum_u + idx);
             #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 s1[v] = svi_blend(s1[v], svi_target(p1[v], A.scale, (double)z[v]), A.rho, A.omr);
-                s2[v] = svi_blend(s2[v], t2[v], A.rho, A.omr);
+                s2[v] = svi_blend(s2[v], A.su_mat ? svi_target(t2[v], A.scale, tg[v]) : t2[v], A.rho, A.omr);
                 e[v] = s1[v] / s2[v];                                                       // gamma.py:37-46
                 el[v] = gamma_meanlog_f32(s1[v], s2[v]);                                    // gamma.py:52-61
                 sE[v] += e[v];
@@ -1166,7 +1170,7 @@ static void svi_vec_launch_lpr(const SviArgs &a, int lpr, int64_t nblk, hipStrea
 template <bool FIN>
 static void svi_launch(SviArgs a, hipStream_t s) {
     const bool wide_ok = aligned_to(a.b1, 16) && aligned_to(a.b2, 16) && aligned_to(a.E, 16) && aligned_to(a.Elog, 16) &&
-                         aligned_to(a.Z, 16) && aligned_to(a.F, 16) && aligned_to(a.R, 16);
+                         aligned_to(a.Z, 16) && aligned_to(a.F, 16) && aligned_to(a.R, 16) && (!a.su_mat || aligned_to(a.sum_u, 16));
     int vec, lpr;
     if (gu_vec_cfg(a.K, wide_ok, &vec, &lpr)) {
         a.rpb = gu_vec_rpb(a.r, lpr);
@@ -1182,10 +1186,10 @@ static void svi_launch(SviArgs a, hipStream_t s) {
     hipLaunchKernelGGL((k_svi_gene_update<FIN>), dim3((unsigned)((a.r + a.rpb - 1) / a.rpb)), block, 0, s, a);
 }
 
-extern "C" int oriana_svi_gene_update(double *b1, double *b2, double *E, float *Elog, double *colsum_E, double *colsum_Elog,
-                                      const double *beta1, const double *beta2, float *Z, const float *F, const float *R,
-                                      int64_t nslab, const int32_t *row_index, const double *sum_u, double scale, double rho,
-                                      int64_t m, int64_t K, void *stream) {
+// one entry behind both forms of the rate statistic: a K-vector every gene shares (pCMF) or an (m, K) matrix (ZI-pCMF)
+static int svi_gene_update(double *b1, double *b2, double *E, float *Elog, double *colsum_E, double *colsum_Elog, const double *beta1,
+                           const double *beta2, float *Z, const float *F, const float *R, int64_t nslab, const int32_t *row_index,
+                           const double *sum_u, int su_mat, double scale, double rho, int64_t m, int64_t K, void *stream) {
     if (m < 0 || K <= 0 || !(rho >= 0.0 && rho <= 1.0) || !(scale >= 0.0 && scale < INFINITY)) return ORIANA_EINVAL;
     if (F && (nslab < 1 || nslab > 65535)) return ORIANA_EINVAL;
     const int64_t Kp = oriana_kpad(K);
@@ -1193,11 +1197,28 @@ extern "C" int oriana_svi_gene_update(double *b1, double *b2, double *E, float *
     if (m == 0) return 0;
     if (!b1 || !b2 || !E || !Elog || !beta1 || !beta2 || !Z || !sum_u || (F && !R)) return ORIANA_EINVAL;
     const SviArgs a = {b1, b2, E, Elog, colsum_E, colsum_Elog, beta1, beta2, Z, F, F ? R : nullptr, F ? row_index : nullptr, sum_u,
-                       scale, rho, 1.0 - rho, m, (int)K, (int)Kp, F ? (int)nslab : 1, 0};
+                       scale, rho, 1.0 - rho, m, (int)K, (int)Kp, F ? (int)nslab : 1, 0, su_mat};
     if (F) svi_launch<true>(a, (hipStream_t)stream);
     else svi_launch<false>(a, (hipStream_t)stream);
     ORIANA_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int oriana_svi_gene_update(double *b1, double *b2, double *E, float *Elog, double *colsum_E, double *colsum_Elog,
+                                      const double *beta1, const double *beta2, float *Z, const float *F, const float *R,
+                                      int64_t nslab, const int32_t *row_index, const double *sum_u, double scale, double rho,
+                                      int64_t m, int64_t K, void *stream) {
+    return svi_gene_update(b1, b2, E, Elog, colsum_E, colsum_Elog, beta1, beta2, Z, F, R, nslab, row_index, sum_u, 0, scale, rho, m, K,
+                           stream);
+}
+
+// the rate statistic as an (m, K) float64 matrix in the caller's gene order (ZIGaP.fold_in_fit: G_jk = sum_i d_ij U_hat_ik)
+extern "C" int oriana_svi_gene_update_mat(double *b1, double *b2, double *E, float *Elog, double *colsum_E, double *colsum_Elog,
+                                          const double *beta1, const double *beta2, float *Z, const float *F, const float *R,
+                                          int64_t nslab, const int32_t *row_index, const double *rate, double scale, double rho,
+                                          int64_t m, int64_t K, void *stream) {
+    return svi_gene_update(b1, b2, E, Elog, colsum_E, colsum_Elog, beta1, beta2, Z, F, R, nslab, row_index, rate, 1, scale, rho, m, K,
+                           stream);
 }
 
 extern "C" int oriana_colsum_f64(double *out, const double *A, const float *mul, int64_t r, int64_t K, void *stream) {

@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
 """Cells the model was not fitted on: folding them into a fitted gene side (fold_in, fold_in_zi) and each cell's share of the
 variational bound (cell_bounds, zi_cell_bounds), and -- a streaming fit's global step, GaP.partial_fit -- a folded-in batch's
-per-gene statistics and their blend into the gene side (gene_statistics, svi_gene_update), on a ZWorkspace of the call's own.  This module calls into the sweep sequencer of
+per-gene statistics and their blend into the gene side (gene_statistics, svi_gene_update; for ZIGaP.fold_in_fit the dropout-weighted
+rate statistic beside them, zi_gene_rate), on a ZWorkspace of the call's own.  This module calls into the sweep sequencer of
 engine.py (the row phase: zq_rows_open, plain or -- S_tilde, S_hat given: the sparse models' project() -- masked); nothing in a
 sweep calls back."""
 import torch
@@ -224,13 +225,17 @@ def gene_statistics(ct, K, a1, a2_row, log_V_hat, ws=None, finalize=True):
     own tiles on `ws`, a ZWorkspace over `ct` -- the one the fold-in ran on (its in-place FU arrangement and the pending
     preparation are reset here: this pass prepares both factors from lu and log_V_hat) or None for a fresh one.  The cell
     sums of the pass are not completed: nothing reads them.
+    a2_row may also be the (n', K) rate matrix of a ZI pair (ZIGaP.fold_in_fit: every cell its own rate): lu and sum_u then read
+    each cell's own row, sum_u[k] = sum_i a1_ik / a2_ik.
     Returns (Z_j (m, K) float32, sum_u); with finalize=False the first is (Z_j, F, C, row_index) instead -- Z_j then holds the
     slow path's additions only and Z_j[row_index[p]] += F[p] * C[p] is left to the caller (oriana_svi_gene_update folds it
     into the blend: one launch and one pass over Z_j less).  Nothing in a sweep calls this."""
     n, m, dev = ct.n, ct.m, ct.device
     if ct.gd:
         raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
-    for name, t, dtype, shape in (('log_V_hat', log_V_hat, _F32, (m, K)), ('a1', a1, _F64, (n, K)), ('a2_row', a2_row, _F64, (K,))):
+    pair = isinstance(a2_row, torch.Tensor) and a2_row.dim() == 2
+    for name, t, dtype, shape in (('log_V_hat', log_V_hat, _F32, (m, K)), ('a1', a1, _F64, (n, K)),
+                                  ('a2_row', a2_row, _F64, (n, K) if pair else (K,))):
         _operand(name, t, dtype, shape)
     sum_u = (a1 / a2_row).sum(dim=0)
     Zj = torch.zeros(max(m, 1), K, dtype=_F32, device=dev)
@@ -241,7 +246,7 @@ def gene_statistics(ct, K, a1, a2_row, log_V_hat, ws=None, finalize=True):
     else:
         ws.fu_pending, ws.prep_blocks = False, 0
         ws.FU_alt = ws.mu_u = ws.upart = None
-    lu = gamma_expectations(a1, a2_row.expand(n, K).contiguous())[1]
+    lu = gamma_expectations(a1, a2_row if pair else a2_row.expand(n, K).contiguous())[1]
     Zi = torch.empty(n, K, dtype=_F32, device=dev)
     zq(ws, Zi, Zj[:m], None, lu, log_V_hat, finalize_rows=False, finalize_cols=finalize)
     return (Zj[:m] if finalize else (Zj[:m], ws.FV, ws.C, ct.col_perm)), sum_u
@@ -251,13 +256,42 @@ def svi_gene_update(b1, b2, V_hat, log_V_hat, sums, beta1, beta2, stats, sum_u, 
     """The blend of a streaming fit's global step, ONE oriana_svi_gene_update launch, everything in place:
       b1 <- max(1e-15, (1 - rho) b1 + rho (beta1 + scale Z_j)),   b2 <- max(1e-15, (1 - rho) b2 + rho (beta2 + scale sum_u)),
     V_hat = b1 / b2, log_V_hat = float32 E[log V] and their column sums into `sums` (2, K) float64, zeroed here.
-    `stats`: Z_j complete, or gene_statistics' unfinished (Z_j, F, C, row_index).  `ws`: whose timer the launch reports to."""
+    `stats`: Z_j complete, or gene_statistics' unfinished (Z_j, F, C, row_index).  `sum_u`: the K-vector every gene shares, or an
+    (m, K) float64 matrix in the caller's gene order (zi_gene_rate: oriana_svi_gene_update_mat, the same kernels).  `ws`: whose
+    timer the launch reports to."""
     m, K = b1.shape
     Zj, F, C, perm = stats if isinstance(stats, tuple) else (stats, None, None, None)
+    if sum_u.dim() == 2:
+        _operand('sum_u', sum_u, _F64, (m, K))
     sums.zero_()
     with _span(ws, 'svi_gene_update'):
-        call('oriana_svi_gene_update', ptr(b1), ptr(b2), ptr(V_hat), ptr(log_V_hat), ptr(sums[0]), ptr(sums[1]), ptr(beta1),
+        call('oriana_svi_gene_update_mat' if sum_u.dim() == 2 else 'oriana_svi_gene_update', ptr(b1), ptr(b2), ptr(V_hat), ptr(log_V_hat), ptr(sums[0]), ptr(sums[1]), ptr(beta1),
              ptr(beta2), ptr(Zj), ptr(F), ptr(C), 1, ptr(perm), ptr(sum_u), float(scale), float(rho), m, K, stream_ptr())
+
+
+def zi_gene_rate(ct, K, U_hat, V_hat, pi_d, ws=None):
+    """The dropout-weighted rate statistic of a folded-in batch under a ZI model (ZIGaP.fold_in_fit), at the batch's final
+    U_hat (n', K) float64 with V_hat (m, K) and pi_d [m] float64 as the fold-in read them:
+      G[j,k] = sum_{i in batch} d_ij U_hat_ik   (m, K) float64,     dsum[j] = sum_{i in batch} d_ij   [m] float64,
+    d the dropout posterior of fold_in_zi at that pair (1 at the non-zeros, the column overrides, else the float32 sigmoid), never
+    stored: ONE oriana_zi_gene_rate launch sequence over the query's own non-zero mask with the per-gene operands padded to a
+    multiple of 4 genes (_padded_genes), on scratch of the call's own.  Every element is written in a fixed order (two calls agree
+    bit for bit).  K <= 128.  `ws`: whose timer the launches report to.  Returns (G, dsum)."""
+    n, m, dev = ct.n, ct.m, ct.device
+    if ct.gd:
+        raise ValueError('fold_in walks the sliced layout only: pack the new counts without dense_density')
+    if K > 128:
+        raise ValueError('the zero-inflated gene rate serves K <= 128 (the float32 dense kernels), got K = %d' % K)
+    for name, t, dtype, shape in (('U_hat', U_hat, _F64, (n, K)), ('V_hat', V_hat, _F64, (m, K)), ('pi_d', pi_d, _F64, (m,))):
+        _operand(name, t, dtype, shape)
+    if n == 0 or m == 0:
+        return torch.zeros(m, K, dtype=_F64, device=dev), torch.zeros(m, dtype=_F64, device=dev)
+    mp, Vp, pip, nzmask = _padded_genes(ct, K, V_hat, pi_d)
+    scratch = torch.empty(max(int(_lib.load().oriana_zi_gene_rate_scratch_doubles(n, mp, K)), 1), dtype=_F64, device=dev)
+    G, dsum = torch.empty(mp, K, dtype=_F64, device=dev), torch.empty(mp, dtype=_F64, device=dev)
+    with _span(ws, 'zi_gene_rate'):
+        call('oriana_zi_gene_rate', ptr(G), ptr(dsum), ptr(U_hat), ptr(Vp), ptr(pip), ptr(nzmask), ptr(scratch), n, mp, K, stream_ptr())
+    return (G[:m], dsum[:m]) if mp == m else (G[:m].contiguous(), dsum[:m])        # (the inert genes' rows are dropped)
 
 
 PI_D_FLOOR = 1e-10                # the override values of zigap.py:133-134: pi~ = min(max(pi_d, 1e-10), 1 - 1e-10)

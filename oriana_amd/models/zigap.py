@@ -414,6 +414,76 @@ class ZIGaP(_ZIMixin, FactorModel):
         return self._mean_score(self.fold_in_score_samples(cmatrix, **kw))
 
 
+    # ---- streaming fits ----------------------------------------------------------------------------------------------------
+    # partial_fit() stays undefined here (the training sweep ascends no single bound), but DESIGN.md 5d's point carries over: with
+    # the gene side frozen every cell has a proper collapsed bound, fold_in() ascends it, and the sum of those cell bounds over
+    # the population minus KL(q(V) || p(V)) is a bound whose gene-side natural gradient is well defined.  Its b1 line is
+    # zigap.py:123 with D_hat[i, j] (= 1 at every non-zero count), its b2 line zigap.py:124 on the batch's own dropout posterior:
+    #   b1 <- (1 - rho) b1 + rho (beta1 + scale Z_j),   b2 <- (1 - rho) b2 + rho (beta2 + scale G),   G_jk = sum_{i in B} d_ij U_hat_ik
+    # and pi_d follows the batch's mean posterior.  d is never stored (heldout.zi_gene_rate).
+    n_batches_ = 0
+    fold_in_fit_rho_ = None
+    fold_in_fit_unconverged_ = None
+    _no_partial_fit = ('partial_fit() is defined for pCMF (GaP) only: the zero-inflated SWEEP of the reference ascends no single bound, so '
+                       'there is no gradient of the training cells\' bound to follow.  Batches of held-out cells do have one, with the '
+                       'gene side frozen: ZIGaP.fold_in_fit() folds a batch in as fold_in() does and blends its statistics into the '
+                       'gene side -- call fold_in_fit() instead')
+
+    def fold_in_fit(self, cmatrix, n_total, rho=None, tau0=1.0, kappa=0.7, n_iter=200, tol=1e-4, init=None, check_every=5,
+                    update_pi_d=True):
+        """One stochastic variational update of the gene side from a batch of cells: `cmatrix` (anything fold_in() takes, a
+        prebuilt sliced ``engine.CountTiles`` included) is a sample of a population of `n_total` cells.  The batch is folded in
+        exactly as fold_in() folds it (`n_iter`, `tol`, `init`, `check_every`; ``fold_in_fit_unconverged_`` counts the cells that
+        never froze, ``fold_in_unconverged_`` keeps its value), and at the final pairs
+          b1 <- (1 - rho) b1 + rho (beta1 + scale Z_j),   b2 <- (1 - rho) b2 + rho (beta2 + scale sum_{i in B} d_ij U_hat_ik),
+        scale = n_total / n_B, d the batch's dropout posterior (1 at the non-zeros, the column overrides, else the float32
+        sigmoid; never stored) and, with `update_pi_d`, pi_d <- (1 - rho) pi_d + rho mean_{i in B} d_ij.  `rho` in [0, 1] -- default
+        min(1, (tau0 + n_batches_) ** -kappa), tau0 > 0, kappa in (0.5, 1]; the value used is kept in ``fold_in_fit_rho_`` and
+        ``n_batches_`` counts the non-empty calls.  V_hat, E[log V] and their column sums follow in the blend's launch, all in
+        place, so step(), fold_in() and fold_in_score() read the streamed gene side; the priors and the model's own cells (a1, a2,
+        D_hat, p_d) stay as they are.  A later step() is the ordinary sweep on the construction cells: its D update reads the
+        streamed pi_d and its own M-step then replaces pi_d; with reference_quirks=True it weights b1 with the reference's
+        D_hat[i, k] (zigap.py:94), which this call does not (D_hat[i, j]).  An empty batch changes nothing.  K <= 128.  Returns
+        self."""
+        if self.sharded:
+            raise NotImplementedError('fold_in_fit() under row sharding is not implemented: the batch statistics of the ranks '
+                                      'would need a collective of their own')
+        K = self.k
+        if K > 128:
+            raise ValueError('fold_in_fit() serves K <= 128 (the float32 dense kernels of the sweep); the float64 ZI path has no '
+                             'fold-in, got k = %d' % K)
+        tau0, kappa = float(tau0), float(kappa)
+        if not tau0 > 0.0:
+            raise ValueError('fold_in_fit needs tau0 > 0, got %r' % (tau0,))
+        if not 0.5 < kappa <= 1.0:
+            raise ValueError('fold_in_fit needs kappa in (0.5, 1], got %r' % (kappa,))
+        if rho is not None and not 0.0 <= float(rho) <= 1.0:
+            raise ValueError('fold_in_fit needs rho in [0, 1], got %r' % (rho,))
+        ct = self._query_counts(cmatrix, 'fold_in_fit()')
+        if not int(n_total) >= ct.n:
+            raise ValueError('fold_in_fit needs n_total >= the %d cells of the batch, got %r' % (ct.n, n_total))
+        if ct.n == 0:
+            return self
+        rho = min(1.0, (tau0 + self.n_batches_) ** -kappa) if rho is None else float(rho)
+        kept = self.fold_in_unconverged_
+        ct, ws, a1, a2, _ = self._fold_in_pairs(ct, n_iter, tol, init, check_every, 'fold_in_fit()')
+        self.fold_in_fit_unconverged_, self.fold_in_unconverged_ = self.fold_in_unconverged_, kept
+        pi_d = self.pi_d.tensor
+        stats, _ = heldout.gene_statistics(ct, K, a1, a2, self._log_V_hat, ws=ws, finalize=False)
+        G, dsum = heldout.zi_gene_rate(ct, K, a1 / a2, self._V_hat.contiguous(), pi_d.contiguous(), ws=ws)     # (the OLD gene side)
+        # what load_state() would leave: the pair, its expectations and their column sums where the next sweep reads them
+        heldout.svi_gene_update(self.b1.tensor, self.b2.tensor, self._V_hat, self._log_V_hat, self._sumV, self.beta1.tensor,
+                                self.beta2.tensor, stats, G, float(int(n_total)) / ct.n, rho, ws=ws)
+        if update_pi_d:
+            pi_d.mul_(1.0 - rho).add_(dsum / float(ct.n), alpha=rho)
+        self._v_sums_in_acc = False
+        self._touch()
+        self._DV_next = None                            # (formed from the V_hat that was)
+        self.n_batches_ += 1
+        self.fold_in_fit_rho_ = rho
+        return self
+
+
 class SparseGaP(_SparseMixin, FactorModel):
     """Sparse pCMF (reference sparse_gap.py:15-172; the NameError of sparse_gap.py:127 -- a bare
     `S_hat` -- is read as the evident self.S_hat, SURVEY.md 8(a) policy)."""
