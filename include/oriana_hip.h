@@ -388,6 +388,27 @@ int oriana_count_stats(const oriana_counts *cm, double *colsum, double *colnnz, 
 int oriana_dropout_metric(double *out2, const float *D_hat, const double *U, const double *V, const double *pi_d,
                           const uint32_t *nzmask, int64_t n, int64_t m, int64_t K, void *stream);
 
+/* ---- the deviance along a prefix of the factors (oriana_amd/models/base.py: deviance_path) ----------------------
+ * Lambda^(k)_ij = sum_{l < k} U_il V_jl over the first k columns of the factors handed in (the caller has put the columns
+ * into its factor order).  ends: int32 device array of n_ends prefix lengths, strictly increasing, within 1..K (an end
+ * above K is read as K).  out: (n_ends, 2) float64, out[e] += { sum Lambda^(ends[e]), sum x log Lambda^(ends[e]) } over the
+ * non-zero counts (float64 atomics per work-group; the caller zeroes it).  A prefix whose rate is exactly 0 at a non-zero
+ * count gives -inf in out[e, 1] for that e.
+ *   oriana_metric_nnz_prefix   : the stored entries of the sliced layout, walked once.  FU (n, Kp), FV (m, Kp): float32
+ *                                images of oriana_factor_cast_f32 in packed row / gene order (hybrid layout: FV advanced to
+ *                                the packed gene gd); the running sum is float32 and a value below 1e-10, zero, NaN or
+ *                                infinite at an end is replaced by the float64 sum of U (n, K), V (m, K) (caller's row /
+ *                                gene order, found through row_perm / col_perm as in oriana_metric_nnz).  K <= 256.
+ *   oriana_dense_metric_prefix : the non-zero counts of the dense genes of a hybrid layout, float64 throughout
+ *                                (K <= 1024, as oriana_dense_metric).
+ * Both return ORIANA_EINVAL on a missing pointer, K <= 0 or n_ends outside 0..K, and 0 without a launch for an empty
+ * problem (no stored entry, no dense gene, n_ends == 0). */
+int oriana_metric_nnz_prefix(const oriana_counts *cm, const float *FU, const float *FV, const double *U, const double *V,
+                             int64_t K, const int32_t *ends, int64_t n_ends, double *out, void *stream);
+int oriana_dense_metric_prefix(const oriana_dense *d, const double *U, const double *V, const int32_t *row_perm,
+                               const int32_t *col_perm, int64_t K, const int32_t *ends, int64_t n_ends, double *out,
+                               void *stream);
+
 /* ---- the variational bound of pCMF (oriana_amd/models/gap.py: elbo; no counterpart in the reference) --------
  * With q(Z) at its optimum for the current q(U) q(V), Gamma(shape, rate) throughout:
  *   ELBO = sum_{x != 0} [x log den - lgamma(x + 1)] - sum_k (sum_i U_hat_ik)(sum_j V_hat_jk) - KL_U - KL_V,

@@ -131,6 +131,36 @@ __device__ __forceinline__ uint32_t lanes_or(uint32_t v) {
     return v;
 }
 
+// float64 sum over the 64 lanes of a wave, in every lane, by the moves of lanes_max on the two words of the value (DPP inside a
+// row of 16, v_permlane16_swap / v_permlane32_swap across rows): no LDS instruction, where __shfl_xor costs two ds_bpermute per
+// round -- the per-prefix sums of the deviance path (metrics.hip, dense_pass.hip) take two of these per entry and prefix
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = dpp_u32<CTRL>((uint32_t)b), hi = dpp_u32<CTRL>((uint32_t)(b >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double f64_of(uint32_t lo, uint32_t hi) { return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo); }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v += dpp_f64<0xB1>(v);
+    v += dpp_f64<0x4E>(v);
+    v += dpp_f64<0x141>(v);
+    v += dpp_f64<0x140>(v);
+    {
+        const uint64_t b = __builtin_bit_cast(uint64_t, v);
+        uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32), lo2 = opaque_copy(lo), hi2 = opaque_copy(hi);
+        swap_rows16(lo, lo2); swap_rows16(hi, hi2);            // (the same permutation on both words: {x[l], x[l ^ 16]})
+        v = f64_of(lo, hi) + f64_of(lo2, hi2);
+    }
+    {
+        const uint64_t b = __builtin_bit_cast(uint64_t, v);
+        uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32), lo2 = opaque_copy(lo), hi2 = opaque_copy(hi);
+        swap_halves32(lo, lo2); swap_halves32(hi, hi2);
+        v = f64_of(lo, hi) + f64_of(lo2, hi2);
+    }
+    return v;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;

@@ -705,6 +705,58 @@ __global__ __launch_bounds__(256) void k_dn_metric(const uint16_t *__restrict__ 
     }
 }
 
+// The deviance sums of every prefix of the factors over the dense block (oriana_metric_nnz_prefix for the dense genes; the twin
+// of k_dn_metric): the same staging of 32 cells x 32 genes of float64 factor rows (U, V: caller's cell / gene order, columns in
+// the caller's factor order), Lambda^(k) the running float64 sum over l < k, out[e, 0] += sum Lambda^(ends[e]),
+// out[e, 1] += sum x log Lambda^(ends[e]) over the non-zero counts.  A lane walks the factors of its entry once; at each end
+// the wave adds its lanes' two terms and lane 0 adds the pair into the wave's own row of part[wave][end][2], behind the factor
+// rows in LDS (all 64 lanes run all four entries of the block's loop together: a zero count contributes 0).
+__global__ __launch_bounds__(256) void k_dn_metric_prefix(const uint16_t *__restrict__ Xd, const double *__restrict__ U,
+                                                          const double *__restrict__ V, const int32_t *__restrict__ row_perm,
+                                                          const int32_t *__restrict__ col_perm, const int32_t *__restrict__ ends,
+                                                          int E, double *__restrict__ out, int64_t n, int ngt, int K) {
+    extern __shared__ double fac[];                // [32 cells][K], [32 genes][K], then part[4][E][2]
+    double *part = fac + 64 * K;
+    const int gt = blockIdx.x;
+    const int64_t ct = blockIdx.y;
+    const int tid = threadIdx.x, w = tid >> 6;
+    for (int e = tid; e < 32 * K; e += 256) {
+        const int r = e / K, k = e - r * K;
+        const int64_t ip = ct * 32 + r, jp = (int64_t)gt * 32 + r;
+        const int64_t i = (ip < n) ? (row_perm ? (int64_t)row_perm[ip] : ip) : -1;
+        const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+        fac[e] = (i >= 0) ? U[i * K + k] : 0.0;
+        fac[32 * K + e] = V[j * K + k];
+    }
+    for (int e = tid; e < 8 * E; e += 256) part[e] = 0.0;
+    __syncthreads();
+    const uint16_t *blk = Xd + (ct * ngt + gt) * 1024;
+    for (int e4 = tid; e4 < 1024; e4 += 256) {
+        const int v = ((e4 >> 9) << 3) | (e4 & 7), l = (e4 >> 3) & 63;
+        const int c = l & 31, h = l >> 5, g = acc_row(v, h);
+        const uint32_t xi = blk[e4];
+        const bool live = xi != 0u && ct * 32 + c < n;
+        if (__ballot(live) == 0ull) continue;       // (uniform over the wave)
+        const double x = (double)xi;
+        const double *u = fac + c * K, *vv = fac + 32 * K + g * K;
+        double lam = 0.0;
+        int k = 0;
+        for (int e = 0; e < E; ++e) {
+            const int end = min((int)ends[e], K);
+            for (; k < end; ++k) lam += u[k] * vv[k];
+            double a0 = live ? lam : 0.0, a1 = live ? x * log(lam) : 0.0;
+            a0 = wave_sum_f64(a0);
+            a1 = wave_sum_f64(a1);
+            if ((tid & 63) == 0) { part[(w * E + e) * 2] += a0; part[(w * E + e) * 2 + 1] += a1; }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * E; e += 256) {
+        const double s = ((part[e] + part[2 * E + e]) + part[4 * E + e]) + part[6 * E + e];
+        if (s != 0.0) atomicAdd(&out[e], s);
+    }
+}
+
 // The data term of the variational bound over the dense block (oriana_elbo_nnz for the dense genes): out2 += {sum x log den,
 // sum lgamma(x + 1)} over the non-zero counts, log den = log sum_k exp(lu_ik + lv_jk) as a float64 log-sum-exp from the float32
 // E[log U], E[log V] (caller's cell / gene order).  One work-group per (cell tile, gene tile).
@@ -904,6 +956,18 @@ extern "C" int oriana_dense_metric(const oriana_dense *d, const double *U, const
     const size_t lb = U ? (size_t)64 * K * sizeof(double) : 0;
     return launch(k_dn_metric, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), lb, (hipStream_t)stream, d->x, U, V,
                   row_perm, col_perm, colsum, colnnz, out2, out4, d->n, ngt, (int)K);
+}
+
+extern "C" int oriana_dense_metric_prefix(const oriana_dense *d, const double *U, const double *V, const int32_t *row_perm,
+                                          const int32_t *col_perm, int64_t K, const int32_t *ends, int64_t n_ends, double *out,
+                                          void *stream) {
+    if (!dense_ok(d) || K <= 0 || K > 1024 || n_ends < 0 || n_ends > K) return ORIANA_EINVAL;
+    if (n_ends == 0 || d->gd == 0 || d->n == 0) return 0;
+    if (!U || !V || !ends || !out) return ORIANA_EINVAL;
+    const int ngt = (int)(d->gd / 32);
+    return launch(k_dn_metric_prefix, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256),
+                  (size_t)(64 * K + 8 * n_ends) * sizeof(double), (hipStream_t)stream, d->x, U, V, row_perm, col_perm, ends,
+                  (int)n_ends, out, d->n, ngt, (int)K);
 }
 
 extern "C" int oriana_dense_elbo(const oriana_dense *d, const float *logU, const float *logV, const int32_t *row_perm,

@@ -119,6 +119,94 @@ __global__ __launch_bounds__(256) void k_metric_nnz(oriana_counts cm, const floa
     }
 }
 
+constexpr int PREFIX_MAX_ENDS = 256;       // K <= 256 in the sliced layout (oriana_kpad), one end per factor at most
+
+// The deviance sums of every prefix of the factors (models/base.py: deviance_path): with Lambda^(k)_ij = sum_{l < k} FU[ip, l]
+// FV[jp, l] the running float32 sum over the factor images (packed row / gene order, row stride Kp, columns already in the
+// caller's factor order), out[e, 0] += sum Lambda^(ends[e]), out[e, 1] += sum x log Lambda^(ends[e]) over the stored entries.
+// One work-group per tile and one lane per stored entry, as k_metric_nnz; a lane walks the factors ONCE and stops at each end.
+// A running sum that is not a trusted float32 value there (below 1e-10 -- the row pass's threshold --, zero, NaN or infinite)
+// is replaced by the float64 sum of U, V (caller's row / gene order through row_perm / col_perm, columns in the same factor
+// order), itself a running sum that is advanced only when asked for: the fall-back costs one more walk, not one per end.
+// Accumulators: a lane cannot hold 2 x 100+ float64 sums in registers, so nothing is accumulated per lane.  At each end the
+// wave adds its 64 lanes' two terms (wave_sum_f64, common.h: DPP and permlane swaps, no LDS) and lane 0 adds the pair into the wave's own row of an LDS table
+// part[wave][end][2] (16 KiB), which no other wave touches: no barrier inside the walk.  The table is summed over the four
+// waves at the end and goes out as one float64 atomic per (end, term) and work-group.  Slice lengths are multiples of 64
+// (pack.hip: k_pack_fill), and the slot loop is written so that the lanes of a wave run it together whatever the length:
+// the cross-lane sums always see all 64 lanes (a padding slot or a lane past the end contributes 0).
+__global__ __launch_bounds__(256) void k_metric_nnz_prefix(oriana_counts cm, const float *__restrict__ FU,
+                                                           const float *__restrict__ FV, const double *__restrict__ U,
+                                                           const double *__restrict__ V, int K, int Kp,
+                                                           const int32_t *__restrict__ ends, int E,
+                                                           double *__restrict__ out) {
+    __shared__ double part[4][PREFIX_MAX_ENDS][2];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int e = tid; e < 4 * E; e += 256) { part[e / E][e % E][0] = 0.0; part[e / E][e % E][1] = 0.0; }
+    __syncthreads();
+    const int64_t t = blockIdx.x;
+    const int64_t rb = t / cm.ncb, cb = t - rb * cm.ncb;
+    const int64_t rbase = cm.roff[t];
+    for (int sl = 0; sl < 16; ++sl) {
+        const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+        for (uint32_t wbase = s0 + (uint32_t)(w * 64); wbase < s1; wbase += 256) {      // (uniform over the wave)
+            const uint32_t slot = wbase + (uint32_t)lane;
+            double x = 0.0;
+            int64_t ip = 0, jp = 0;
+            if (slot < s1) {
+                const oriana_rowrec rec = cm.rowrec[rbase + slot];
+                x = (double)rec.x;
+                ip = rb * TILE + sl * 16 + (int)(((slot - s0) & 63u) >> 2);
+                jp = cb * TILE + rec.col;
+            }
+            const bool live = x != 0.0 && ip < cm.n && jp < cm.m;
+            if (!live) { ip = 0; jp = 0; }                                // (a row every lane may read)
+            if (__ballot(live) == 0ull) continue;                        // (uniform: a wave of padding)
+            const float *__restrict__ fu = FU + ip * Kp;
+            const float *__restrict__ fv = FV + jp * Kp;
+            const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+            const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+            const double *__restrict__ u = U + i * K;
+            const double *__restrict__ v = V + j * K;
+            float acc = 0.f;
+            double dacc = 0.0;
+            int dl = 0, e = 0;
+            int end = min((int)ends[0], K);
+            // four factors per 16-byte load (Kp is a multiple of 4 and the images hold zeros from K on); an end is met when the
+            // number of factors added equals it (ends that do not increase are never met: their sums stay 0)
+            for (int c = 0; 4 * c < K && e < E; ++c) {
+                const float4 a4 = reinterpret_cast<const float4 *>(fu)[c], b4 = reinterpret_cast<const float4 *>(fv)[c];
+                const float pa[4] = {a4.x, a4.y, a4.z, a4.w}, pb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc = fmaf(pa[q], pb[q], acc);
+                    if (4 * c + q + 1 != end) continue;                  // (uniform over the wave)
+                    double a0 = 0.0, a1 = 0.0;
+                    if (live) {
+                        double lam = (double)acc;
+                        if (!(acc >= DEN_MIN && acc < INFINITY)) {
+                            for (; dl < end; ++dl) dacc += u[dl] * v[dl];
+                            lam = dacc;
+                        }
+                        a0 = lam;
+                        a1 = x * log(lam);
+                    }
+                    a0 = wave_sum_f64(a0);
+                    a1 = wave_sum_f64(a1);
+                    if (lane == 0) { part[w][e][0] += a0; part[w][e][1] += a1; }
+                    ++e;
+                    end = e < E ? min((int)ends[e], K) : -1;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * E; e += 256) {
+        const int q = e & 1, ee = e >> 1;
+        const double s = ((part[0][ee][q] + part[1][ee][q]) + part[2][ee][q]) + part[3][ee][q];
+        if (s != 0.0) atomicAdd(&out[e], s);
+    }
+}
+
 // One stored entry of the data term, count x != 0 at the packed position (ip, jp), s its row-pass value: a0 += x log den,
 // a1 += lgamma(x + 1).  log den_ij = mu_u[i] + mu_v[j] + log(x / s); what the shifted form could not represent (NaN sentinel or
 // 0 in s, a rejected row's NaN maximum) is a float64 log-sum-exp over the K factors.  THE arithmetic of k_elbo_nnz and
@@ -252,6 +340,21 @@ extern "C" int oriana_metric_nnz(const oriana_counts *cm, const float *s_rs, con
     if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
     hipLaunchKernelGGL(k_metric_nnz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, U, V, (int)K,
                        out4);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_metric_nnz_prefix(const oriana_counts *cm, const float *FU, const float *FV, const double *U,
+                                        const double *V, int64_t K, const int32_t *ends, int64_t n_ends, double *out,
+                                        void *stream) {
+    const int64_t Kp = oriana_kpad(K);
+    if (!cm || !FU || !FV || !U || !V || !out || K <= 0 || n_ends < 0 || n_ends > K) return ORIANA_EINVAL;
+    if (Kp == 0 || n_ends > PREFIX_MAX_ENDS) return ORIANA_EKRANGE;
+    const int64_t nt = cm->nrb * cm->ncb;
+    if (n_ends == 0 || nt == 0 || cm->rslots == 0) return 0;
+    if (!ends || nt > 0x7fffffffLL) return ORIANA_EINVAL;
+    hipLaunchKernelGGL(k_metric_nnz_prefix, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, FU, FV, U, V, (int)K,
+                       (int)Kp, ends, (int)n_ends, out);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

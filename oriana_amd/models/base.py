@@ -627,14 +627,14 @@ class FactorModel:
         one = torch.ones(self.m, dtype=torch.float64, device=self.device)
         return torch.zeros_like(one), one
 
-    def _loglikelihoods(self):
+    def _ll_constants(self):
+        """What the log-likelihoods hold apart from the rate matrix: sum_j nnz_j log pi_j, ll(X | X), ll(X | mean) (device
+        scalars) and the count constants."""
         colsum, colnnz, xc = self._count_constants()
-        nz, zz = self._metric_terms()
         lpi, pi = self._log_pi()
         has = colnnz > 0
         nnz_lpi = torch.where(has, colnnz * lpi, torch.zeros_like(lpi)).sum()
         ll_x = nnz_lpi + xc[0]
-        ll_uv = zz[0] + nnz_lpi - nz[0] + nz[1]
         ntot = float(self.n_total)
         mu = colsum / ntot
         # log(pi e^-mu + 1 - pi) as a log-sum-exp.  Without a dropout node (pi = 1) the literal form is log e^-mu, which
@@ -644,6 +644,12 @@ class FactorModel:
         nz_term = torch.where(has, colnnz * (lpi - mu) + colsum * torch.log(torch.where(has, mu, torch.ones_like(mu))),
                               torch.zeros_like(mu))
         ll_mean = (zero_term + nz_term).sum()
+        return nnz_lpi, ll_x, ll_mean, xc
+
+    def _loglikelihoods(self):
+        nnz_lpi, ll_x, ll_mean, xc = self._ll_constants()
+        nz, zz = self._metric_terms()
+        ll_uv = zz[0] + nnz_lpi - nz[0] + nz[1]
         return float(ll_x), float(ll_uv), float(ll_mean), nz, zz, xc
 
     def loglikelihood_X(self, given='factors'):
@@ -675,6 +681,88 @@ class FactorModel:
         _, _, _, nz, zz, xc = self._loglikelihoods()
         # sum_N (Lambda - x)^2 + sum_{Z - M} Lambda^2
         return float(torch.sqrt(torch.clamp(nz[2] - 2.0 * nz[3] + xc[1] + zz[1], min=0.0)))
+
+    # ---- the deviance along a prefix of the factors ------------------------------------------------------
+    # The columns of U_hat / V_hat come out in the arbitrary order of the start.  With an order o of the factors and
+    # Lambda^(k) = sum_{l < k} U_hat[:, o_l] V_eff[:, o_l]^T (V_eff = _effective_V()), everything else as the full metric has it
+    # (pi_d, the mask M, ll(X | X), ll(X | mean)), in the notation above _count_constants:
+    #   ll_uv^(k) = zz0^(k) + sum_j nnz_j log pi_j - sum_N Lambda^(k) + sum_N x log Lambda^(k)
+    #   ed^(k) = (ll_uv^(k) - ll_mean) / (ll_x - ll_mean),   rd^(k) = -2 (ll_uv^(k) - ll_x)
+    # zz0^(k) = sum_{Z - M} log(pi_j e^-Lambda^(k) + 1 - pi_j).  Without a dropout node it is -sum_Z Lambda^(k), so
+    # zz0^(k) - sum_N Lambda^(k) = -sum_{l < k} su_l sv_l from the permuted column sums; with one it is a call of
+    # oriana_dropout_metric on the first k permuted columns per requested k.  The two sums over N for ALL requested k come from
+    # one walk over the stored counts (oriana_metric_nnz_prefix, oriana_dense_metric_prefix for the dense genes of a hybrid
+    # layout): the full metric's route through the row pass (s = x / Lambda) yields Lambda only as a whole.
+    def factor_order(self):
+        """The factors by decreasing mass (sum_i U_hat_ik)(sum_j V_eff_jk), V_eff = S_hat * V_hat on the sparse models: an int64
+        permutation of range(K), ties by index.  The cell sums are summed over the row shards: every rank returns the same
+        order."""
+        from .. import prefix
+        su = self._U_hat.sum(0)
+        odist.all_reduce_sum(su, self.pg)
+        sv = self._effective_V().sum(0)
+        return prefix.order_by_mass(su.cpu().numpy(), sv.cpu().numpy())
+
+    def deviance_path(self, order=None, ks=None):
+        """explained_deviance() / reconstruction_deviance() of the fitted model restricted to the first k factors of `order`,
+        for every k of `ks`, from one pass over the stored counts.
+
+        order : a permutation of range(K) (default: factor_order()).  ks : strictly increasing prefix lengths within 1..K
+        (default: 1..K).  Anything else raises ValueError before a launch.  Returns a dict: 'order', 'k' (int64) and
+        'explained_deviance', 'reconstruction_deviance' (float64, one value per k): entry t is what the two metrics would return
+        if the model had only the factors order[:k_t].  A prefix whose rate is exactly 0 at a non-zero count (masked factors of
+        a sparse model) gives -inf (+inf for the reconstruction deviance) for that k alone.  Nothing of the model's state is
+        written.
+
+        Cost: the pass over the non-zero counts takes all k at once, one logarithm per count and k.  With a dropout node
+        (ZIGaP, SparseZIGaP; K <= 256) the zero term is one dense n x m pass PER requested k: pass a handful of `ks` at scale
+        rather than the default."""
+        from .. import prefix
+        K, n, m, dev = self.k, self.n, self.m, self.device
+        order = prefix.check_order(order, K) if order is not None else None
+        ks = prefix.check_ks(ks, K)
+        if self.zi and K > 256:
+            raise ValueError('deviance_path() with a dropout node needs k <= 256')
+        if order is None:
+            order = self.factor_order()
+        ct, ws, st, E = self.counts, self._ws, stream_ptr(), int(ks.size)
+        idx = torch.as_tensor(order, device=dev)
+        U = self._U_hat.index_select(1, idx).contiguous()
+        V = self._effective_V().index_select(1, idx).contiguous()
+        ends = torch.as_tensor(ks, dtype=torch.int32, device=dev)
+        FU, FV = ws.extra('MU', n), ws.extra('MV', m)
+        call('oriana_factor_cast_f32', ptr(FU), ptr(U), None, ptr(ct.row_perm), n, K, st)
+        call('oriana_factor_cast_f32', ptr(FV), ptr(V), None, ptr(ct.col_perm), m, K, st)
+        nz = torch.zeros(E, 2, dtype=torch.float64, device=dev)     # per k: sum_N Lambda^(k), sum_N x log Lambda^(k)
+        # (hybrid layout: the sliced part covers the packed genes [gd, m), as in _metric_terms)
+        call('oriana_metric_nnz_prefix', ct.sparse_struct, ptr(FU), ptr(FV) + 4 * ct.gd * ws.Kp, ptr(U), ptr(V), K, ptr(ends), E,
+             ptr(nz), st)
+        if ct.dense is not None:
+            call('oriana_dense_metric_prefix', ct.dense.c_struct, ptr(U), ptr(V), ptr(ct.row_perm), ptr(ct.col_perm), K, ptr(ends),
+                 E, ptr(nz), st)
+        if self.zi:
+            zz = torch.zeros(E, 2, dtype=torch.float64, device=dev)
+            Vp = torch.zeros(self._mp, K, dtype=torch.float64, device=dev)      # (the inert genes of the padded gene axis)
+            Vp[:m].copy_(V)
+            pim = self._padG(self.pi_d.tensor, 'pim')
+            for t, k in enumerate(ks.tolist()):
+                Uk, Vk = U[:, :k].contiguous(), Vp[:, :k].contiguous()
+                call('oriana_dropout_metric', ptr(zz[t]), ptr(self._Dp), ptr(Uk), ptr(Vk), ptr(pim), ptr(self._nzmask), n,
+                     self._mp, k, st)
+            tail = zz[:, 0]
+        else:
+            tail = U.sum(0)
+        packed = torch.cat([nz.reshape(-1), tail])
+        odist.all_reduce_sum(packed, self.pg)
+        nnz_lpi, ll_x, ll_mean, _ = self._ll_constants()
+        packed = packed.cpu().numpy()
+        nz, tail = packed[:2 * E].reshape(E, 2), packed[2 * E:]
+        if self.zi:
+            ll_uv = tail + float(nnz_lpi) - nz[:, 0] + nz[:, 1]
+        else:                                  # zz0^(k) - sum_N Lambda^(k) = -sum_{l < k} su_l sv_l
+            all_lam = np.cumsum(tail * V.sum(0).cpu().numpy())
+            ll_uv = -all_lam[ks - 1] + float(nnz_lpi) + nz[:, 1]
+        return prefix.assemble_path(order, ks, ll_uv, float(ll_x), float(ll_mean))
 
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
     _PARAMS = ('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
