@@ -409,6 +409,31 @@ int oriana_dense_metric_prefix(const oriana_dense *d, const double *U, const dou
                                const int32_t *col_perm, int64_t K, const int32_t *ends, int64_t n_ends, double *out,
                                void *stream);
 
+/* ---- the deviance per gene and per cell (oriana_amd/models/base.py: gene_deviance, cell_deviance) -----------------
+ * The sums of the metrics kept along one axis.  gene_out: (m, 3) float64 in the caller's gene order, cell_out: (n, 5) float64
+ * in the caller's row order; every entry ADDS into them with float64 atomics (the caller zeroes them; reruns agree to the
+ * order of the additions), and a NULL output skips that axis (both NULL: ORIANA_EINVAL).
+ *   gene_out[j] += { sum Lambda, sum x log Lambda, sum (x log x - x) } over the non-zero counts of gene j
+ *   cell_out[i] += the same three over the non-zero counts of cell i, then { sum gene_const[j][0],
+ *                  sum (gene_const[j][1] + x gene_const[j][2]) }; gene_const: (m, 3) float64 in the caller's gene order,
+ *                  needed with cell_out only; the row of a gene without a non-zero count is never used
+ *   oriana_metric_nnz_axes     : the stored entries of the sliced layout, Lambda as oriana_metric_nnz takes it (x / s from
+ *                                the row pass, the float64 sum of U, V for the NaN sentinel and for 0).  K <= 256
+ *                                (ORIANA_EKRANGE above).
+ *   oriana_dense_metric_axes   : the non-zero counts of the dense genes of a hybrid layout, float64 throughout (K <= 1024).
+ *   oriana_dropout_metric_axes : gene_out (m,) and cell_out (n,) += log(pi_j exp(-Lambda_ij) + 1 - pi_j) over the entries
+ *                                with X == 0 and D_hat > 0.5 -- the term of oriana_dropout_metric per axis, on the f64
+ *                                matrix cores; m is the padded gene count of D_hat's rows.  ORIANA_EKRANGE for K > 256.
+ * All three return ORIANA_EINVAL on a missing pointer or K <= 0 before any HIP call, and 0 without a launch for an empty
+ * problem. */
+int oriana_metric_nnz_axes(const oriana_counts *cm, const float *s_rs, const double *U, const double *V, int64_t K,
+                           const double *gene_const, double *gene_out, double *cell_out, void *stream);
+int oriana_dense_metric_axes(const oriana_dense *d, const double *U, const double *V, const int32_t *row_perm,
+                             const int32_t *col_perm, int64_t K, const double *gene_const, double *gene_out,
+                             double *cell_out, void *stream);
+int oriana_dropout_metric_axes(double *gene_out, double *cell_out, const float *D_hat, const double *U, const double *V,
+                               const double *pi_d, const uint32_t *nzmask, int64_t n, int64_t m, int64_t K, void *stream);
+
 /* ---- the variational bound of pCMF (oriana_amd/models/gap.py: elbo; no counterpart in the reference) --------
  * With q(Z) at its optimum for the current q(U) q(V), Gamma(shape, rate) throughout:
  *   ELBO = sum_{x != 0} [x log den - lgamma(x + 1)] - sum_k (sum_i U_hat_ik)(sum_j V_hat_jk) - KL_U - KL_V,

@@ -136,6 +136,9 @@ _SIGS = {
     'oriana_metric_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _I, _P, _P]),
     'oriana_metric_nnz_prefix': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _I, _P, _I, _P, _P]),
     'oriana_dense_metric_prefix': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    'oriana_metric_nnz_axes': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _I, _P, _P, _P, _P]),
+    'oriana_dense_metric_axes': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    'oriana_dropout_metric_axes': (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'oriana_count_stats': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P]),
     'oriana_elbo_nnz': (c_int, [ctypes.POINTER(OrianaCounts), _P, _P, _P, _P, _P, _I, _P, _P]),
     'oriana_dense_elbo': (c_int, [ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _P, _I, _P]),

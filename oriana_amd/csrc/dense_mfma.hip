@@ -160,6 +160,11 @@ __global__ __launch_bounds__(256) void k_dense_times_factor(double *__restrict__
 // MODE 1 (metrics, base.py:58-87 with sparse_zigap.py:44-51): nothing is stored; over the entries with
 // X == 0 and round(D_hat) == 1 the kernel sums log(pi_j exp(-Lambda) + 1 - pi_j) and Lambda^2 into
 // colsum[0], colsum[1] (one pair of f64 atomics per wave); D_hat is read.
+// MODE 2 (models/base.py: gene_deviance, cell_deviance): MODE 1's term log(pi_j exp(-Lambda) + 1 - pi_j) over the same
+// entries, kept per axis instead of summed: per gene into colsum[j] in MODE 0's pattern (__shfl_xor 16 / 32, one atomic per
+// column and work-group), per cell into p_d[i] -- in this mode an (n,) vector, not a matrix -- reduced over the 16 lr lanes,
+// the four column tiles (registers) and the four waves (4 x 64 doubles of LDS behind Us) before one atomic per row and
+// work-group.  Either pointer may be NULL.  Nothing else is stored; D_hat is read.
 template <int MODE>
 __global__ __launch_bounds__(256, 3) void k_dropout_fused(double *__restrict__ p_d, float *__restrict__ D_hat,
                                                        const double *__restrict__ U, const double *__restrict__ V,
@@ -178,6 +183,9 @@ __global__ __launch_bounds__(256, 3) void k_dropout_fused(double *__restrict__ p
     const int kcols = KS * 4;
 
     double cs[4] = {0.0, 0.0, 0.0, 0.0};
+    // MODE 2: the term of ONE row of the sub-block over this wave's 64 columns.  Lane (g, lr) keeps row tile rt = lr >> 2,
+    // register r = 2 (lr & 1) + ((lr >> 1) & 1) of the accumulator, i.e. row 16 rt + g + 4 r
+    double ra = 0.0;
 
     // operands of one (row sub-block, column tile) step that come from global memory; those of the
     // next step are requested before the current step's stores are issued, so that waiting for them
@@ -245,7 +253,44 @@ __global__ __launch_bounds__(256, 3) void k_dropout_fused(double *__restrict__ p
             const double pi = cur.pi;
             const uint32_t w0 = cur.w0, w1 = cur.w1;
             fetch(cur, (ct == 3) ? i0 + 64 : i0, (ct + 1) & 3);
-            if (MODE == 1) {
+            if constexpr (MODE == 2) {
+                // per gene as MODE 0 (cs[ct]); per cell: the 16 lr lanes hold 16 columns of a row.  The four values of a row
+                // tile over four lanes in three exchanges (each lane keeps the half its bit selects), then the quads of the
+                // 16-lane row; the lane that keeps (rt, r) adds the sum.  Every lane takes part: a column past m gives 0
+                double csum = 0.0;
+                int64_t off = (i0 + g) * m + (jok ? j : 0);
+                const int64_t step = 4 * m;
+                const bool b0 = lr & 1, b1 = lr & 2;
+#pragma unroll
+                for (int rt = 0; rt < 4; ++rt) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    const uint32_t w = (rt < 2) ? w0 : w1;
+                    double tz[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int bit = (rt & 1) * 16 + g + 4 * r;
+                        const int64_t i = i0 + rt * 16 + g + 4 * r;
+                        asm volatile("" : "+v"(off));
+                        tz[r] = 0.0;
+                        if (jok && i < n && !((w >> bit) & 1u) && D_hat[off] > 0.5f) {
+                            tz[r] = log(pi * exp(-acc[rt][r]) + (1.0 - pi));
+                            csum += tz[r];
+                        }
+                        off += step;
+                    }
+                    if (p_d) {
+                        double k0 = b0 ? tz[2] : tz[0], k1 = b0 ? tz[3] : tz[1];
+                        k0 += __shfl_xor(b0 ? tz[0] : tz[2], 1, 64);
+                        k1 += __shfl_xor(b0 ? tz[1] : tz[3], 1, 64);
+                        double k = b1 ? k1 : k0;
+                        k += __shfl_xor(b1 ? k0 : k1, 2, 64);
+                        k += __shfl_xor(k, 4, 64);
+                        k += __shfl_xor(k, 8, 64);
+                        if ((lr >> 2) == rt) ra += k;
+                    }
+                }
+                cs[ct] += csum;
+            } else if (MODE == 1) {
                 if (jok) {
                     int64_t off = (i0 + g) * m + j;
                     const int64_t step = 4 * m;
@@ -298,6 +343,20 @@ __global__ __launch_bounds__(256, 3) void k_dropout_fused(double *__restrict__ p
                     }
                 }
                 cs[ct] += csum;
+            }
+        }
+        if constexpr (MODE == 2) {
+            // per cell (p_d: the (n,) output of this mode): ra holds the lane's row over the wave's four column tiles; the four
+            // waves meet in LDS (behind the U_hat sub-block) -- one atomic per row and work-group
+            if (p_d) {
+                double *rsum = Us + 64 * us;                // [4 waves][64 rows]
+                rsum[wave * 64 + (lr >> 2) * 16 + g + 4 * (2 * (lr & 1) + ((lr >> 1) & 1))] = ra;
+                ra = 0.0;
+                __syncthreads();
+                if (tid < 64) {
+                    const double v = ((rsum[tid] + rsum[64 + tid]) + rsum[128 + tid]) + rsum[192 + tid];
+                    if (i0 + tid < n && v != 0.0) atomicAdd(&p_d[i0 + tid], v);
+                }
             }
         }
     }
@@ -388,6 +447,30 @@ extern "C" int oriana_dropout_update_fused(double *p_d, float *D_hat, const doub
     if (n == 0 || m == 0) return 0;
     if ((!p_d && !D_hat && !colsum) || !pi_d || (K > 0 && (!U || !V))) return ORIANA_EINVAL;
     return launch_dropout_fused<0>(p_d, D_hat, U, V, pi_d, nzmask, colsum, n, m, K, stream);
+}
+
+// MODE 2: the same row slabs as launch_dropout_fused; the kernel's p_d parameter carries the per-cell output, advanced by the
+// slab's first row (not by r0 * m as a matrix would be), and 4 x 64 doubles of LDS follow the U_hat sub-block
+extern "C" int oriana_dropout_metric_axes(double *gene_out, double *cell_out, const float *D_hat, const double *U,
+                                          const double *V, const double *pi_d, const uint32_t *nzmask, int64_t n, int64_t m,
+                                          int64_t K, void *stream) {
+    if (n < 0 || m < 0 || K <= 0) return ORIANA_EINVAL;
+    if (K > 256) return ORIANA_EKRANGE;
+    if ((!gene_out && !cell_out) || !D_hat || !U || !V || !pi_d || !nzmask) return ORIANA_EINVAL;
+    if (n == 0 || m == 0) return 0;
+    const int KS = (int)((K + 3) / 4);
+    const int us = KS * 4 + 1;
+    const size_t lds = (size_t)(64 * us + 4 * 64) * sizeof(double);
+    const int64_t ncb = (m + 255) / 256;
+    const int64_t slab = 65535LL * 256;
+    for (int64_t r0 = 0; r0 < n; r0 += slab) {
+        const int64_t rows = (n - r0 < slab) ? n - r0 : slab;
+        const int rc = launch(k_dropout_fused<2>, dim3((unsigned)ncb, (unsigned)((rows + 255) / 256)), dim3(256), lds,
+                              (hipStream_t)stream, cell_out ? cell_out + r0 : nullptr, const_cast<float *>(D_hat) + r0 * m,
+                              U + r0 * K, V, pi_d, nzmask + (r0 / 32) * m, gene_out, rows, m, (int)K, KS, us);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 extern "C" int oriana_dropout_metric(double *out2, const float *D_hat, const double *U, const double *V,

@@ -757,6 +757,80 @@ __global__ __launch_bounds__(256) void k_dn_metric_prefix(const uint16_t *__rest
     }
 }
 
+// The sums of k_dn_metric kept per gene and per cell (oriana_metric_nnz_axes for the dense genes; the twin of k_dn_metric): the
+// same staging of 32 cells x 32 genes of float64 factor rows, Lambda = U V^T in float64 at the non-zero counts, and
+//   gene_out (m, 3) += { sum Lambda, sum x log Lambda, sum (x log x - x) } over the gene's non-zero counts of this cell tile,
+//   cell_out (n, 5) += the same three over the cell's non-zero counts of this gene tile, then { sum gconst[j][0],
+//                      sum (gconst[j][1] + x gconst[j][2]) }
+// (caller's gene / row order through col_perm / row_perm; gconst (m, 3) in the caller's gene order; a NULL output skips that
+// axis).  The 32 + 32 partial sums are LDS float64 atomics; one global float64 atomic per term and touched gene / cell leaves
+// the work-group.
+__global__ __launch_bounds__(256) void k_dn_metric_axes(const uint16_t *__restrict__ Xd, const double *__restrict__ U,
+                                                        const double *__restrict__ V, const int32_t *__restrict__ row_perm,
+                                                        const int32_t *__restrict__ col_perm, const double *__restrict__ gconst,
+                                                        double *__restrict__ gene_out, double *__restrict__ cell_out, int64_t n,
+                                                        int ngt, int K) {
+    extern __shared__ double fac[];                // [32 cells][K] then [32 genes][K]
+    __shared__ double gs[32][3], gc[32][3], rs[32][5];
+    __shared__ int gn[32], rn[32];
+    const int gt = blockIdx.x;
+    const int64_t ct = blockIdx.y;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 32 * K; e += 256) {
+        const int r = e / K, k = e - r * K;
+        const int64_t ip = ct * 32 + r, jp = (int64_t)gt * 32 + r;
+        const int64_t i = (ip < n) ? (row_perm ? (int64_t)row_perm[ip] : ip) : -1;
+        const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+        fac[e] = (i >= 0) ? U[i * K + k] : 0.0;
+        fac[32 * K + e] = V[j * K + k];
+    }
+    if (tid < 32) {
+        const int64_t jp = (int64_t)gt * 32 + tid;
+        const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+        for (int q = 0; q < 3; ++q) { gs[tid][q] = 0.0; gc[tid][q] = cell_out ? gconst[3 * j + q] : 0.0; }
+        for (int q = 0; q < 5; ++q) rs[tid][q] = 0.0;
+        gn[tid] = 0;
+        rn[tid] = 0;
+    }
+    __syncthreads();
+    const uint16_t *blk = Xd + (ct * ngt + gt) * 1024;
+    for (int e = tid; e < 1024; e += 256) {
+        const int v = ((e >> 9) << 3) | (e & 7), l = (e >> 3) & 63;
+        const int c = l & 31, h = l >> 5, g = acc_row(v, h);
+        const uint32_t xi = blk[e];
+        if (xi == 0u || ct * 32 + c >= n) continue;
+        const double x = (double)xi;
+        double lam = 0.0;
+        const double *u = fac + c * K, *vv = fac + 32 * K + g * K;
+        for (int k = 0; k < K; ++k) lam += u[k] * vv[k];
+        const double xl = x * log(lam), xx = x * log(x) - x;
+        if (gene_out) {
+            atomicAdd(&gs[g][0], lam); atomicAdd(&gs[g][1], xl); atomicAdd(&gs[g][2], xx);
+            gn[g] = 1;
+        }
+        if (cell_out) {
+            atomicAdd(&rs[c][0], lam); atomicAdd(&rs[c][1], xl); atomicAdd(&rs[c][2], xx);
+            atomicAdd(&rs[c][3], gc[g][0]); atomicAdd(&rs[c][4], gc[g][1] + x * gc[g][2]);
+            rn[c] = 1;
+        }
+    }
+    __syncthreads();
+    if (tid < 32) {
+        if (gene_out && gn[tid]) {
+            const int64_t jp = (int64_t)gt * 32 + tid;
+            const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+            for (int q = 0; q < 3; ++q) atomicAdd(&gene_out[3 * j + q], gs[tid][q]);
+        }
+    } else if (tid < 64) {
+        const int c = tid - 32;
+        const int64_t ip = ct * 32 + c;
+        if (cell_out && rn[c] && ip < n) {
+            const int64_t i = row_perm ? (int64_t)row_perm[ip] : ip;
+            for (int q = 0; q < 5; ++q) atomicAdd(&cell_out[5 * i + q], rs[c][q]);
+        }
+    }
+}
+
 // The data term of the variational bound over the dense block (oriana_elbo_nnz for the dense genes): out2 += {sum x log den,
 // sum lgamma(x + 1)} over the non-zero counts, log den = log sum_k exp(lu_ik + lv_jk) as a float64 log-sum-exp from the float32
 // E[log U], E[log V] (caller's cell / gene order).  One work-group per (cell tile, gene tile).
@@ -968,6 +1042,17 @@ extern "C" int oriana_dense_metric_prefix(const oriana_dense *d, const double *U
     return launch(k_dn_metric_prefix, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256),
                   (size_t)(64 * K + 8 * n_ends) * sizeof(double), (hipStream_t)stream, d->x, U, V, row_perm, col_perm, ends,
                   (int)n_ends, out, d->n, ngt, (int)K);
+}
+
+extern "C" int oriana_dense_metric_axes(const oriana_dense *d, const double *U, const double *V, const int32_t *row_perm,
+                                        const int32_t *col_perm, int64_t K, const double *gene_const, double *gene_out,
+                                        double *cell_out, void *stream) {
+    if (!dense_ok(d) || K <= 0 || K > 1024) return ORIANA_EINVAL;
+    if (!U || !V || (!gene_out && !cell_out) || (cell_out && !gene_const)) return ORIANA_EINVAL;
+    if (d->gd == 0 || d->n == 0) return 0;
+    const int ngt = (int)(d->gd / 32);
+    return launch(k_dn_metric_axes, dim3((unsigned)ngt, (unsigned)((d->n + 31) / 32)), dim3(256), (size_t)64 * K * sizeof(double),
+                  (hipStream_t)stream, d->x, U, V, row_perm, col_perm, gene_const, gene_out, cell_out, d->n, ngt, (int)K);
 }
 
 extern "C" int oriana_dense_elbo(const oriana_dense *d, const float *logU, const float *logV, const int32_t *row_perm,

@@ -119,7 +119,108 @@ __global__ __launch_bounds__(256) void k_metric_nnz(oriana_counts cm, const floa
     }
 }
 
-constexpr int PREFIX_MAX_ENDS = 256;       // K <= 256 in the sliced layout (oriana_kpad), one end per factor at most
+// The sums of k_metric_nnz kept per gene and per cell (models/base.py: gene_deviance, cell_deviance).  One work-group per tile
+// as k_metric_nnz, the rate by the same rule (Lambda = x / s from the row pass, the float64 sum of U, V for the NaN sentinel
+// and for 0), so the per-axis values and the scalar metrics see the same rate.
+//   gene_out (m, 3), caller's gene order: += { sum Lambda, sum x log Lambda, sum (x log x - x) } over the gene's stored entries
+//   cell_out (n, 5), caller's row order : += the same three over the cell's stored entries, then { sum gconst[j][0],
+//                                          sum (gconst[j][1] + x gconst[j][2]) }, gconst (m, 3) in the caller's gene order
+// A NULL output skips that axis.  Per tile the partial sums live in LDS: a gene table as k_count_stats keeps (LDS float64
+// atomics, one per entry and term) and a row table fed as k_cell_bound_nnz feeds its own -- a thread striding by 256 stays with
+// one row per slice (slice lengths are multiples of 64), adds its entries in registers, the 4 lanes of the row are combined by a
+// butterfly and one lane adds the result for the (wave, slice) into the row table.  What leaves the work-group is one float64
+// atomic per term and touched (tile, gene) or (tile, row): the outputs are sums of atomics, reruns agree to the order of the
+// additions (the dense block and the dropout term add into the same arrays the same way).  24 KiB of LDS.
+__global__ __launch_bounds__(256) void k_metric_nnz_axes(oriana_counts cm, const float *__restrict__ s_rs,
+                                                         const double *__restrict__ U, const double *__restrict__ V, int K,
+                                                         const double *__restrict__ gconst, double *__restrict__ gene_out,
+                                                         double *__restrict__ cell_out) {
+    __shared__ double gs[TILE][3];
+    __shared__ double gc[TILE][3];
+    __shared__ double rs[TILE][5];
+    __shared__ int gn[TILE], rn[TILE];
+    const int tid = threadIdx.x, rl = (tid & 63) >> 2;
+    const int64_t t = blockIdx.x;
+    const int64_t rb = t / cm.ncb, cb = t - rb * cm.ncb;
+    const int64_t rbase = cm.roff[t];
+    {
+        const int64_t jp = cb * TILE + tid;
+        const bool ok = cell_out && jp < cm.m;
+        const int64_t j = ok ? (cm.col_perm ? (int64_t)cm.col_perm[jp] : jp) : 0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { gs[tid][q] = 0.0; gc[tid][q] = ok ? gconst[3 * j + q] : 0.0; }
+#pragma unroll
+        for (int q = 0; q < 5; ++q) rs[tid][q] = 0.0;
+        gn[tid] = 0;
+        rn[tid] = 0;
+    }
+    __syncthreads();
+    for (int sl = 0; sl < 16; ++sl) {
+        const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+        if (s0 == s1) continue;                                  // (uniform over the work-group)
+        const int r = sl * 16 + rl;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
+        int cnt = 0;
+        for (uint32_t slot = s0 + tid; slot < s1; slot += 256) {
+            const oriana_rowrec rec = cm.rowrec[rbase + slot];
+            if (rec.x == 0.f) continue;
+            const float s = s_rs[rbase + slot];
+            const double x = (double)rec.x;
+            const int c = rec.col;
+            double lam;
+            if (s == s && s != 0.f) {
+                lam = x / (double)s;
+            } else {
+                const int64_t ip = rb * TILE + r, jp = cb * TILE + c;
+                const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+                const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+                lam = 0.0;
+                for (int k = 0; k < K; ++k) lam += U[i * K + k] * V[j * K + k];
+            }
+            const double xl = x * log(lam), xx = x * log(x) - x;
+            if (gene_out) {
+                atomicAdd(&gs[c][0], lam);
+                atomicAdd(&gs[c][1], xl);
+                atomicAdd(&gs[c][2], xx);
+                gn[c] = 1;
+            }
+            if (cell_out) {
+                a0 += lam; a1 += xl; a2 += xx;
+                a3 += gc[c][0];
+                a4 += gc[c][1] + x * gc[c][2];
+                cnt = 1;
+            }
+        }
+        if (cell_out) {
+            // (a slice's length is a multiple of 64: the lanes of a wave leave the loop together)
+            a0 += __shfl_xor(a0, 1, 64); a0 += __shfl_xor(a0, 2, 64);
+            a1 += __shfl_xor(a1, 1, 64); a1 += __shfl_xor(a1, 2, 64);
+            a2 += __shfl_xor(a2, 1, 64); a2 += __shfl_xor(a2, 2, 64);
+            a3 += __shfl_xor(a3, 1, 64); a3 += __shfl_xor(a3, 2, 64);
+            a4 += __shfl_xor(a4, 1, 64); a4 += __shfl_xor(a4, 2, 64);
+            cnt |= __shfl_xor(cnt, 1, 64); cnt |= __shfl_xor(cnt, 2, 64);
+            if ((tid & 3) == 0 && cnt) {
+                atomicAdd(&rs[r][0], a0); atomicAdd(&rs[r][1], a1); atomicAdd(&rs[r][2], a2);
+                atomicAdd(&rs[r][3], a3); atomicAdd(&rs[r][4], a4);
+                rn[r] = 1;
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t jp = cb * TILE + tid, ip = rb * TILE + tid;
+    if (gene_out && gn[tid] && jp < cm.m) {
+        const int64_t j = cm.col_perm ? (int64_t)cm.col_perm[jp] : jp;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) atomicAdd(&gene_out[3 * j + q], gs[tid][q]);
+    }
+    if (cell_out && rn[tid] && ip < cm.n) {
+        const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) atomicAdd(&cell_out[5 * i + q], rs[tid][q]);
+    }
+}
+
+constexpr int PREFIX_MAX_ENDS = 256;      // K <= 256 in the sliced layout (oriana_kpad), one end per factor at most
 
 // The deviance sums of every prefix of the factors (models/base.py: deviance_path): with Lambda^(k)_ij = sum_{l < k} FU[ip, l]
 // FV[jp, l] the running float32 sum over the factor images (packed row / gene order, row stride Kp, columns already in the
@@ -340,6 +441,20 @@ extern "C" int oriana_metric_nnz(const oriana_counts *cm, const float *s_rs, con
     if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
     hipLaunchKernelGGL(k_metric_nnz, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, U, V, (int)K,
                        out4);
+    ORIANA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int oriana_metric_nnz_axes(const oriana_counts *cm, const float *s_rs, const double *U, const double *V,
+                                      int64_t K, const double *gene_const, double *gene_out, double *cell_out,
+                                      void *stream) {
+    if (!cm || !s_rs || !U || !V || K <= 0 || (!gene_out && !cell_out) || (cell_out && !gene_const)) return ORIANA_EINVAL;
+    if (oriana_kpad(K) == 0) return ORIANA_EKRANGE;
+    const int64_t nt = cm->nrb * cm->ncb;
+    if (nt == 0 || cm->rslots == 0) return 0;
+    if (nt > 0x7fffffffLL) return ORIANA_EINVAL;
+    hipLaunchKernelGGL(k_metric_nnz_axes, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, *cm, s_rs, U, V, (int)K,
+                       gene_const, gene_out, cell_out);
     ORIANA_LAUNCH_CHECK();
     return 0;
 }

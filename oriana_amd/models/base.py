@@ -581,7 +581,9 @@ class FactorModel:
             self._xconst = (colsum, colnnz, out2)
         return self._xconst
 
-    def _metric_terms(self):
+    def _rate_pass(self):
+        """The row pass over float32 casts of U_hat, V_eff: leaves s = x / Lambda in the row-side slots (ws.s_rs), the rate every
+        sum over the stored entries reads.  Returns the float64 (U, V) the fall-back entries are recomputed from."""
         ct, K, n, m, dev = self.counts, self.k, self.n, self.m, self.device
         st = stream_ptr()
         U, V = self._U_hat, self._effective_V().contiguous()
@@ -596,6 +598,13 @@ class FactorModel:
         # (hybrid layout: the sliced part covers the packed genes [gd, m); the dense genes are summed in float64)
         call('oriana_row_pass', ct.sparse_struct, ptr(FU), ptr(FV) + 4 * ct.gd * ws.Kp, None, ptr(ws.R), ptr(ws.s_cs), None,
              ptr(ws.s_rs), ptr(ws.tile_flag), K, st)
+        return U, V
+
+    def _metric_terms(self):
+        ct, K, n, m, dev = self.counts, self.k, self.n, self.m, self.device
+        st = stream_ptr()
+        ws = self._ws
+        U, V = self._rate_pass()
         nz = torch.zeros(4, dtype=torch.float64, device=dev)      # sum Lambda, sum x log Lambda, sum Lambda^2, sum x Lambda
         call('oriana_metric_nnz', ct.sparse_struct, ptr(ws.s_rs), ptr(U), ptr(V), K, ptr(nz), st)
         if ct.dense is not None:
@@ -627,23 +636,33 @@ class FactorModel:
         one = torch.ones(self.m, dtype=torch.float64, device=self.device)
         return torch.zeros_like(one), one
 
-    def _ll_constants(self):
-        """What the log-likelihoods hold apart from the rate matrix: sum_j nnz_j log pi_j, ll(X | X), ll(X | mean) (device
-        scalars) and the count constants."""
-        colsum, colnnz, xc = self._count_constants()
+    def _gene_ll_terms(self):
+        """Per gene, what the log-likelihoods hold apart from the rate matrix (device float64, global under row sharding):
+        lpi = log pi_j, mu = the mean count, t = log(pi e^-mu + 1 - pi) (one zero's term of ll(X | mean)), log_mu (0 for a gene
+        without counts), nnz_lpi = nnz_j log pi_j and the gene's share of ll(X | mean)."""
+        colsum, colnnz, _ = self._count_constants()
         lpi, pi = self._log_pi()
         has = colnnz > 0
-        nnz_lpi = torch.where(has, colnnz * lpi, torch.zeros_like(lpi)).sum()
-        ll_x = nnz_lpi + xc[0]
+        nnz_lpi = torch.where(has, colnnz * lpi, torch.zeros_like(lpi))
         ntot = float(self.n_total)
         mu = colsum / ntot
         # log(pi e^-mu + 1 - pi) as a log-sum-exp.  Without a dropout node (pi = 1) the literal form is log e^-mu, which
         # underflows to log 0 = -inf once mu passes ~745: -inf for such a gene with a zero among its counts, 0 * -inf = NaN
         # for one without, and explained_deviance NaN either way.  (With pi <= 1 - 1e-10 the 1 - pi keeps it finite.)
-        zero_term = (ntot - colnnz) * torch.logaddexp(lpi - mu, torch.log1p(-pi))
-        nz_term = torch.where(has, colnnz * (lpi - mu) + colsum * torch.log(torch.where(has, mu, torch.ones_like(mu))),
-                              torch.zeros_like(mu))
-        ll_mean = (zero_term + nz_term).sum()
+        t = torch.logaddexp(lpi - mu, torch.log1p(-pi))
+        log_mu = torch.log(torch.where(has, mu, torch.ones_like(mu)))
+        zero_term = (ntot - colnnz) * t
+        nz_term = torch.where(has, colnnz * (lpi - mu) + colsum * log_mu, torch.zeros_like(mu))
+        return dict(lpi=lpi, mu=mu, t=t, log_mu=log_mu, has=has, nnz_lpi=nnz_lpi, mean=zero_term + nz_term)
+
+    def _ll_constants(self):
+        """What the log-likelihoods hold apart from the rate matrix: sum_j nnz_j log pi_j, ll(X | X), ll(X | mean) (device
+        scalars) and the count constants."""
+        xc = self._count_constants()[2]
+        g = self._gene_ll_terms()
+        nnz_lpi = g['nnz_lpi'].sum()
+        ll_x = nnz_lpi + xc[0]
+        ll_mean = g['mean'].sum()
         return nnz_lpi, ll_x, ll_mean, xc
 
     def _loglikelihoods(self):
@@ -681,6 +700,92 @@ class FactorModel:
         _, _, _, nz, zz, xc = self._loglikelihoods()
         # sum_N (Lambda - x)^2 + sum_{Z - M} Lambda^2
         return float(torch.sqrt(torch.clamp(nz[2] - 2.0 * nz[3] + xc[1] + zz[1], min=0.0)))
+
+    # ---- the deviance per gene and per cell ---------------------------------------------------------------
+    # The three log-likelihoods above are sums over the entries (i, j); kept per gene j (summed over the cells) or per cell i
+    # (summed over the genes), in the notation above _count_constants and with t_j = log(pi_j e^-mu_j + 1 - pi_j):
+    #   factors: x != 0: log pi_j - Lambda_ij + x log Lambda_ij     x == 0, not in M: log(pi_j e^-Lambda_ij + 1 - pi_j)    in M: 0
+    #   counts : x != 0: log pi_j + x log x - x                     x == 0: 0
+    #   mean   : x != 0: log pi_j - mu_j + x log mu_j               x == 0: t_j
+    # The sums over the non-zeros of a gene / a cell come from oriana_metric_nnz_axes (oriana_dense_metric_axes for the dense
+    # genes of a hybrid layout) behind the same row pass as _metric_terms, the zero term of a dropout node from
+    # oriana_dropout_metric_axes.  Without a dropout node the zero term is -Lambda and needs no pass: per gene
+    # factors_j = -(V_eff su)_j + sum_{N_j} x log Lambda (su the column sums of U_hat), per cell -(U_hat sv)_i + sum_{N_i} ...
+    # Per cell the mean's sum over ALL genes is sum_j t_j + sum_{N_i} (c1_j + x c2_j), c1_j = log pi_j - mu_j - t_j,
+    # c2_j = log mu_j: the kernels read {log pi_j, c1_j, c2_j} per gene.  A gene without a count has mean 0, and its t_j is
+    # log 1 = 0 exactly (the log-sum-exp of _gene_ll_terms may leave an ulp there): counts_j = mean_j = 0.
+    def _axis_terms(self, genes, cells):
+        """(factors, counts, mean) as host float64 arrays for the gene axis (m,), the cell axis (n_local,) or both: a dict
+        with 'genes' / 'cells'.  Only the requested axis is computed.  Under row sharding the gene arrays are summed over the
+        ranks in one packed all-reduce; the cell arrays are this rank's rows against the global per-gene mean."""
+        ct, K, n, m, dev = self.counts, self.k, self.n, self.m, self.device
+        if self.zi and K > 256:
+            raise ValueError('gene_deviance() / cell_deviance() with a dropout node need k <= 256')
+        st, ws = stream_ptr(), self._ws
+        g = self._gene_ll_terms()
+        zero = torch.zeros_like(g['t'])
+        t = torch.where(g['has'], g['t'], zero)
+        nnz_lpi = g['nnz_lpi']
+        U, V = self._rate_pass()
+        gene_out = torch.zeros(max(m, 1), 3, dtype=torch.float64, device=dev) if genes else None
+        cell_out = torch.zeros(max(n, 1), 5, dtype=torch.float64, device=dev) if cells else None
+        gconst = torch.stack([g['lpi'], g['lpi'] - g['mu'] - t, g['log_mu']], dim=1).contiguous() if cells else None
+        call('oriana_metric_nnz_axes', ct.sparse_struct, ptr(ws.s_rs), ptr(U), ptr(V), K, ptr(gconst), ptr(gene_out),
+             ptr(cell_out), st)
+        if ct.dense is not None:
+            call('oriana_dense_metric_axes', ct.dense.c_struct, ptr(U), ptr(V), ptr(ct.row_perm), ptr(ct.col_perm), K,
+                 ptr(gconst), ptr(gene_out), ptr(cell_out), st)
+        zg = zc = None
+        if self.zi:
+            # (the padded gene axis of the dropout node's matrices, as in _metric_terms: pi_d = 0 there, the term is 0)
+            zg = torch.zeros(self._mp, dtype=torch.float64, device=dev) if genes else None
+            zc = torch.zeros(max(n, 1), dtype=torch.float64, device=dev) if cells else None
+            call('oriana_dropout_metric_axes', ptr(zg), ptr(zc), ptr(self._Dp), ptr(U), ptr(self._padG(V, 'Vm')),
+                 ptr(self._padG(self.pi_d.tensor, 'pim')), ptr(self._nzmask), n, self._mp, K, st)
+        out = {}
+        if genes:
+            packed = torch.cat([gene_out[:m].reshape(-1), zg[:m] if self.zi else U.sum(0)])
+            odist.all_reduce_sum(packed, self.pg)
+            go, tail = packed[:3 * m].reshape(m, 3), packed[3 * m:]
+            if self.zi:
+                factors = tail + nnz_lpi - go[:, 0] + go[:, 1]
+            else:                              # sum_i Lambda_ij = (V_eff su)_j: sum_N Lambda cancels against the zero term
+                factors = -(V @ tail) + nnz_lpi + go[:, 1]
+            counts = nnz_lpi + go[:, 2]
+            mean = torch.where(g['has'], g['mean'], zero)
+            out['genes'] = tuple(a.cpu().numpy() for a in (factors, counts, mean))
+        if cells:
+            co = cell_out[:n]
+            if self.zi:
+                factors = zc[:n] + co[:, 3] - co[:, 0] + co[:, 1]
+            else:
+                factors = -(U @ V.sum(0)) + co[:, 3] + co[:, 1]
+            counts = co[:, 3] + co[:, 2]
+            mean = t.sum() + co[:, 4]
+            out['cells'] = tuple(a.cpu().numpy() for a in (factors, counts, mean))
+        return out
+
+    @staticmethod
+    def _axis_result(factors, counts, mean):
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return {'factors': factors, 'counts': counts, 'mean': mean,
+                    'reconstruction_deviance': -2.0 * (factors - counts),
+                    'explained_deviance': (factors - mean) / (counts - mean)}
+
+    def gene_deviance(self):
+        """The deviance metrics per gene: a dict of (m,) float64 arrays in the caller's gene order.  'factors', 'counts',
+        'mean': each gene's share of loglikelihood_X(given=...) (they sum to it, up to the order of the additions);
+        'reconstruction_deviance' = -2 (factors - counts) and 'explained_deviance' = (factors - mean) / (counts - mean) per
+        gene, the literal float64 values: a gene without a count has counts = mean = 0 and gives a non-finite value (NaN when
+        its rate is 0 as well), a rate that is exactly 0 at a non-zero count -inf (+inf) for that gene alone.  Under row
+        sharding every rank returns the same arrays.  Nothing of the model's state is written.  With a dropout node: k <= 256."""
+        return self._axis_result(*self._axis_terms(True, False)['genes'])
+
+    def cell_deviance(self):
+        """gene_deviance() along the other axis: a dict of (n_local,) float64 arrays in the caller's row order, each cell's
+        share of the three log-likelihoods (against the global per-gene mean under row sharding) and the two deviances of
+        the cell.  A cell without a count has counts = 0 and a finite explained deviance."""
+        return self._axis_result(*self._axis_terms(False, True)['cells'])
 
     # ---- the deviance along a prefix of the factors ------------------------------------------------------
     # The columns of U_hat / V_hat come out in the arbitrary order of the start.  With an order o of the factors and
