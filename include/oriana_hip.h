@@ -914,6 +914,34 @@ int oriana_zq_sparse_zigap_resident(oriana_resident *h, float *DSZ_hat, float *D
                                     const float *log_U_hat, const float *log_V_hat, const float *S_tilde, const float *S_hat,
                                     const float *D_hat, void *stream);
 
+/* ---- k-means on the cell factors (csrc/kmeans.hip) ------------------------------------------------------------
+ * The reference's pipeline ends in sklearn.cluster.KMeans(n_clusters, n_init=100) on np.log(U) (experiments/clustering.py).
+ * One Lloyd half-step of R independent restarts over the same rows Y (n, d) float32, row stride ldy >= d:
+ *   d2(i, c) = sum_k (y_ik - c_rck)^2 in float32 (the direct difference form, k ascending), label = the arg-min over c (the
+ *   smallest index wins an exact tie); sums[r, c, :] = the sum of the rows labelled c, counts[r, c] their exact number,
+ *   inertia[r] = sum_i d2(i, label).  labels (n) or NULL receives the labels of restart label_restart only, mind (R, n) or NULL
+ *   the minimum distances.  A row tile is read once per group of oriana_kmeans_group(d, C) restarts; no (n, C) array exists.
+ * Deterministic: no float atomics; two calls with the same inputs and the same `blocks` (work-groups along the rows; 0: sized
+ * from the device) agree bit for bit, and a restart's outputs do not depend on the other restarts of the call.  The sums add
+ * at most oriana_kmeans_partial_rows() rows in float32 before the partial sum is promoted to float64.
+ * scratch: oriana_kmeans_scratch_bytes(n, d, C, R, blocks) bytes, 16-byte aligned, contents undefined on entry and exit.
+ * All arguments are validated before any HIP call: n < 0, d < 1, C < 1, R < 1, ldy < d, blocks < 0 -> ORIANA_EINVAL;
+ * C > oriana_kmeans_max_centers(d) -> ORIANA_EKRANGE; a NULL required pointer -> ORIANA_EINVAL.  n = 0: zeroed outputs. */
+int oriana_kmeans_step(const float *Y, int64_t n, int64_t d, int64_t ldy, const float *centers, int64_t C, int64_t R,
+                       double *sums, int64_t *counts, double *inertia, int32_t *labels, int64_t label_restart, float *mind,
+                       void *scratch, int64_t blocks, void *stream);
+/* The largest C served at feature width d: 8192 / pad4(d) for d <= 256, 0 for any other d. */
+int64_t oriana_kmeans_max_centers(int64_t d);
+/* Restarts that share one read of a row tile (the waves of a work-group): 4, or 2 where the partial sums of 4 exceed the LDS;
+ * 0 for an unsupported (d, C). */
+int64_t oriana_kmeans_group(int64_t d, int64_t C);
+/* Bytes of scratch of a step (negative: the argument error the step would return). */
+int64_t oriana_kmeans_scratch_bytes(int64_t n, int64_t d, int64_t C, int64_t R, int64_t blocks);
+/* The largest number of rows added in float32 before a partial sum is promoted to float64. */
+int64_t oriana_kmeans_partial_rows(void);
+/* Rows of a tile (the unit `blocks` divides). */
+int64_t oriana_kmeans_tile_rows(void);
+
 #ifdef __cplusplus
 }
 #endif

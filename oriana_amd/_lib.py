@@ -165,6 +165,12 @@ _SIGS = {
     'oriana_inverse_digamma_f64': (c_int, [_P, _P, _I, _P]),
     'oriana_sigmoid_f64': (c_int, [_P, _P, _I, _P]),
     'oriana_logit_f64': (c_int, [_P, _P, _I, _P]),
+    'oriana_kmeans_step': (c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    'oriana_kmeans_max_centers': (_I, [_I]),
+    'oriana_kmeans_group': (_I, [_I, _I]),
+    'oriana_kmeans_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_kmeans_partial_rows': (_I, []),
+    'oriana_kmeans_tile_rows': (_I, []),
 }
 
 _lib = None

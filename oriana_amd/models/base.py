@@ -869,8 +869,36 @@ class FactorModel:
             ll_uv = -all_lam[ks - 1] + float(nnz_lpi) + nz[:, 1]
         return prefix.assemble_path(order, ks, ll_uv, float(ll_x), float(ll_mean))
 
+    # ---- clustering the cells (the last step of the reference's pipeline, experiments/clustering.py) -----------------
+    def cluster_cells(self, n_clusters, features='log_mean', factors=None, **kmeans_kw):
+        """k-means of the cells on the fitted cell factors, on the device (cluster.kmeans; its keywords pass through).
+
+        features : 'log_mean' -- float32(log(U_hat)), the logarithm taken in float64: the reference's ``np.log(U)``; 'mean_log' --
+            the model's own float32 E[log U].  factors : an optional index array of the columns to use, for example
+            ``model.factor_order()[:k]``.  Returns the dict of cluster.kmeans plus 'features' (the (n_local, d) float32 matrix that
+            was clustered, NumPy) and 'factors' (the column indices, int64).  Under row sharding the model's process group is used:
+            every rank returns the same centres and its own rows' labels.  Nothing of the model's state is written."""
+        from .. import cluster
+        if features not in ('log_mean', 'mean_log'):
+            raise ValueError("features must be 'log_mean' or 'mean_log'")
+        cols = np.arange(self.k, dtype=np.int64) if factors is None else np.asarray(factors)
+        if cols.ndim != 1 or cols.size < 1 or cols.dtype.kind not in 'iu' or cols.min() < 0 or cols.max() >= self.k:
+            raise ValueError('factors must be a non-empty 1-D array of column indices within [0, %d)' % self.k)
+        cols = cols.astype(np.int64)
+        if 'pg' in kmeans_kw:
+            raise ValueError('cluster_cells() uses the process group of the model')
+        if features == 'log_mean':
+            F = torch.log(self.U.buffer).to(torch.float32)          # (the accessor factors() reads: a lazy U_hat is evaluated)
+        else:
+            F = self._log_U_hat
+        F = F.index_select(1, torch.as_tensor(cols, device=self.device)).contiguous()
+        out = cluster.kmeans(F, n_clusters, pg=self.pg, **kmeans_kw)
+        out['features'] = F.cpu().numpy()
+        out['factors'] = cols
+        return out
+
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
-    _PARAMS = ('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
+    _PARAMS =('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
 
     def state(self):
         """Host copy of every parameter and expectation, keyed like the oracle / golden files."""
