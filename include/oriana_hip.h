@@ -942,6 +942,51 @@ int64_t oriana_kmeans_partial_rows(void);
 /* Rows of a tile (the unit `blocks` divides). */
 int64_t oriana_kmeans_tile_rows(void);
 
+/* ---- exact k nearest neighbours of the cells (csrc/knn.hip) --------------------------------------------------
+ * For every query row of Q (nq, d) float32, row stride ldq >= d, the k nearest of the candidate rows Y (n, d) float32, row
+ * stride ldy >= d, by brute force; no distance matrix exists.  Query row i has the global index q0 + i, candidate row j the
+ * global index y0 + j; the indices written are global and int32 (y0 + n <= 2^31 - 1).
+ *   the pair   f(q, c) = sum_j (q_j - c_j)^2 in float32: one sequential fmaf chain over j ascending that starts from 0, every
+ *              difference rounded once -- the chain of oriana_kmeans_step.  Zero padding of the features adds fmaf(0, 0, acc)
+ *              and is exact.  f(q, c) == f(c, q) bit for bit (the chain is symmetric under negation of the differences).
+ *   the row    the k candidates smallest under the total order (f, global candidate index), both ascending, in that order:
+ *              idx (nq, k) int32 and d2 (nq, k) float32, row-major.  With exclude_self the candidate whose global index equals
+ *              the query's is skipped -- that one row only: other bit-identical rows stay eligible and come back with f = 0.
+ *              Where fewer than k candidates exist the tail is idx = -1, d2 = +inf.  A pair whose f overflows float32 counts
+ *              as absent.
+ *   merge = 1  the incoming idx / d2 rows are valid rows of the same form made from OTHER candidates; the k best of the union
+ *              are left in place.
+ * Partition independence: the value of a pair does not depend on how the work is tiled, and a row is the k smallest of a set
+ * under a total order, so the outputs are the same bit for bit for any `blocks` (ranges the candidates are cut into inside a
+ * call; 0: sized from the device), for any split of the candidates over merging calls in any order, and for any split of the
+ * queries over calls with the matching q0.  No atomics: every list has one writer and a fixed order.
+ * scratch: oriana_knn_scratch_bytes_for(nq, n, d, k, blocks, Y, ldy) bytes (oriana_knn_scratch_bytes(..) is never less),
+ * 16-byte aligned, contents undefined on entry and exit.
+ * All arguments are validated before any HIP call: a negative size, index base or `blocks`, d < 1, k < 1, ldq < d, ldy < d,
+ * nq or y0 + n beyond 2^31 - 1, n beyond 2^31 - 9 -> ORIANA_EINVAL; d > 256 or k > oriana_knn_max_neighbors(d) -> ORIANA_EKRANGE; a NULL idx, d2
+ * or scratch, a NULL Q with nq > 0 or Y with n > 0, a scratch that is not 16-byte aligned -> ORIANA_EINVAL.  nq = 0 is a
+ * no-op; n = 0 without merge writes the padding values, with merge nothing. */
+int oriana_knn(const float *Q, int64_t nq, int64_t ldq, int64_t q0, const float *Y, int64_t n, int64_t ldy, int64_t y0,
+               int64_t d, int64_t k, int exclude_self, int merge, int32_t *idx, float *d2, void *scratch, int64_t blocks,
+               void *stream);
+/* The largest k served at feature width d, from the LDS of a work-group (the query tile and the lists of four waves):
+ * (160 KiB - 260 pad4(d)) / 2048 for d <= 256 (47 at d = 256, 67 at d = 100), 0 for any other d. */
+int64_t oriana_knn_max_neighbors(int64_t d);
+/* Bytes of scratch that serve a call with any Y (negative: the argument error the call would return): a padded image of the
+ * candidates (n pad4(d) floats), the partial lists (8 k bytes per query, wave and range) and a copy of the incoming rows. */
+int64_t oriana_knn_scratch_bytes(int64_t nq, int64_t n, int64_t d, int64_t k, int64_t blocks);
+/* Bytes of scratch of the call with this Y and ldy: no image where Y itself serves as one (d and ldy multiples of four, Y
+ * 16-byte aligned; Y is not dereferenced). */
+int64_t oriana_knn_scratch_bytes_for(int64_t nq, int64_t n, int64_t d, int64_t k, int64_t blocks, const float *Y, int64_t ldy);
+/* Queries of a tile (one work-group along the queries). */
+int64_t oriana_knn_tile_rows(void);
+/* Waves of a work-group at (d, k): 8 where the lists of eight waves fit the LDS beside the query tile, else 4 (ORIANA_KNN_WAVES=4
+ * in the environment: always 4, for tuning runs; no result depends on it); 0 for an unsupported (d, k). */
+int64_t oriana_knn_waves(int64_t d, int64_t k);
+/* Ranges the candidates of a call are cut into (at most 64 / oriana_knn_waves(d, k), at least one 8-candidate step per wave);
+ * negative: the argument error. */
+int64_t oriana_knn_splits(int64_t nq, int64_t n, int64_t d, int64_t k, int64_t blocks);
+
 #ifdef __cplusplus
 }
 #endif

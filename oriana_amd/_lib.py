@@ -171,6 +171,13 @@ _SIGS = {
     'oriana_kmeans_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
     'oriana_kmeans_partial_rows': (_I, []),
     'oriana_kmeans_tile_rows': (_I, []),
+    'oriana_knn': (c_int, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, c_int, c_int, _P, _P, _P, _I, _P]),
+    'oriana_knn_max_neighbors': (_I, [_I]),
+    'oriana_knn_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_knn_scratch_bytes_for': (_I, [_I, _I, _I, _I, _I, _P, _I]),
+    'oriana_knn_tile_rows': (_I, []),
+    'oriana_knn_waves': (_I, [_I, _I]),
+    'oriana_knn_splits': (_I, [_I, _I, _I, _I, _I]),
 }
 
 _lib = None

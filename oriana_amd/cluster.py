@@ -2,7 +2,10 @@
 """k-means on the device: all restarts of a run advance together through oriana_kmeans_step (csrc/kmeans.hip), which reads a row
 tile once for a group of restarts and emits only per-cluster sums.  The reference's pipeline ends in
 ``KMeans(n_clusters, n_init=100).fit(np.log(U))`` (experiments/clustering.py); this is that step without the host copy.
-DESIGN.md section 5i."""
+DESIGN.md section 5i.
+
+knn() is the exact k-nearest-neighbour graph of the same rows through oriana_knn (csrc/knn.hip): brute force, no distance
+matrix, results independent of every partition of the work.  DESIGN.md section 5j."""
 import numpy as np
 import torch
 
@@ -10,7 +13,8 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 from . import dist as odist
 
-__all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows', 'tile_rows', 'draws', 'distinct_rows']
+__all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows', 'tile_rows', 'draws', 'distinct_rows',
+           'knn', 'knn_plan', 'knn_step', 'max_neighbors']
 
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
@@ -112,8 +116,10 @@ class _Rows:
             sizes = t.cpu().numpy()
             self.row0 = int(sizes[:self.rank].sum())
             self.N = int(sizes.sum())
+            self.sizes = [int(v) for v in sizes]
         else:
             self.row0, self.N = 0, self.n
+            self.sizes = [self.n]
 
     def gather(self, g):
         """The rows with global indices g (int64 device tensor, any shape) as float32 (.., d): a zero buffer to which the
@@ -311,3 +317,161 @@ def kmeans(Y, n_clusters, n_init=10, max_iter=300, tol=1e-4, init='k-means++', s
     return {'labels': labels.cpu().numpy(), 'centers': all_c[best].cpu().numpy(), 'inertia': float(inertias_h[best]),
             'n_iter': int(n_iters_h[best]), 'inertias': inertias_h, 'converged': conv.cpu().numpy(), 'best': best,
             'n_iters': n_iters_h, 'all_centers': all_c.cpu().numpy(), 'init_centers': init_c.cpu().numpy()}
+
+
+# ---- exact k nearest neighbours (csrc/knn.hip) ----------------------------------------------------------------
+def max_neighbors(d):
+    """The largest n_neighbors served at feature width d (0: d is not served)."""
+    return int(_lib.load().oriana_knn_max_neighbors(int(d)))
+
+
+def _rows_ld(T):
+    """(rows, row stride) of a 2-D float32 tensor with unit column stride, as the kernels take it."""
+    n, d = int(T.shape[0]), int(T.shape[1])
+    return n, (int(T.stride(0)) if n > 1 else d)
+
+
+def _knn_scratch_bytes(nq, n, d, k, blocks, y_ptr, ldy):
+    """Bytes of scratch of one oriana_knn call whose candidates start at y_ptr with row stride ldy."""
+    nbytes = int(_lib.load().oriana_knn_scratch_bytes_for(nq, n, d, k, int(blocks), y_ptr, ldy))
+    if nbytes < 0:
+        raise _lib.OrianaHipError('oriana_knn_scratch_bytes_for failed with code %d' % nbytes)
+    return nbytes
+
+
+def knn_plan(nq, n, d, k, blocks=0, y_ptr=16, ldy=None, candidate_chunk=None, query_block=None, budget=None):
+    """How knn() cuts nq queries against n candidates (of its largest shard) into oriana_knn calls: (query_block,
+    candidate_chunk, scratch bytes that serve every call issued).  Needs no device.  The scratch of a call is NOT monotone in its
+    queries (fewer query tiles are cut into more candidate ranges, each with partial lists of its own), so the bytes are the
+    largest need over the block sizes that occur: the full block and the shorter last one.  What is not given is chosen so that the scratch stays
+    within `budget` (default SCRATCH_BUDGET): first the candidates are halved until a padded image of a chunk (needed only where
+    Y does not serve as the image: y_ptr, ldy) takes at most half the budget, then the queries -- whose partial lists and copy
+    of the incoming rows are the part of the scratch that no candidate chunk shrinks -- are halved, in whole tiles, until the
+    call fits.  Either split leaves the result unchanged bit for bit."""
+    nq, n, d, k = int(nq), int(n), int(d), int(k)
+    budget = SCRATCH_BUDGET if budget is None else int(budget)
+    ldy = d if ldy is None else int(ldy)
+    tile = int(_lib.load().oriana_knn_tile_rows())
+
+    def need(qb, c):
+        sizes = {min(qb, nq)} | ({nq % qb} if nq > qb else set())
+        return max(_knn_scratch_bytes(b, min(c, n), d, k, blocks, y_ptr, ldy) for b in sizes)
+
+    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
+    qb = int(query_block) if query_block is not None else max(nq, 1)
+    if candidate_chunk is None:
+        while chunk > 1 and need(tile, chunk) > budget // 2:
+            chunk = (chunk + 1) // 2
+    if query_block is None:
+        while qb > tile and need(qb, chunk) > budget:
+            qb = max(tile, -(-qb // (2 * tile)) * tile)
+    return qb, chunk, need(qb, chunk)
+
+
+def knn_step(Q, Y, idx, d2, q0=0, y0=0, exclude_self=False, merge=False, blocks=0, scratch=None):
+    """One oriana_knn call: the rows of Q (nq, d) against the candidates Y (n, d), both float32 device tensors (row stride >= d,
+    unit column stride) whose first rows have the global indices q0 and y0; idx (nq, k) int32 and d2 (nq, k) float32, contiguous,
+    are written, or with `merge` merged with what they hold."""
+    nq, ldq = _rows_ld(Q)
+    n, ldy = _rows_ld(Y)
+    d, k = int(Q.shape[1]), int(idx.shape[1])
+    nbytes = _knn_scratch_bytes(nq, n, d, k, blocks, ptr(Y) if n else None, ldy)
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=idx.device)
+    elif scratch.numel() * scratch.element_size() < nbytes:            # (oriana_knn itself takes no size: it would write past it)
+        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    call('oriana_knn', ptr(Q) if nq else None, nq, ldq, int(q0), ptr(Y) if n else None, n, ldy, int(y0), d, k,
+         1 if exclude_self else 0, 1 if merge else 0, ptr(idx), ptr(d2), ptr(scratch), int(blocks), stream_ptr())
+
+
+def _check_rows(T, what):
+    if not isinstance(T, torch.Tensor) or T.dim() != 2:
+        raise ValueError('%s must be a 2-D torch tensor' % what)
+    if T.dtype != torch.float32:
+        raise ValueError('%s must be float32, got %s' % (what, T.dtype))
+    if T.shape[0] > 1 and T.shape[1] > 0 and (T.stride(1) != 1 or T.stride(0) < T.shape[1]):
+        raise ValueError('the columns of %s must be contiguous and its rows must not overlap' % what)
+    if T.shape[0] == 1 and T.shape[1] > 1 and T.stride(1) != 1:
+        raise ValueError('the columns of %s must be contiguous' % what)
+
+
+def knn(Y, n_neighbors, queries=None, exclude_self=None, pg=None, candidate_chunk=None, blocks=0, query_block=None):
+    """The exact n_neighbors nearest rows of Y, an (n, d) float32 device tensor (unit column stride, row stride >= d; with `pg`:
+    this rank's rows), for every row of `queries` ((n_q, d) float32, same device), or of Y itself.
+
+    The squared distance of a pair is sum_j (q_j - y_j)^2 in float32 as one sequential fma chain (oriana_knn); a row of the
+    result holds the candidates smallest under (distance, index), in that order, padded with index -1 / distance +inf where
+    fewer exist.  exclude_self (default: True exactly when queries is None) leaves a row out of its own list -- only itself:
+    other identical rows come back at distance 0.  candidate_chunk splits the candidates over merging calls and query_block
+    the queries over calls (default: one call unless its scratch exceeds SCRATCH_BUDGET, see knn_plan()); `blocks` is
+    oriana_knn's.  None of them changes a bit of the result.
+
+    Under row sharding the candidates are every rank's rows in rank order under their global indices: shard after shard is made
+    available on all ranks by an all-reduce onto a zero buffer and merged in.  The concatenated output of the ranks equals a
+    one-process run on the concatenated rows bit for bit; explicit queries are each rank's own.
+
+    Returns {'indices': (n_q, k) int32, 'sq_distances': (n_q, k) float32}, device tensors.  ValueError before any launch for a
+    wrong dtype, rank or device, non-finite entries, n_neighbors < 1 or beyond max_neighbors(d)."""
+    _check_rows(Y, 'Y')
+    if queries is not None:
+        _check_rows(queries, 'queries')
+        if int(queries.shape[1]) != int(Y.shape[1]):
+            raise ValueError('queries have %d columns, Y has %d' % (queries.shape[1], Y.shape[1]))
+    if exclude_self is None:
+        exclude_self = queries is None
+    if exclude_self and queries is not None:
+        raise ValueError('exclude_self needs queries=None: explicit queries are not rows of Y')
+    k, blocks = int(n_neighbors), int(blocks)
+    n, d = int(Y.shape[0]), int(Y.shape[1])
+    if k < 1:
+        raise ValueError('n_neighbors must be at least 1')
+    if blocks < 0 or (candidate_chunk is not None and int(candidate_chunk) < 1) or (query_block is not None and int(query_block) < 1):
+        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+    kmax = max_neighbors(d) if d >= 1 else 0
+    if kmax == 0:
+        raise ValueError('%d features are not served' % d)
+    if k > kmax:
+        raise ValueError('n_neighbors = %d is beyond the %d served at %d features' % (k, kmax, d))
+    if not Y.is_cuda or (queries is not None and queries.device != Y.device):
+        raise ValueError('Y and queries must be tensors of one device')
+    finite = torch.isfinite(Y).all() if queries is None else torch.isfinite(Y).all() & torch.isfinite(queries).all()
+    finite = finite.to(torch.float64).reshape(1)
+    if odist.sharded(pg):
+        finite = 1.0 - finite
+        odist.all_reduce_sum(finite, pg)
+        finite = 1.0 - finite.clamp(max=1.0)
+    if not bool(finite.item()):
+        raise ValueError('Y or queries have non-finite entries')
+    rows = _Rows(Y, pg)
+    if rows.N > 2 ** 31 - 1:
+        raise ValueError('%d rows are beyond the int32 indices' % rows.N)
+
+    dev = Y.device
+    Q, q0 = (Y, rows.row0) if queries is None else (queries, 0)
+    nq = int(Q.shape[0])
+    # the shards arrive in contiguous buffers of their own; without sharding the candidates are Y as it lies
+    y_ptr, ldy = (16, d) if odist.sharded(pg) else (ptr(Y) if n else None, _rows_ld(Y)[1])
+    qb, chunk, nbytes = knn_plan(nq, max(rows.sizes), d, k, blocks, y_ptr, ldy, candidate_chunk, query_block)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    d2 = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    merge = False
+    y0 = 0
+    for s, ns in enumerate(rows.sizes):
+        if odist.sharded(pg):
+            # shard s on every rank: a zero buffer to which its owner adds its rows, summed over the ranks (exact)
+            cand = torch.zeros(ns, d, dtype=torch.float32, device=dev)
+            if s == rows.rank and ns:
+                cand.copy_(Y)
+            odist.all_reduce_sum(cand, pg)
+        else:
+            cand = Y
+        for a in range(0, ns, chunk):
+            for b in range(0, nq, qb):
+                knn_step(Q[b:b + qb], cand[a:a + chunk], idx[b:b + qb], d2[b:b + qb], q0=q0 + b, y0=y0 + a,
+                         exclude_self=exclude_self, merge=merge, blocks=blocks, scratch=scratch)
+            merge = True
+        y0 += ns
+    if not merge:                                     # (no candidates at all: the padding values)
+        knn_step(Q, Y[:0], idx, d2, q0=q0, blocks=blocks)
+    return {'indices': idx, 'sq_distances': d2}

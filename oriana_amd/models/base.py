@@ -879,23 +879,71 @@ class FactorModel:
             was clustered, NumPy) and 'factors' (the column indices, int64).  Under row sharding the model's process group is used:
             every rank returns the same centres and its own rows' labels.  Nothing of the model's state is written."""
         from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in kmeans_kw:
+            raise ValueError('cluster_cells() uses the process group of the model')
+        F = self._cell_features(features, cols)
+        out = cluster.kmeans(F, n_clusters, pg=self.pg, **kmeans_kw)
+        out['features'] = F.cpu().numpy()
+        out['factors'] = cols
+        return out
+
+    def _cell_feature_columns(self, features, factors):
+        """The validated `features` / `factors` arguments of cluster_cells() and cell_neighbors(): the column indices, int64."""
         if features not in ('log_mean', 'mean_log'):
             raise ValueError("features must be 'log_mean' or 'mean_log'")
         cols = np.arange(self.k, dtype=np.int64) if factors is None else np.asarray(factors)
         if cols.ndim != 1 or cols.size < 1 or cols.dtype.kind not in 'iu' or cols.min() < 0 or cols.max() >= self.k:
             raise ValueError('factors must be a non-empty 1-D array of column indices within [0, %d)' % self.k)
-        cols = cols.astype(np.int64)
-        if 'pg' in kmeans_kw:
-            raise ValueError('cluster_cells() uses the process group of the model')
-        if features == 'log_mean':
+        return cols.astype(np.int64)
+
+    def _cell_features(self, features, cols, U=None):
+        """The (n_local, len(cols)) float32 feature matrix of the fitted cells, or with `U` ((n_q, K) float64 device tensor of
+        E[U] rows of other cells, 'log_mean' only) of those."""
+        if U is not None:
+            F = torch.log(U).to(torch.float32)
+        elif features == 'log_mean':
             F = torch.log(self.U.buffer).to(torch.float32)          # (the accessor factors() reads: a lazy U_hat is evaluated)
         else:
             F = self._log_U_hat
-        F = F.index_select(1, torch.as_tensor(cols, device=self.device)).contiguous()
-        out = cluster.kmeans(F, n_clusters, pg=self.pg, **kmeans_kw)
-        out['features'] = F.cpu().numpy()
-        out['factors'] = cols
-        return out
+        return F.index_select(1, torch.as_tensor(cols, device=self.device)).contiguous()
+
+    def cell_neighbors(self, n_neighbors=15, features='log_mean', factors=None, queries=None, **knn_kw):
+        """The exact k-nearest-neighbour graph of the cells on the feature matrix cluster_cells() uses, on the device (cluster.knn;
+        its keywords candidate_chunk and blocks pass through).
+
+        Without `queries` every fitted cell gets its n_neighbors nearest OTHER cells (a cell is never its own neighbour; an
+        identical cell is, at distance 0).  queries : an (n_q, K) array or tensor of E[U] rows of other cells -- what
+        transform() / fold_in() / project() return; they go through the same float64 logarithm, float32 cast and column
+        selection and are searched against the fitted cells, nothing excluded; defined for features='log_mean' only.
+        Returns NumPy arrays: 'indices' (n_q, n_neighbors) int32 global cell indices and 'sq_distances' float32, each row ordered
+        by (distance, index) and padded with -1 / inf where fewer cells exist; 'features' (the (n_local, d) float32 matrix that
+        was searched) and 'factors' as cluster_cells() returns them.  Under row sharding the model's process group is used: every
+        rank returns the rows of its own cells (or of its own queries), the candidates are all ranks' cells.  Nothing of the
+        model's state is written."""
+        from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in knn_kw:
+            raise ValueError('cell_neighbors() uses the process group of the model')
+        if 'exclude_self' in knn_kw:
+            raise ValueError('cell_neighbors() excludes a cell from its own list exactly when queries is None')
+        if int(n_neighbors) < 1:
+            raise ValueError('n_neighbors must be at least 1')
+        Qf = None
+        if queries is not None:
+            if features != 'log_mean':
+                raise ValueError("queries are rows of E[U]: they are defined for features='log_mean' only")
+            q = queries.detach().cpu().numpy() if isinstance(queries, torch.Tensor) else queries
+            q = np.asarray(q, dtype=np.float64)
+            if q.ndim != 2 or q.shape[1] != self.k:
+                raise ValueError('queries must be (n_q, %d), got %s' % (self.k, q.shape))
+            if not (np.isfinite(q).all() and (q > 0).all()):
+                raise ValueError('queries must be finite and positive')
+            Qf = self._cell_features(features, cols, U=torch.as_tensor(q).to(self.device))
+        F = self._cell_features(features, cols)
+        out = cluster.knn(F, n_neighbors, queries=Qf, pg=self.pg, **knn_kw)
+        return {'indices': out['indices'].cpu().numpy(), 'sq_distances': out['sq_distances'].cpu().numpy(),
+                'features': F.cpu().numpy(), 'factors': cols}
 
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
     _PARAMS =('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
