@@ -987,6 +987,44 @@ int64_t oriana_knn_waves(int64_t d, int64_t k);
  * negative: the argument error. */
 int64_t oriana_knn_splits(int64_t nq, int64_t n, int64_t d, int64_t k, int64_t blocks);
 
+/* ---- per-cluster sums of distances: the silhouette of a clustering of the cells (csrc/silhouette.hip) --------
+ * For every query row of Q (nq, d) float32, row stride ldq >= d, and every cluster c: the sum of the Euclidean distances to the
+ * candidate rows of cluster c.  The candidates Y (n, d) float32, row stride ldy >= d, lie GROUPED BY CLUSTER: cluster c owns
+ * the rows [offsets[c], offsets[c + 1]).  No distance matrix exists.
+ *   the pair   f(q, c) of oriana_knn: sum_j (q_j - c_j)^2 in float32 as one sequential fmaf chain over j ascending that starts
+ *              from 0, every difference rounded once, zero padding exact; f of a row with itself or with a bit-identical row
+ *              is exactly 0.  The distance is sqrtf(f), the correctly rounded float32 square root (the library is built
+ *              without any fast-math flag).
+ *   the sum    every distance is converted to float64 and added in float64; no float32 partial sum exists.  No atomics: every
+ *              sum has one writer.  Inside a launch the order of addition is fixed by the plan (a function of the sizes, the
+ *              offsets and `blocks`), so the same call twice gives the same bits.  Bits are NOT promised across different
+ *              partitions of the work (`blocks`, candidates in several accumulating calls, queries in several calls); the
+ *              terms are the same bit for bit, so two partitions differ by the float64 summation order only.
+ *   the output sums[c * lds + q], device, float64, cluster-major, lds >= nq.  accumulate = 0 overwrites all C x nq entries (a
+ *              cluster without rows becomes 0), accumulate = 1 adds the call's sums to what is there.  Entries of a row of
+ *              `sums` beyond nq are never touched.
+ * offsets: HOST memory, C + 1 ascending entries, offsets[0] = 0, offsets[C] = n; it may be freed when the call returns (the
+ * call waits for the stream once, after the copy of its small work table and before its launches).
+ * `blocks`: ranges the candidates as a whole are cut into (0: sized from the device, two work-groups per CU); a cluster is cut
+ * where it exceeds one range, at most 32,767 ranges.
+ * scratch: oriana_cluster_distance_sums_scratch_bytes_for(..) bytes, 16-byte aligned, contents undefined on entry and exit.
+ * All arguments are validated before any HIP call: a negative size or `blocks`, d < 1, ldq < d, ldy < d, lds < nq, nq beyond
+ * 2^31 - 1, n beyond 2^31 - 9 (the step counter is 32-bit) -> ORIANA_EINVAL; d > 256 or C beyond
+ * oriana_cluster_distance_sums_max_clusters() -> ORIANA_EKRANGE; a NULL offsets or scratch, a NULL sums with nq, C > 0, Q with
+ * nq > 0 or Y with n > 0, a scratch that is not 16-byte aligned, offsets that do not start at 0, descend or do not end at n ->
+ * ORIANA_EINVAL.  nq = 0 or C = 0 is a no-op. */
+int oriana_cluster_distance_sums(const float *Q, int64_t nq, int64_t ldq, const float *Y, int64_t n, int64_t ldy, int64_t d,
+                                 const int64_t *offsets, int64_t C, double *sums, int64_t lds, int accumulate, void *scratch,
+                                 int64_t blocks, void *stream);
+/* Bytes of scratch of a call with this Y and ldy, an upper bound for every valid offsets (negative: the argument error the call
+ * would return): a padded image of the candidates (n pad4(d) floats; none where Y itself serves: d and ldy multiples of four, Y
+ * 16-byte aligned; Y is not dereferenced), the work table, and 512 bytes per query tile and work item (at most min(C, n) +
+ * ranges items). */
+int64_t oriana_cluster_distance_sums_scratch_bytes_for(int64_t nq, int64_t n, int64_t d, int64_t C, int64_t blocks, const float *Y,
+                                                       int64_t ldy);
+/* The largest C served (32,768: the work items of a call are one extent of its grid). */
+int64_t oriana_cluster_distance_sums_max_clusters(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,9 @@ _SIGS = {
     'oriana_knn_tile_rows': (_I, []),
     'oriana_knn_waves': (_I, [_I, _I]),
     'oriana_knn_splits': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_cluster_distance_sums': (c_int, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, c_int, _P, _I, _P]),
+    'oriana_cluster_distance_sums_scratch_bytes_for': (_I, [_I, _I, _I, _I, _I, _P, _I]),
+    'oriana_cluster_distance_sums_max_clusters': (_I, []),
 }
 
 _lib = None

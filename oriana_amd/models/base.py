@@ -945,6 +945,27 @@ class FactorModel:
         return {'indices': out['indices'].cpu().numpy(), 'sq_distances': out['sq_distances'].cpu().numpy(),
                 'features': F.cpu().numpy(), 'factors': cols}
 
+    def cell_silhouette(self, labels, features='log_mean', factors=None, **silhouette_kw):
+        """The exact silhouette of a labelling of the cells (for example ``cluster_cells(C)['labels']``) on the feature matrix
+        cluster_cells() clusters, on the device (cluster.silhouette; its keywords n_clusters, candidate_chunk, query_block and
+        blocks pass through): the number that compares clusterings across n_clusters and across `factors`.
+
+        labels : an integer array or tensor, one id >= 0 per local cell.  Returns 'values', 'a', 'b' ((n_local,) float64 NumPy),
+        'mean' (float, over all cells), 'cluster_means' ((C,) float64, NaN for an id without cells), 'counts' ((C,) int64, global),
+        'features' (the (n_local, d) float32 matrix that was measured) and 'factors' as cluster_cells() returns them.  Under
+        row sharding the model's process group is used.  Nothing of the model's state is written."""
+        from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in silhouette_kw:
+            raise ValueError('cell_silhouette() uses the process group of the model')
+        F = self._cell_features(features, cols)
+        out = cluster.silhouette(F, labels, pg=self.pg, **silhouette_kw)
+        for k in ('values', 'a', 'b'):
+            out[k] = out[k].cpu().numpy()
+        out['features'] = F.cpu().numpy()
+        out['factors'] = cols
+        return out
+
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
     _PARAMS =('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
 
