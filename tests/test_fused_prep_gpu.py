@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import gamma_update_reference as gr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -81,9 +83,22 @@ def test_update_with_prep_outputs_matches_separate_preparation(eng, r, K, form):
     a1_ref = torch.clamp(torch.nan_to_num(p1 + Z.double(), nan=0.0), min=1e-15)
     ok = torch.isfinite(a1_ref)
     assert torch.allclose(outs['prep']['a1'][ok], a1_ref[ok], rtol=1e-6 if form == 'finalize' else 0, atol=0)
-    el_ref = (torch.digamma(a1_ref.float().double()).float() - torch.log((p2 + rate).float())[None, :])
-    fin = torch.isfinite(el_ref) & torch.isfinite(El)
-    assert float((El[fin] - el_ref[fin]).abs().max()) <= 2e-6 * float(el_ref[fin].abs().max())
+    # ... and against the float64 statement of tests/gamma_update_reference.py: a1, a2 bit for bit, E within an ulp, E[log .]
+    # inside its bound ELEMENT BY ELEMENT (the clamped entry has psi = -1e15: a bound scaled by the largest |E[log .]| of the
+    # matrix would let every other entry be anything), the column sums within the float64 summation error
+    if form == 'plain':
+        ref = gr.gamma_update_ref(prior1=p1.cpu().numpy(), prior2=p2.cpu().numpy(), Z=Z.cpu().numpy(), rate_vec=rate.cpu().numpy())
+    else:
+        ref = gr.gamma_update_ref(prior1=p1.cpu().numpy(), prior2=p2.cpu().numpy(), Z=np.zeros((r, K), np.float32),
+                                  rate_vec=rate.cpu().numpy(), F=F.cpu().numpy(), R=R.cpu().numpy(), nslab=2, slab_row0=r // 2)
+    got = {k: outs['prep'][k].cpu().numpy() for k in ('a1', 'a2', 'E', 'El', 'sums')}
+    assert np.array_equal(got['a1'], ref['a1']) and np.array_equal(got['a2'], ref['a2'])
+    assert np.isfinite(ref['E']).all() and (np.abs(got['E'] - ref['E']) <= np.spacing(ref['E'])).all()
+    ratio = gr.elog_ratio(got['El'], ref)
+    assert float(ratio.max()) <= 1.0, np.unravel_index(int(ratio.argmax()), ratio.shape)
+    for i, x in enumerate((ref['E'], got['El'].astype(np.float64))):
+        want, tol = gr.colsum_total(np.zeros(K), x), gr.colsum_tol(np.zeros(K), x)
+        assert (np.abs(got['sums'][i] - want) <= tol).all(), ('sum E', 'sum Elog')[i]
     # the separate preparation over the same E[log U]
     m = 64
     lv = torch.randn(m, K, device=dev, generator=g)
