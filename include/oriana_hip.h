@@ -1025,6 +1025,29 @@ int64_t oriana_cluster_distance_sums_scratch_bytes_for(int64_t nq, int64_t n, in
 /* The largest C served (32,768: the work items of a call are one extent of its grid). */
 int64_t oriana_cluster_distance_sums_max_clusters(void);
 
+/* ---- per-cell totals and per-cluster gene moments of the counts (oriana_amd/models/base.py: cell_totals,
+ * cluster_gene_stats, marker_genes; no counterpart in the reference) --------------------------------------------------------
+ * Sums over the NON-ZERO counts of both layouts of a model's matrix: cm is the sliced layout (of a hybrid matrix: its packed
+ * genes [gd, m), as every entry above takes it), dn the dense block of a hybrid layout or NULL, row_perm / col_perm the FULL
+ * orderings the dense block is read through (NULL = identity; the sliced layout carries its own).  Counts are read as stored
+ * (float32 records, uint16 block); every sum is float64 and ADDS into its output with float64 atomics (the caller zeroes it;
+ * reruns agree to the order of the additions -- exactly, while every partial sum is an integer below 2^53).
+ *   oriana_cell_totals : totals[i] += sum_j x_ij, (n,) in the caller's row order.
+ *   oriana_group_stats : labels (n,) int32 in the caller's row order, each in [0, C) (a label outside is never counted and never
+ *                        addresses memory); scale (n,) float64 in the caller's row order or NULL.  Per non-zero count x of cell
+ *                        i and gene j: y = x (scale == NULL) or (double)x * scale[i]; with log1p_flag y = log1p(y) in float64;
+ *                        out[0, c, j] += 1, out[1, c, j] += y, out[2, c, j] += y * y with c = labels[i].  out: (3, C, m_all)
+ *                        float64, caller's gene order, m_all = cm->m + (dn ? dn->gd : 0).
+ *   oriana_group_stats_max_groups : the largest C (1024).
+ * ORIANA_EINVAL for a NULL cm / labels / out / totals, a negative size, a dense block whose gd is no multiple of 32 or whose
+ * cells are not cm's, or C < 1; ORIANA_EKRANGE for C above the limit; both before any HIP call.  0 without a launch for a
+ * layout without a stored count. */
+int oriana_cell_totals(const oriana_counts *cm, const oriana_dense *dn, const int32_t *row_perm, const int32_t *col_perm,
+                       double *totals, void *stream);
+int oriana_group_stats(const oriana_counts *cm, const oriana_dense *dn, const int32_t *row_perm, const int32_t *col_perm,
+                       const int32_t *labels, const double *scale, int log1p_flag, int64_t C, double *out, void *stream);
+int64_t oriana_group_stats_max_groups(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,9 @@ _SIGS = {
     'oriana_cluster_distance_sums': (c_int, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, c_int, _P, _I, _P]),
     'oriana_cluster_distance_sums_scratch_bytes_for': (_I, [_I, _I, _I, _I, _I, _P, _I]),
     'oriana_cluster_distance_sums_max_clusters': (_I, []),
+    'oriana_cell_totals': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P]),
+    'oriana_group_stats': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P, c_int, _I, _P, _P]),
+    'oriana_group_stats_max_groups': (_I, []),
 }
 
 _lib = None

@@ -966,6 +966,91 @@ class FactorModel:
         out['factors'] = cols
         return out
 
+    # ---- which genes distinguish a cluster (scanpy's rank_genes_groups(method='t-test') on the counts the model holds) --------
+    # Per cluster and gene the test needs the mean, the variance and the expressing fraction of the log-normalised counts
+    # y_ij = log1p(x_ij target_sum / total_i).  y = 0 wherever x = 0, so the moments are sums over the non-zero counts only:
+    # one walk over the sliced layout and the dense block (csrc/groupstats.hip) with the labels as a cluster axis, never a dense
+    # n x m matrix; the statistic itself is assembled on the host from (C, m) arrays (markers.py).
+    def _cell_totals_device(self):
+        """sum_j x_ij of this rank's cells: an (n_local,) float64 device tensor in the caller's row order, cached like
+        _count_constants() (X is constant)."""
+        if getattr(self, '_xtotals', None) is None:
+            ct = self.counts
+            tot = torch.zeros(max(self.n, 1), dtype=torch.float64, device=self.device)
+            call('oriana_cell_totals', ct.sparse_struct, ct.dense.c_struct if ct.dense is not None else None, ptr(ct.row_perm),
+                 ptr(ct.col_perm), ptr(tot), stream_ptr())
+            self._xtotals = tot[:self.n]
+        return self._xtotals
+
+    def cell_totals(self):
+        """The total count of every local cell (the library size): an (n_local,) float64 NumPy array in the caller's row order,
+        exact for integer counts.  Computed once on the device from the layouts the model holds, then cached."""
+        return self._cell_totals_device().cpu().numpy()
+
+    def cluster_gene_stats(self, labels, n_clusters=None, normalize=True, target_sum=1e4, log1p=True):
+        """Per cluster and gene the moments of the (log-normalised) counts, on the device.
+
+        labels : an integer array or tensor, one id >= 0 per local cell (for example ``cluster_cells(C)['labels']``).
+        n_clusters : C (default: the largest id + 1 over all ranks).  normalize : scale every cell to `target_sum` counts
+        (scale_i = target_sum / total_i, 0 for a cell without counts); log1p : take log1p of the scaled count -- the defaults are
+        scanpy's ``normalize_total(target_sum=1e4)`` + ``log1p``.  Returns (C, m) float64 NumPy arrays in the caller's gene order:
+        'n_expressing' (cells of the cluster with a non-zero count), 'sum' and 'sumsq' of the values over them (= over all cells of
+        the cluster: a zero count gives 0), and 'sizes' (C,) int64, the cells per cluster.  Under row sharding everything is summed
+        over the ranks in one packed all-reduce and every rank returns the same arrays.  ValueError before any launch for labels
+        that are not n_local non-negative integers below n_clusters, target_sum <= 0 or more clusters than
+        oriana_group_stats_max_groups().  Nothing of the model's state is written."""
+        from .. import cluster, _lib
+        n, m, dev, ct = self.n, self.m, self.device, self.counts
+        lab = cluster._label_tensor(labels, n, 'labels')
+        if not float(target_sum) > 0.0:
+            raise ValueError('target_sum must be positive')
+        top = int(lab.max()) + 1 if lab.numel() else 0
+        if n_clusters is None:
+            C = cluster._global_max(top, dev, self.pg)
+        else:
+            C = int(n_clusters)
+            if top > C:
+                raise ValueError('labels must lie within [0, n_clusters = %d), found %d' % (C, top - 1))
+        limit = int(_lib.load().oriana_group_stats_max_groups())
+        if C < 1 or C > limit:
+            raise ValueError('the number of clusters must lie within 1..%d, got %d' % (limit, C))
+        lab = lab.to(dev)
+        scale = None
+        if normalize:
+            tot = self._cell_totals_device()
+            scale = torch.where(tot > 0, float(target_sum) / tot, torch.zeros_like(tot)).contiguous()
+        lab32 = lab.to(torch.int32).contiguous()
+        packed = torch.zeros(3 * C * m + C, dtype=torch.float64, device=dev)
+        if n > 0:
+            call('oriana_group_stats', ct.sparse_struct, ct.dense.c_struct if ct.dense is not None else None, ptr(ct.row_perm),
+                 ptr(ct.col_perm), ptr(lab32), ptr(scale), 1 if log1p else 0, C, ptr(packed), stream_ptr())
+        packed[3 * C * m:] = torch.bincount(lab, minlength=C).to(torch.float64)        # (exact: cell counts below 2^53)
+        odist.all_reduce_sum(packed, self.pg)
+        host = packed.cpu().numpy()
+        st = host[:3 * C * m].reshape(3, C, m)
+        return {'n_expressing': st[0], 'sum': st[1], 'sumsq': st[2], 'sizes': np.rint(host[3 * C * m:]).astype(np.int64)}
+
+    def marker_genes(self, labels, n_top=50, **stats_kw):
+        """The genes that distinguish each cluster of a labelling of the cells: Welch's t statistic of every cluster against the
+        rest on the log-normalised counts -- scanpy's ``rank_genes_groups(method='t-test')`` without a host copy of X.
+
+        labels and the keywords n_clusters, normalize, target_sum, log1p: as cluster_gene_stats().  Returns its arrays plus,
+        per cluster and gene ((C, m) float64, caller's gene order; NaN rows for an id without cells): 'scores' (exactly 0 for a
+        gene without variance on both sides), 'df' (Welch-Satterthwaite, NaN where undefined), 'logfoldchanges', 'pct_in',
+        'pct_out' (markers.welch_from_moments), and 'genes', a (C, min(n_top, m)) int64 array: per cluster the gene indices by
+        decreasing score, ties by index (markers.rank).  p-values are not computed: scores and df are what any t distribution
+        takes.  ValueError for fewer than 2 non-empty clusters.  Nothing of the model's state is written."""
+        from .. import markers
+        if int(n_top) < 0:
+            raise ValueError('n_top must not be negative')
+        out = self.cluster_gene_stats(labels, **stats_kw)
+        w = markers.welch_from_moments(out['n_expressing'], out['sum'], out['sumsq'], out['sizes'],
+                                       log1p=bool(stats_kw.get('log1p', True)))
+        for k in ('scores', 'df', 'logfoldchanges', 'pct_in', 'pct_out'):
+            out[k] = w[k]
+        out['genes'] = markers.rank(w['scores'], n_top)
+        return out
+
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
     _PARAMS =('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
 
