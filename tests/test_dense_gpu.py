@@ -66,7 +66,7 @@ def test_hybrid_pack_roundtrip(eng, n, m, dtype):
 
 @pytest.mark.parametrize('n,m,K', [(257, 131, 100), (300, 200, 96), (512, 64, 100), (100, 70, 20), (90, 40, 5),
                                    (600, 260, 50), (257, 300, 64), (130, 96, 37), (33, 64, 84), (700, 150, 68),
-                                   (64, 64, 16), (257, 131, 72)])
+                                   (64, 64, 16), (257, 131, 72), (130, 96, 29), (257, 131, 33)])
 def test_zq_gap_hybrid_vs_oracle(eng, n, m, K):
     rng = np.random.default_rng(n + 31 * m + 977 * K)
     dens = np.clip(rng.beta(1.0, 2.0, size=m), 0.01, 1.0)
