@@ -1048,6 +1048,54 @@ int oriana_group_stats(const oriana_counts *cm, const oriana_dense *dn, const in
                        const int32_t *labels, const double *scale, int log1p_flag, int64_t C, double *out, void *stream);
 int64_t oriana_group_stats_max_groups(void);
 
+/* ---- the exact t-SNE layout of the cells (csrc/tsne.hip, oriana_amd/cluster.py: tsne) --------------------------
+ * oriana_tsne_affinities : conditional neighbour probabilities at a perplexity.  sq_distances (n, k) float32 contiguous, what
+ *   oriana_knn wrote: every row ascending and padded with +inf.  Per row, over its m finite entries, p_j = exp(-beta (d_j - d_0))
+ *   / sum with the beta at which the entropy H = -sum p log p equals log(perplexity), all in float64.  The search is
+ *   deterministic: from beta = 1 the value is doubled (halved) while no upper (lower) bracket exists, then bisected; it stops at
+ *   |H - log perplexity| <= 1e-9 or after oriana_tsne_affinity_steps() = 200 evaluations of H.  p (n, k) float32 (exactly 0 at
+ *   the padded slots) and beta (n) float64 are written.  A row whose finite entries are all equal gets the uniform distribution
+ *   and a finite beta; a row without finite entries p = 0 and beta = 1.  Whether a row holds enough finite entries for the
+ *   perplexity is the caller's check.  n < 0, k < 1, a perplexity that is not in [1, inf), a NULL pointer with n > 0 ->
+ *   ORIANA_EINVAL; n = 0 is a no-op.
+ * oriana_tsne_attract : P (n, n) as CSR (row_ptr (n + 1) int64, cols int32 within [0, n) -- an entry outside is skipped and
+ *   addresses nothing --, vals float32), Y (n, 2) float32 contiguous, 8-byte aligned.  In float64, with D = 1 + |y_i - y_j|^2:
+ *   attr[i] = sum_j P_ij (y_i - y_j) / D, (n, 2); klrow[i] = sum_j P_ij (log P_ij + log D) over the entries with P_ij > 0.  One
+ *   wave per row: lane l takes the row's entries l, l + 64, .. in order and the 64 partial sums are added in one fixed shape, so
+ *   a row's bits depend on the row alone.  n < 0 or beyond 2^31 - 1, a NULL row_ptr / Y / attr / klrow with n > 0, a misaligned
+ *   Y -> ORIANA_EINVAL; n = 0 is a no-op.
+ * oriana_tsne_repulse : queries Q (nq, 2) and candidates Y (n, 2), float32 contiguous, 8-byte aligned.  rep[i] = sum_j w_ij^2
+ *   (q_i - y_j), (nq, 2) float64, and zrow[i] = sum_j w_ij, (nq) float64, over ALL candidates (nothing is excluded).
+ *   the pair   one float32 sequence: dx = qx - yx and dy = qy - yy, each rounded once; s = fmaf(dy, dy, fmaf(dx, dx, 1));
+ *              w = the hardware reciprocal of s (v_rcp_f32, 1 ulp); w2 = w * w; the terms w, w2 * dx, w2 * dy, the last two
+ *              entering their sums by fmaf (the products are not rounded on their own).  A pair of bit-identical points
+ *              gives w = 1 exactly and force terms of exactly 0.
+ *   the sum    every w is converted to float64 and added in float64 (Z loses nothing to the n exact self pairs the caller
+ *              subtracts).  The candidates are taken in steps of 8; the force terms of one step are added in float32 in
+ *              candidate order starting from 0, each step's two sums are converted to float64 and everything beyond is added in
+ *              float64.  No atomics:
+ *              every sum has one writer.  Inside a launch the order is fixed by the plan (a function of nq, n and `blocks`), so
+ *              the same call twice gives the same bits.  Bits are NOT promised across different partitions of the candidates:
+ *              `blocks` cuts at whole steps, so the step sums are the same bit for bit and only the float64 summation order
+ *              differs; so it is for accumulating calls whose candidate chunks are multiples of 8, while other chunk sizes
+ *              move candidates between steps (the float32 order inside a step differs too).  A partition of the QUERIES
+ *              changes nothing.
+ *   accumulate = 0 overwrites rep and zrow of the nq queries (n = 0: zeros), 1 adds the call's sums to what is there.
+ *   `blocks`: ranges the candidates are cut into (0: sized from the device, two work-groups per CU; at most 32,767 and at most
+ *   one per step).  scratch: oriana_tsne_repulse_scratch_bytes_for(nq, n, blocks) bytes (1,536 per query tile and range), 16-byte
+ *   aligned, contents undefined on entry and exit.
+ *   A negative size or `blocks`, nq beyond 2^31 - 1, n beyond 2^31 - 9 (the step counter is 32-bit), a NULL scratch, a NULL Q /
+ *   rep / zrow with nq > 0, a NULL Y with n > 0, a misaligned scratch, Q or Y -> ORIANA_EINVAL, all before any HIP call.  nq = 0
+ *   is a no-op. */
+int oriana_tsne_affinities(const float *sq_distances, int64_t n, int64_t k, double perplexity, float *p, double *beta, void *stream);
+int64_t oriana_tsne_affinity_steps(void);
+int oriana_tsne_attract(const int64_t *row_ptr, const int32_t *cols, const float *vals, const float *Y, int64_t n, double *attr,
+                        double *klrow, void *stream);
+int oriana_tsne_repulse(const float *Q, int64_t nq, const float *Y, int64_t n, double *rep, double *zrow, int accumulate,
+                        void *scratch, int64_t blocks, void *stream);
+/* Bytes of scratch of such a call (negative: the argument error the call would return). */
+int64_t oriana_tsne_repulse_scratch_bytes_for(int64_t nq, int64_t n, int64_t blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,12 @@ matrix, results independent of every partition of the work.  DESIGN.md section 5
 
 silhouette() is the exact silhouette of a labelling of the same rows through oriana_cluster_distance_sums (csrc/silhouette.hip):
 all Euclidean distances of all pairs, added per cluster in float64, no distance matrix; adjusted_rand() is the exact adjusted
-Rand index of two labellings.  DESIGN.md section 5k."""
+Rand index of two labellings.  DESIGN.md section 5k.
+
+tsne() is the exact t-SNE layout of the same rows (csrc/tsne.hip): the neighbour graph of knn(), perplexity-calibrated affinities,
+and a gradient whose repulsive term is all n^2 pairs by brute force -- no tree, no sampling, deterministic.  DESIGN.md section 5m."""
+import math
+
 import numpy as np
 import torch
 
@@ -19,7 +24,9 @@ from . import dist as odist
 
 __all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows', 'tile_rows', 'draws', 'distinct_rows',
            'knn', 'knn_plan', 'knn_step', 'max_neighbors',
-           'silhouette', 'silhouette_plan', 'silhouette_from_sums', 'distance_sums', 'max_clusters', 'adjusted_rand']
+           'silhouette', 'silhouette_plan', 'silhouette_from_sums', 'distance_sums', 'max_clusters', 'adjusted_rand',
+           'tsne', 'tsne_plan', 'tsne_default_neighbors', 'tsne_affinities', 'tsne_joint', 'tsne_attract', 'tsne_repulse',
+           'tsne_gradient', 'tsne_pca_init']
 
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
@@ -761,3 +768,301 @@ def adjusted_rand(labels_a, labels_b, pg=None):
     if fn == 0 and fp == 0:
         return 1.0
     return 2 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+
+
+# ---- the exact t-SNE layout (csrc/tsne.hip) --------------------------------------------------------------------
+def tsne_default_neighbors(perplexity, d, n, kmax=None):
+    """n_neighbors where tsne() is given none: min(ceil(3 perplexity), max_neighbors(d), n - 1).  `kmax` replaces the
+    max_neighbors(d) of the library (then no library is needed)."""
+    kmax = max_neighbors(d) if kmax is None else int(kmax)
+    return min(int(math.ceil(3.0 * float(perplexity))), kmax, int(n) - 1)
+
+
+def _check_layout(T, what):
+    if not isinstance(T, torch.Tensor) or T.dim() != 2 or int(T.shape[1]) != 2:
+        raise ValueError('%s must be an (n, 2) torch tensor' % what)
+    if T.dtype != torch.float32:
+        raise ValueError('%s must be float32, got %s' % (what, T.dtype))
+    if not T.is_contiguous():
+        raise ValueError('%s must be C-contiguous' % what)
+
+
+def tsne_affinities(sq_distances, perplexity):
+    """One oriana_tsne_affinities call: `sq_distances` (n, k) float32 contiguous device tensor as knn() returns it (rows ascending,
+    padded with +inf).  Returns (p, beta): p (n, k) float32 with p[i, j] = p_{j|i} over the finite entries of row i at the beta[i]
+    (float64) whose entropy is log(perplexity); exactly 0 at the padded slots.  ValueError for a perplexity below 1 and (one host
+    read) for a row with fewer than ceil(perplexity) + 1 finite entries."""
+    D = sq_distances
+    if not isinstance(D, torch.Tensor) or D.dim() != 2 or D.dtype != torch.float32 or not D.is_contiguous() or int(D.shape[1]) < 1:
+        raise ValueError('sq_distances must be a contiguous (n, k >= 1) float32 tensor')
+    perplexity = float(perplexity)
+    if not (1.0 <= perplexity < float('inf')):
+        raise ValueError('perplexity must be a finite number >= 1')
+    n, k = int(D.shape[0]), int(D.shape[1])
+    need = int(math.ceil(perplexity)) + 1
+    if n and int((D < float('inf')).sum(1).min()) < need:
+        raise ValueError('a row has fewer than ceil(perplexity) + 1 = %d finite distances' % need)
+    p = torch.empty(n, k, dtype=torch.float32, device=D.device)
+    beta = torch.empty(n, dtype=torch.float64, device=D.device)
+    call('oriana_tsne_affinities', ptr(D) if n else None, n, k, perplexity, ptr(p) if n else None, ptr(beta) if n else None,
+         stream_ptr())
+    return p, beta
+
+
+def tsne_joint(indices, p):
+    """The joint P = (p_{j|i} + p_{i|j}) / (2 n) of the conditional probabilities p (n, k) over the neighbours `indices` (n, k)
+    int32, as CSR on the device: both directions as one COO matrix, coalesced by torch.  Padded slots (index -1) and exact zeros
+    are dropped; the two directions are added in float64 (two terms: no order), the values are stored as float32, the columns
+    ascend inside a row.  Returns {'crow': (n + 1) int64, 'col': (nnz) int32, 'val': (nnz) float32, 'n': n,
+    'sum': the float64 sum of the stored values (a device scalar)}."""
+    if not isinstance(indices, torch.Tensor) or not isinstance(p, torch.Tensor) or indices.dim() != 2 or indices.shape != p.shape:
+        raise ValueError('indices and p must be (n, k) tensors of one shape')
+    if indices.dtype not in (torch.int32, torch.int64) or p.dtype != torch.float32:
+        raise ValueError('indices must be int32 or int64 and p float32')
+    n, k = int(indices.shape[0]), int(indices.shape[1])
+    dev = p.device
+    idx = indices.to(torch.int64)
+    keep = (idx >= 0) & (idx < n) & (p > 0)
+    r = torch.arange(n, device=dev, dtype=torch.int64)[:, None].expand(n, k)[keep]
+    c = idx[keep]
+    v = p[keep].to(torch.float64)
+    coo = torch.sparse_coo_tensor(torch.stack([torch.cat([r, c]), torch.cat([c, r])]), torch.cat([v, v]), (n, n)).coalesce()
+    ij = coo.indices()
+    val = (coo.values() / (2.0 * n)).to(torch.float32) if n else coo.values().to(torch.float32)
+    crow = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        crow[1:] = torch.cumsum(torch.bincount(ij[0], minlength=n), 0)
+    return {'crow': crow, 'col': ij[1].to(torch.int32).contiguous(), 'val': val.contiguous(), 'n': n,
+            'sum': val.sum(dtype=torch.float64)}
+
+
+def _check_joint(P, n):
+    if not isinstance(P, dict) or int(P['n']) != n:
+        raise ValueError('P must be what tsne_joint() returned for these %d rows' % n)
+    crow, col, val = P['crow'], P['col'], P['val']
+    if crow.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float32 or int(crow.numel()) != n + 1 \
+            or col.numel() != val.numel() or not (crow.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+        raise ValueError('P must hold int64 row pointers (n + 1), int32 columns and float32 values, contiguous')
+
+
+def tsne_attract(P, Y):
+    """One oriana_tsne_attract call: P as tsne_joint() returns it, Y (n, 2) float32 contiguous.  Returns (attr, klrow), float64:
+    attr[i] = sum_j P_ij (y_i - y_j) / (1 + |y_i - y_j|^2), klrow[i] = sum_j P_ij (log P_ij + log(1 + |y_i - y_j|^2))."""
+    _check_layout(Y, 'Y')
+    n = int(Y.shape[0])
+    _check_joint(P, n)
+    attr = torch.empty(n, 2, dtype=torch.float64, device=Y.device)
+    klrow = torch.empty(n, dtype=torch.float64, device=Y.device)
+    nnz = int(P['col'].numel())
+    call('oriana_tsne_attract', ptr(P['crow']), ptr(P['col']) if nnz else None, ptr(P['val']) if nnz else None,
+         ptr(Y) if n else None, n, ptr(attr) if n else None, ptr(klrow) if n else None, stream_ptr())
+    return attr, klrow
+
+
+def _repulse_scratch_bytes(nq, n, blocks):
+    nbytes = int(_lib.load().oriana_tsne_repulse_scratch_bytes_for(int(nq), int(n), int(blocks)))
+    if nbytes < 0:
+        raise _lib.OrianaHipError('oriana_tsne_repulse_scratch_bytes_for failed with code %d' % nbytes)
+    return nbytes
+
+
+def tsne_repulse(Q, Y, rep=None, zrow=None, accumulate=False, blocks=0, scratch=None):
+    """One oriana_tsne_repulse call: for the queries Q (nq, 2) against ALL candidates Y (n, 2), float32 contiguous device tensors,
+    rep[i] = sum_j w_ij^2 (q_i - y_j) ((nq, 2) float64) and zrow[i] = sum_j w_ij ((nq,) float64), w = 1 / (1 + |q_i - y_j|^2).
+    rep / zrow : contiguous float64 tensors to write (default: new ones) or, with `accumulate`, to add to.  Returns (rep, zrow)."""
+    _check_layout(Q, 'Q')
+    _check_layout(Y, 'Y')
+    nq, n = int(Q.shape[0]), int(Y.shape[0])
+    if (rep is None or zrow is None) and accumulate:
+        raise ValueError('accumulate needs the sums to add to')
+    if rep is None:
+        rep = torch.empty(nq, 2, dtype=torch.float64, device=Q.device)
+    if zrow is None:
+        zrow = torch.empty(nq, dtype=torch.float64, device=Q.device)
+    if rep.dtype != torch.float64 or tuple(rep.shape) != (nq, 2) or not rep.is_contiguous():
+        raise ValueError('rep must be a contiguous (nq, 2) = %s float64 tensor' % ((nq, 2),))
+    if zrow.dtype != torch.float64 or tuple(zrow.shape) != (nq,) or not zrow.is_contiguous():
+        raise ValueError('zrow must be a contiguous (nq,) = %s float64 tensor' % ((nq,),))
+    nbytes = _repulse_scratch_bytes(nq, n, blocks)
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=Q.device)
+    elif scratch.numel() * scratch.element_size() < nbytes:            # (the entry takes no size: it would write past it)
+        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    call('oriana_tsne_repulse', ptr(Q) if nq else None, nq, ptr(Y) if n else None, n, ptr(rep) if nq else None,
+         ptr(zrow) if nq else None, 1 if accumulate else 0, ptr(scratch), int(blocks), stream_ptr())
+    return rep, zrow
+
+
+def tsne_plan(n, blocks=0, query_block=None, candidate_chunk=None, budget=None):
+    """How tsne_gradient() cuts the n x n repulsive pass into tsne_repulse() calls: (query_block, candidate_chunk, scratch bytes
+    that serve every call issued).  What is not given: all candidates in one call (a chunk costs nothing but launches), and the
+    queries halved in whole tiles until the scratch (1,536 bytes per query tile and candidate range) stays within `budget`
+    (default SCRATCH_BUDGET)."""
+    n = int(n)
+    budget = SCRATCH_BUDGET if budget is None else int(budget)
+    tile = 64
+    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
+    qb = int(query_block) if query_block is not None else max(n, 1)
+    if chunk < 1 or qb < 1 or int(blocks) < 0:
+        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+
+    def need(q, c):
+        qs = {min(q, n)} | ({n % q} if n > q else set())
+        cs = {min(c, n)} | ({n % c} if n > c else set())
+        return max(_repulse_scratch_bytes(a, b, blocks) for a in qs for b in cs)
+
+    if query_block is None:
+        while qb > tile and need(qb, chunk) > budget:
+            qb = max(tile, -(-qb // (2 * tile)) * tile)
+    return qb, chunk, need(qb, chunk)
+
+
+def tsne_gradient(P, Y32, exaggeration=1.0, query_block=None, candidate_chunk=None, blocks=0):
+    """The gradient of the t-SNE objective at the layout Y32 ((n, 2) float32 contiguous) for the joint P of tsne_joint():
+    grad = 4 (exaggeration attr - rep / Z), (n, 2) float64, with Z = sum zrow - n (the n self pairs, each exactly 1), and
+    kl = sum klrow + log Z sum P, the Kullback-Leibler divergence where exaggeration = 1, as a device scalar.  Everything is
+    enqueued on the current stream; nothing is read on the host.  Returns (grad, kl)."""
+    _check_layout(Y32, 'Y32')
+    n = int(Y32.shape[0])
+    _check_joint(P, n)
+    qb, chunk, nbytes = tsne_plan(n, blocks, query_block, candidate_chunk)
+    dev = Y32.device
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    attr, klrow = tsne_attract(P, Y32)
+    rep = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    zrow = torch.empty(n, dtype=torch.float64, device=dev)
+    for b in range(0, n, qb):
+        for a in range(0, n, chunk):
+            tsne_repulse(Y32[b:b + qb], Y32[a:a + chunk], rep[b:b + qb], zrow[b:b + qb], accumulate=a > 0, blocks=blocks,
+                         scratch=scratch)
+    Z = zrow.sum() - float(n)
+    grad = 4.0 * (float(exaggeration) * attr - rep / Z)
+    kl = klrow.sum() + torch.log(Z) * P['sum']
+    return grad, kl
+
+
+def tsne_pca_init(Y):
+    """The start of init='pca': the rows of Y (n, d) float32 projected on the top two principal axes of the d x d covariance
+    (torch.linalg.eigh in float64), every axis signed so that its largest-magnitude loading is positive, rescaled so that the
+    first coordinate has standard deviation 1e-4 (scikit-learn's rule).  (n, 2) float64 on Y's device."""
+    n, d = int(Y.shape[0]), int(Y.shape[1])
+    mean = Y.sum(0, dtype=torch.float64) / n
+    cov = torch.zeros(d, d, dtype=torch.float64, device=Y.device)
+    for a in range(0, n, 1 << 18):
+        X = Y[a:a + (1 << 18)].to(torch.float64) - mean
+        cov += X.T @ X
+    _, vec = torch.linalg.eigh(cov / max(n - 1, 1))
+    axes = vec[:, -2:].flip(1) if d >= 2 else torch.cat([vec, torch.zeros_like(vec)], 1)      # (eigenvalues ascend)
+    top = axes.gather(0, axes.abs().argmax(0, keepdim=True))[0]
+    axes = axes * torch.where(top < 0, -torch.ones_like(top), torch.ones_like(top))
+    out = torch.empty(n, 2, dtype=torch.float64, device=Y.device)
+    for a in range(0, n, 1 << 18):
+        out[a:a + (1 << 18)] = (Y[a:a + (1 << 18)].to(torch.float64) - mean) @ axes
+    sd = out[:, 0].std(unbiased=False)
+    return out / sd * 1e-4
+
+
+def _tsne_descend(P, y, n_steps, exaggeration, momentum, lr, kw, trace=None, check_every=0, it0=0):
+    """scikit-learn's _gradient_descent on the float64 master copy y (in place): gains + 0.2 where the update and the gradient
+    disagree in sign, x 0.8 elsewhere, floor 0.01; update = momentum update - lr gains grad.  Update and gains start afresh."""
+    update = torch.zeros_like(y)
+    gains = torch.ones_like(y)
+    for it in range(n_steps):
+        grad, kl = tsne_gradient(P, y.to(torch.float32), exaggeration, **kw)
+        inc = update * grad < 0.0
+        gains = torch.where(inc, gains + 0.2, gains * 0.8).clamp_(min=0.01)
+        update = momentum * update - lr * (gains * grad)
+        y += update
+        if trace is not None and (it0 + it + 1) % check_every == 0:
+            trace.append((it0 + it, float(kl)))                                # (the KL at the layout BEFORE this step)
+    return y
+
+
+def tsne(Y, perplexity=20.0, n_neighbors=None, n_iter=750, early_exaggeration=12.0, exaggeration_iter=250, learning_rate='auto',
+         init='pca', seed=0, graph=None, check_every=50, pg=None, **plan_kw):
+    """The exact t-SNE layout in two dimensions of the rows of Y, an (n, d) float32 device tensor (unit column stride).
+
+    The neighbour graph is knn(Y, n_neighbors) (or `graph` = (indices, sq_distances) as knn() / cell_neighbors() returned them,
+    tensors or arrays); n_neighbors defaults to tsne_default_neighbors(); perplexity <= n_neighbors / 2 is required.  The
+    affinities are tsne_affinities() and tsne_joint(); the gradient is tsne_gradient() -- the repulsive term over all n^2 pairs,
+    nothing approximated, nothing random after the start.  The optimiser is scikit-learn's: `exaggeration_iter` iterations with
+    P x early_exaggeration at momentum 0.5, then the rest of `n_iter` at momentum 0.8, gains + 0.2 / x 0.8 with floor 0.01
+    (update and gains start afresh at the switch, as scikit-learn's two calls do), learning_rate 'auto' =
+    max(n / early_exaggeration / 4, 50); elementwise torch on a float64 master copy of the layout whose float32 cast the kernels
+    read.  init : 'pca' (tsne_pca_init), 'random' (N(0, 1e-4^2) from a host generator seeded with `seed`) or an (n, 2) array.
+    plan_kw : query_block, candidate_chunk, blocks of tsne_gradient(), and candidate_chunk / blocks also serve knn().
+
+    The host reads the KL divergence every `check_every` iterations after the exaggeration ends, and nothing else.
+    Returns a dict: 'embedding' (n, 2) float64 device tensor, 'kl' (float, at the final layout's float32 cast, exaggeration 1),
+    'kl_trace' (a list of (iteration, kl)), 'n_iter', 'beta' (n,) float64 device tensor, 'n_neighbors'.
+    ValueError before any launch for a wrong dtype, rank or device, non-finite entries or arguments out of range;
+    NotImplementedError for a process group of more than one rank: row-sharded layouts are not implemented."""
+    if odist.world_size(pg) > 1:
+        raise NotImplementedError('tsne() is not implemented for a process group of more than one rank: gather the rows first')
+    _check_rows(Y, 'Y')
+    n, d = int(Y.shape[0]), int(Y.shape[1])
+    perplexity, n_iter, exaggeration_iter = float(perplexity), int(n_iter), int(exaggeration_iter)
+    early_exaggeration, check_every = float(early_exaggeration), int(check_every)
+    unknown = set(plan_kw) - {'query_block', 'candidate_chunk', 'blocks'}
+    if unknown:
+        raise ValueError('unknown arguments: %s' % ', '.join(sorted(unknown)))
+    if n < 4 or d < 1:
+        raise ValueError('tsne() needs at least 4 rows and one column')
+    if not (1.0 <= perplexity < float('inf')):
+        raise ValueError('perplexity must be a finite number >= 1')
+    if n_iter < 0 or not 0 <= exaggeration_iter <= n_iter or check_every < 1 or not early_exaggeration >= 1.0:
+        raise ValueError('0 <= exaggeration_iter <= n_iter, check_every >= 1 and early_exaggeration >= 1 are required')
+    if learning_rate != 'auto' and not float(learning_rate) > 0.0:
+        raise ValueError("learning_rate must be 'auto' or positive")
+    explicit = None
+    if not isinstance(init, str):
+        explicit = np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+        if explicit.shape != (n, 2) or not np.isfinite(explicit).all():
+            raise ValueError('init must be a finite (n, 2) = %s array' % ((n, 2),))
+    elif init not in ('pca', 'random'):
+        raise ValueError("init must be 'pca', 'random' or an (n, 2) array")
+    if graph is not None:
+        gi, gd = graph
+        k = int(gi.shape[1]) if getattr(gi, 'ndim', 0) == 2 else 0
+        if tuple(gi.shape) != (n, k) or tuple(gd.shape) != (n, k) or k < 1:
+            raise ValueError('graph must be (indices, sq_distances), both (n, k)')
+        if n_neighbors is not None and int(n_neighbors) != k:
+            raise ValueError('n_neighbors = %d, the graph holds %d' % (int(n_neighbors), k))
+    else:
+        kmax = max_neighbors(d)
+        if kmax == 0:
+            raise ValueError('%d features are not served' % d)
+        k = tsne_default_neighbors(perplexity, d, n, kmax) if n_neighbors is None else int(n_neighbors)
+        if k < 1 or k > kmax or k > n - 1:
+            raise ValueError('n_neighbors = %d must lie within 1..min(%d, n - 1 = %d)' % (k, kmax, n - 1))
+    if not perplexity <= k / 2.0:
+        raise ValueError('perplexity = %g needs n_neighbors >= %d, got %d' % (perplexity, int(math.ceil(2 * perplexity)), k))
+    if not Y.is_cuda:
+        raise ValueError('Y must be a device tensor')
+    if not bool(torch.isfinite(Y).all()):
+        raise ValueError('Y has non-finite entries')
+
+    dev = Y.device
+    if graph is None:
+        g = knn(Y, k, **{a: plan_kw[a] for a in ('candidate_chunk', 'blocks') if a in plan_kw})
+        gi, gd = g['indices'], g['sq_distances']
+    else:
+        gi = torch.as_tensor(np.asarray(gi) if not isinstance(gi, torch.Tensor) else gi).to(dev, torch.int32).contiguous()
+        gd = torch.as_tensor(np.asarray(gd) if not isinstance(gd, torch.Tensor) else gd).to(dev, torch.float32).contiguous()
+    p, beta = tsne_affinities(gd, perplexity)
+    P = tsne_joint(gi, p)
+    if explicit is not None:
+        y = torch.as_tensor(explicit).to(dev)
+    elif init == 'pca':
+        y = tsne_pca_init(Y)
+    else:
+        gen = torch.Generator()
+        gen.manual_seed(int(seed))
+        y = (torch.randn(n, 2, dtype=torch.float64, generator=gen) * 1e-4).to(dev)
+    y = y.clone()
+    lr = max(n / early_exaggeration / 4.0, 50.0) if learning_rate == 'auto' else float(learning_rate)
+    trace = []
+    _tsne_descend(P, y, exaggeration_iter, early_exaggeration, 0.5, lr, plan_kw)
+    _tsne_descend(P, y, n_iter - exaggeration_iter, 1.0, 0.8, lr, plan_kw, trace, check_every, exaggeration_iter)
+    _, kl = tsne_gradient(P, y.to(torch.float32), 1.0, **plan_kw)
+    return {'embedding': y, 'kl': float(kl), 'kl_trace': trace, 'n_iter': n_iter, 'beta': beta, 'n_neighbors': k}

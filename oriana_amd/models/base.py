@@ -966,6 +966,31 @@ class FactorModel:
         out['factors'] = cols
         return out
 
+    def cell_layout(self, features='log_mean', factors=None, **tsne_kw):
+        """The exact t-SNE layout of the cells in two dimensions on the feature matrix cluster_cells() uses, on the device
+        (cluster.tsne; its keywords perplexity, n_neighbors, n_iter, early_exaggeration, exaggeration_iter, learning_rate, init,
+        seed, graph, check_every, query_block, candidate_chunk and blocks pass through): the picture of the fit.  Deterministic:
+        the repulsive term is all pairs by brute force, and nothing is random after the start.
+
+        graph : ``(indices, sq_distances)`` as cell_neighbors() returned them on the same features, to spare the search.
+        Returns NumPy arrays: 'embedding' (n, 2) float64 and 'beta' (n,) float64; 'kl' (float, at the final layout), 'kl_trace',
+        'n_iter', 'n_neighbors'; 'features' (the (n, d) float32 matrix that was laid out) and 'factors' as cluster_cells()
+        returns them.  A model sharded over more than one rank raises NotImplementedError: row-sharded layouts are not
+        implemented.  Nothing of the model's state is written."""
+        from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in tsne_kw:
+            raise ValueError('cell_layout() uses the process group of the model')
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('cell_layout() is not implemented for a model sharded over more than one rank')
+        F = self._cell_features(features, cols)
+        out = cluster.tsne(F, pg=self.pg, **tsne_kw)
+        out['embedding'] = out['embedding'].cpu().numpy()
+        out['beta'] = out['beta'].cpu().numpy()
+        out['features'] = F.cpu().numpy()
+        out['factors'] = cols
+        return out
+
     # ---- which genes distinguish a cluster (scanpy's rank_genes_groups(method='t-test') on the counts the model holds) --------
     # Per cluster and gene the test needs the mean, the variance and the expressing fraction of the log-normalised counts
     # y_ij = log1p(x_ij target_sum / total_i).  y = 0 wherever x = 0, so the moments are sums over the non-zero counts only:
