@@ -31,6 +31,72 @@ __all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
 
+# ---- what kmeans(), knn(), silhouette() and tsne() share on the host -----------------------------------------------------------
+def _scratch_bytes(entry, *args):
+    """Bytes of scratch of one call, from the library's `entry` (a *_scratch_bytes* function of the call's sizes)."""
+    nbytes = int(getattr(_lib.load(), entry)(*args))
+    if nbytes < 0:
+        raise _lib.OrianaHipError('%s failed with code %d' % (entry, nbytes))
+    return nbytes
+
+
+def _scratch_for(scratch, nbytes, device):
+    """The caller's scratch, refused where it holds fewer than nbytes (the entries take no size: they would write past it), or
+    a new one."""
+    if scratch is None:
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    if scratch.numel() * scratch.element_size() < nbytes:
+        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    return scratch
+
+
+def _check_cuts(blocks, candidate_chunk, query_block):
+    if int(blocks) < 0 or any(v is not None and int(v) < 1 for v in (candidate_chunk, query_block)):
+        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+
+
+def _block_sizes(total, block):
+    """The sizes that occur when `total` rows are cut into blocks of `block`: the full block and the shorter last one."""
+    return {min(block, total)} | ({total % block} if total > block else set())
+
+
+def _plan(nq, n, candidate_chunk, query_block, budget, scratch, need=None, chunk_need=None):
+    """The planning of knn_plan(), silhouette_plan() and tsne_plan(): (query_block, candidate_chunk, scratch(query_block,
+    candidate_chunk)).  What the caller left open starts at everything in one call; then the candidates are halved while
+    chunk_need(chunk, tile) exceeds half the budget (never without a chunk_need), then the queries, in whole tiles of the
+    kernels, while need(query_block, chunk) (default: the scratch) exceeds the budget."""
+    budget = SCRATCH_BUDGET if budget is None else int(budget)
+    tile = int(_lib.load().oriana_knn_tile_rows())
+    need = scratch if need is None else need
+    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
+    qb = int(query_block) if query_block is not None else max(nq, 1)
+    if candidate_chunk is None and chunk_need is not None:
+        while chunk > 1 and chunk_need(chunk, tile) > budget // 2:
+            chunk = (chunk + 1) // 2
+    if query_block is None:
+        while qb > tile and need(qb, chunk) > budget:
+            qb = max(tile, -(-qb // (2 * tile)) * tile)
+    return qb, chunk, scratch(qb, chunk)
+
+
+def _finite_flag(*tensors):
+    """(1,) float64 on the tensors' device: 1 where every entry of every tensor is finite, else 0."""
+    ok = torch.isfinite(tensors[0]).all()
+    for t in tensors[1:]:
+        ok = ok & torch.isfinite(t).all()
+    return ok.to(torch.float64).reshape(1)
+
+
+def _all_finite(pg, *tensors):
+    """Whether the tensors are finite on every rank (one all-reduced flag under sharding)."""
+    finite = _finite_flag(*tensors)
+    if odist.sharded(pg):
+        finite = 1.0 - finite
+        odist.all_reduce_sum(finite, pg)
+        finite = 1.0 - finite.clamp(max=1.0)
+    return bool(finite.item())
+
+
 def max_centers(d):
     """The largest number of clusters served at feature width d (0: d is not served)."""
     return int(_lib.load().oriana_kmeans_max_centers(int(d)))
@@ -61,16 +127,13 @@ def lloyd_step(Y, centers, label_restart=None, want_mind=False, blocks=0):
     if Y.stride(1) != 1 and n > 1:
         raise ValueError('the columns of Y must be contiguous')
     ldy = int(Y.stride(0)) if n > 1 else d
-    lib = _lib.load()
-    nbytes = int(lib.oriana_kmeans_scratch_bytes(n, d, C, R, int(blocks)))
-    if nbytes < 0:
-        raise _lib.OrianaHipError('oriana_kmeans_scratch_bytes failed with code %d' % nbytes)
+    nbytes = _scratch_bytes('oriana_kmeans_scratch_bytes', n, d, C, R, int(blocks))
     out = {'sums': torch.empty(R, C, d, dtype=torch.float64, device=dev),
            'counts': torch.empty(R, C, dtype=torch.int64, device=dev),
            'inertia': torch.empty(R, dtype=torch.float64, device=dev)}
     labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if label_restart is not None else None
     mind = torch.empty(R, max(n, 1), dtype=torch.float32, device=dev) if want_mind else None
-    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    scratch = _scratch_for(None, nbytes, dev)
     call('oriana_kmeans_step', ptr(Y) if n else None, n, d, ldy, ptr(centers), C, R, ptr(out['sums']), ptr(out['counts']),
          ptr(out['inertia']), ptr(labels), int(label_restart or 0), ptr(mind), ptr(scratch), int(blocks), stream_ptr())
     if labels is not None:
@@ -142,6 +205,23 @@ class _Rows:
         if self.n:
             buf[mine] = self.Y[li[mine]]
         return odist.all_reduce_sum(buf, self.pg)
+
+    def shards(self, labels=None):
+        """All rows as candidates, shard after shard in rank order: yields (first global row, rows) or, with this rank's
+        `labels` (int64), (first global row, rows, labels).  Under sharding shard s is made available on every rank: zero
+        buffers to which its owner adds its rows (and labels), summed over the ranks (exact); else Y as it lies."""
+        mine = (self.Y,) if labels is None else (self.Y, labels)
+        row0 = 0
+        for s, ns in enumerate(self.sizes):
+            shard = mine
+            if odist.sharded(self.pg):
+                shard = tuple(torch.zeros((ns,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.Y.device) for t in mine)
+                for buf, t in zip(shard, mine):
+                    if s == self.rank and ns:
+                        buf.copy_(t)
+                    odist.all_reduce_sum(buf, self.pg)
+            yield (row0,) + shard
+            row0 += ns
 
 
 def _kmeanspp(rows, u, C, pg):
@@ -293,12 +373,7 @@ def kmeans(Y, n_clusters, n_init=10, max_iter=300, tol=1e-4, init='k-means++', s
     rows = _Rows(Y, pg)
     if C > rows.N:
         raise ValueError('n_clusters = %d exceeds the %d rows' % (C, rows.N))
-    finite = torch.isfinite(Y).all().to(torch.float64).reshape(1)
-    if odist.sharded(pg):
-        finite = 1.0 - finite
-        odist.all_reduce_sum(finite, pg)
-        finite = 1.0 - finite.clamp(max=1.0)
-    if not bool(finite.item()):
+    if not _all_finite(pg, Y):
         raise ValueError('Y has non-finite entries')
 
     dev = Y.device
@@ -345,10 +420,7 @@ def _rows_ld(T):
 
 def _knn_scratch_bytes(nq, n, d, k, blocks, y_ptr, ldy):
     """Bytes of scratch of one oriana_knn call whose candidates start at y_ptr with row stride ldy."""
-    nbytes = int(_lib.load().oriana_knn_scratch_bytes_for(nq, n, d, k, int(blocks), y_ptr, ldy))
-    if nbytes < 0:
-        raise _lib.OrianaHipError('oriana_knn_scratch_bytes_for failed with code %d' % nbytes)
-    return nbytes
+    return _scratch_bytes('oriana_knn_scratch_bytes_for', nq, n, d, k, int(blocks), y_ptr, ldy)
 
 
 def knn_plan(nq, n, d, k, blocks=0, y_ptr=16, ldy=None, candidate_chunk=None, query_block=None, budget=None):
@@ -361,23 +433,12 @@ def knn_plan(nq, n, d, k, blocks=0, y_ptr=16, ldy=None, candidate_chunk=None, qu
     of the incoming rows are the part of the scratch that no candidate chunk shrinks -- are halved, in whole tiles, until the
     call fits.  Either split leaves the result unchanged bit for bit."""
     nq, n, d, k = int(nq), int(n), int(d), int(k)
-    budget = SCRATCH_BUDGET if budget is None else int(budget)
     ldy = d if ldy is None else int(ldy)
-    tile = int(_lib.load().oriana_knn_tile_rows())
 
-    def need(qb, c):
-        sizes = {min(qb, nq)} | ({nq % qb} if nq > qb else set())
-        return max(_knn_scratch_bytes(b, min(c, n), d, k, blocks, y_ptr, ldy) for b in sizes)
+    def scratch(qb, c):
+        return max(_knn_scratch_bytes(b, min(c, n), d, k, blocks, y_ptr, ldy) for b in _block_sizes(nq, qb))
 
-    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
-    qb = int(query_block) if query_block is not None else max(nq, 1)
-    if candidate_chunk is None:
-        while chunk > 1 and need(tile, chunk) > budget // 2:
-            chunk = (chunk + 1) // 2
-    if query_block is None:
-        while qb > tile and need(qb, chunk) > budget:
-            qb = max(tile, -(-qb // (2 * tile)) * tile)
-    return qb, chunk, need(qb, chunk)
+    return _plan(nq, n, candidate_chunk, query_block, budget, scratch, chunk_need=lambda c, tile: scratch(tile, c))
 
 
 def knn_step(Q, Y, idx, d2, q0=0, y0=0, exclude_self=False, merge=False, blocks=0, scratch=None):
@@ -387,11 +448,7 @@ def knn_step(Q, Y, idx, d2, q0=0, y0=0, exclude_self=False, merge=False, blocks=
     nq, ldq = _rows_ld(Q)
     n, ldy = _rows_ld(Y)
     d, k = int(Q.shape[1]), int(idx.shape[1])
-    nbytes = _knn_scratch_bytes(nq, n, d, k, blocks, ptr(Y) if n else None, ldy)
-    if scratch is None:
-        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=idx.device)
-    elif scratch.numel() * scratch.element_size() < nbytes:            # (oriana_knn itself takes no size: it would write past it)
-        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    scratch = _scratch_for(scratch, _knn_scratch_bytes(nq, n, d, k, blocks, ptr(Y) if n else None, ldy), idx.device)
     call('oriana_knn', ptr(Q) if nq else None, nq, ldq, int(q0), ptr(Y) if n else None, n, ldy, int(y0), d, k,
          1 if exclude_self else 0, 1 if merge else 0, ptr(idx), ptr(d2), ptr(scratch), int(blocks), stream_ptr())
 
@@ -437,8 +494,7 @@ def knn(Y, n_neighbors, queries=None, exclude_self=None, pg=None, candidate_chun
     n, d = int(Y.shape[0]), int(Y.shape[1])
     if k < 1:
         raise ValueError('n_neighbors must be at least 1')
-    if blocks < 0 or (candidate_chunk is not None and int(candidate_chunk) < 1) or (query_block is not None and int(query_block) < 1):
-        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+    _check_cuts(blocks, candidate_chunk, query_block)
     kmax = max_neighbors(d) if d >= 1 else 0
     if kmax == 0:
         raise ValueError('%d features are not served' % d)
@@ -446,13 +502,7 @@ def knn(Y, n_neighbors, queries=None, exclude_self=None, pg=None, candidate_chun
         raise ValueError('n_neighbors = %d is beyond the %d served at %d features' % (k, kmax, d))
     if not Y.is_cuda or (queries is not None and queries.device != Y.device):
         raise ValueError('Y and queries must be tensors of one device')
-    finite = torch.isfinite(Y).all() if queries is None else torch.isfinite(Y).all() & torch.isfinite(queries).all()
-    finite = finite.to(torch.float64).reshape(1)
-    if odist.sharded(pg):
-        finite = 1.0 - finite
-        odist.all_reduce_sum(finite, pg)
-        finite = 1.0 - finite.clamp(max=1.0)
-    if not bool(finite.item()):
+    if not _all_finite(pg, *((Y,) if queries is None else (Y, queries))):
         raise ValueError('Y or queries have non-finite entries')
     rows = _Rows(Y, pg)
     if rows.N > 2 ** 31 - 1:
@@ -461,29 +511,19 @@ def knn(Y, n_neighbors, queries=None, exclude_self=None, pg=None, candidate_chun
     dev = Y.device
     Q, q0 = (Y, rows.row0) if queries is None else (queries, 0)
     nq = int(Q.shape[0])
-    # the shards arrive in contiguous buffers of their own; without sharding the candidates are Y as it lies
+    # the shards (_Rows.shards) arrive in contiguous buffers of their own; without sharding the candidates are Y as it lies
     y_ptr, ldy = (16, d) if odist.sharded(pg) else (ptr(Y) if n else None, _rows_ld(Y)[1])
     qb, chunk, nbytes = knn_plan(nq, max(rows.sizes), d, k, blocks, y_ptr, ldy, candidate_chunk, query_block)
     scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
     idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
     d2 = torch.empty(nq, k, dtype=torch.float32, device=dev)
     merge = False
-    y0 = 0
-    for s, ns in enumerate(rows.sizes):
-        if odist.sharded(pg):
-            # shard s on every rank: a zero buffer to which its owner adds its rows, summed over the ranks (exact)
-            cand = torch.zeros(ns, d, dtype=torch.float32, device=dev)
-            if s == rows.rank and ns:
-                cand.copy_(Y)
-            odist.all_reduce_sum(cand, pg)
-        else:
-            cand = Y
-        for a in range(0, ns, chunk):
+    for y0, cand in rows.shards():
+        for a in range(0, int(cand.shape[0]), chunk):
             for b in range(0, nq, qb):
                 knn_step(Q[b:b + qb], cand[a:a + chunk], idx[b:b + qb], d2[b:b + qb], q0=q0 + b, y0=y0 + a,
                          exclude_self=exclude_self, merge=merge, blocks=blocks, scratch=scratch)
             merge = True
-        y0 += ns
     if not merge:                                     # (no candidates at all: the padding values)
         knn_step(Q, Y[:0], idx, d2, q0=q0, blocks=blocks)
     return {'indices': idx, 'sq_distances': d2}
@@ -497,10 +537,7 @@ def max_clusters():
 
 def _sums_scratch_bytes(nq, n, d, C, blocks, y_ptr, ldy):
     """Bytes of scratch of one oriana_cluster_distance_sums call whose candidates start at y_ptr with row stride ldy."""
-    nbytes = int(_lib.load().oriana_cluster_distance_sums_scratch_bytes_for(nq, n, d, C, int(blocks), y_ptr, ldy))
-    if nbytes < 0:
-        raise _lib.OrianaHipError('oriana_cluster_distance_sums_scratch_bytes_for failed with code %d' % nbytes)
-    return nbytes
+    return _scratch_bytes('oriana_cluster_distance_sums_scratch_bytes_for', nq, n, d, C, int(blocks), y_ptr, ldy)
 
 
 def distance_sums(Q, Y, offsets, sums=None, accumulate=False, blocks=0, scratch=None):
@@ -527,11 +564,7 @@ def distance_sums(Q, Y, offsets, sums=None, accumulate=False, blocks=0, scratch=
     lds = int(sums.stride(0)) if C > 1 else nq
     if lds < nq:
         raise ValueError('the rows of sums overlap')
-    nbytes = _sums_scratch_bytes(nq, n, d, C, blocks, ptr(Y) if n else None, ldy)
-    if scratch is None:
-        scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=Q.device)
-    elif scratch.numel() * scratch.element_size() < nbytes:            # (the entry takes no size: it would write past it)
-        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    scratch = _scratch_for(scratch, _sums_scratch_bytes(nq, n, d, C, blocks, ptr(Y) if n else None, ldy), Q.device)
     call('oriana_cluster_distance_sums', ptr(Q) if nq else None, nq, ldq, ptr(Y) if n else None, n, ldy, d, off.ctypes.data, C,
          ptr(sums), lds, 1 if accumulate else 0, ptr(scratch), int(blocks), stream_ptr())
     return sums
@@ -579,12 +612,9 @@ def silhouette_plan(nq, n, d, C, blocks=0, candidate_chunk=None, query_block=Non
     for knn_plan() the scratch of a call is not monotone in its queries, so the bytes are the largest need over the block sizes
     that occur.  Either split changes the float64 summation order and nothing else."""
     nq, n, d, C = int(nq), int(n), int(d), int(C)
-    budget = SCRATCH_BUDGET if budget is None else int(budget)
-    tile = int(_lib.load().oriana_knn_tile_rows())
 
-    def scratch(qb, c):
-        sizes = {min(qb, nq)} | ({nq % qb} if nq > qb else set())
-        return max(_sums_scratch_bytes(b, min(c, n), d, C, blocks, 16, d) for b in sizes)      # (the copy is contiguous and aligned)
+    def scratch(qb, c):                               # (the grouped copy is contiguous and aligned)
+        return max(_sums_scratch_bytes(b, min(c, n), d, C, blocks, 16, d) for b in _block_sizes(nq, qb))
 
     def candidates(c):
         return min(c, n) * (4 * d + 24)
@@ -592,15 +622,8 @@ def silhouette_plan(nq, n, d, C, blocks=0, candidate_chunk=None, query_block=Non
     def need(qb, c):
         return scratch(qb, c) + candidates(c) + 8 * C * (nq if resident else min(qb, nq))
 
-    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
-    qb = int(query_block) if query_block is not None else max(nq, 1)
-    if candidate_chunk is None:
-        while chunk > 1 and candidates(chunk) + (scratch(tile, chunk) - scratch(tile, 1)) > budget // 2:
-            chunk = (chunk + 1) // 2
-    if query_block is None:
-        while qb > tile and need(qb, chunk) > budget:
-            qb = max(tile, -(-qb // (2 * tile)) * tile)
-    return qb, chunk, scratch(qb, chunk)
+    return _plan(nq, n, candidate_chunk, query_block, budget, scratch, need,
+                 chunk_need=lambda c, tile: candidates(c) + (scratch(tile, c) - scratch(tile, 1)))
 
 
 def _label_tensor(labels, n, what):
@@ -659,8 +682,7 @@ def silhouette(Y, labels, n_clusters=None, pg=None, candidate_chunk=None, query_
     blocks = int(blocks)
     if d < 1 or d > 256:
         raise ValueError('%d features are not served' % d)
-    if blocks < 0 or (candidate_chunk is not None and int(candidate_chunk) < 1) or (query_block is not None and int(query_block) < 1):
-        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+    _check_cuts(blocks, candidate_chunk, query_block)
     lab = _label_tensor(labels, n, 'labels')
     sharded = odist.sharded(pg)
     if sharded and not Y.is_cuda:
@@ -673,8 +695,7 @@ def silhouette(Y, labels, n_clusters=None, pg=None, candidate_chunk=None, query_
     if C > max_clusters():
         raise ValueError('%d clusters are beyond the %d served' % (C, max_clusters()))
     counts = torch.bincount(lab, minlength=C).to(torch.float64)              # (exact: counts stay below 2^53)
-    finite = 1.0 - torch.isfinite(Y).all().to(torch.float64).reshape(1)
-    packed = torch.cat([counts, finite])
+    packed = torch.cat([counts, 1.0 - _finite_flag(Y)])         # (the flag travels with the counts: one all-reduce)
     odist.all_reduce_sum(packed, pg)
     packed = packed.cpu().numpy()
     counts_h = packed[:C].astype(np.int64)
@@ -705,15 +726,8 @@ def silhouette(Y, labels, n_clusters=None, pg=None, candidate_chunk=None, query_
 
     if sharded:
         S = torch.zeros(C, n, dtype=torch.float64, device=dev)
-        for s, ns in enumerate(rows.sizes):
-            # shard s on every rank: zero buffers to which its owner adds its rows and labels, summed over the ranks (exact)
-            cand = torch.zeros(ns, d, dtype=torch.float32, device=dev)
-            clab = torch.zeros(ns, dtype=torch.int64, device=dev)
-            if s == rows.rank and ns:
-                cand.copy_(Y)
-                clab.copy_(lab)
-            odist.all_reduce_sum(cand, pg)
-            odist.all_reduce_sum(clab, pg)
+        for _, cand, clab in rows.shards(lab):
+            ns = int(cand.shape[0])
             for a0 in range(0, ns, chunk):
                 g, off = grouped(cand, clab, a0, min(a0 + chunk, ns))
                 for b0 in range(0, n, qb):
@@ -860,10 +874,7 @@ def tsne_attract(P, Y):
 
 
 def _repulse_scratch_bytes(nq, n, blocks):
-    nbytes = int(_lib.load().oriana_tsne_repulse_scratch_bytes_for(int(nq), int(n), int(blocks)))
-    if nbytes < 0:
-        raise _lib.OrianaHipError('oriana_tsne_repulse_scratch_bytes_for failed with code %d' % nbytes)
-    return nbytes
+    return _scratch_bytes('oriana_tsne_repulse_scratch_bytes_for', int(nq), int(n), int(blocks))
 
 
 def tsne_repulse(Q, Y, rep=None, zrow=None, accumulate=False, blocks=0, scratch=None):
@@ -883,11 +894,7 @@ def tsne_repulse(Q, Y, rep=None, zrow=None, accumulate=False, blocks=0, scratch=
         raise ValueError('rep must be a contiguous (nq, 2) = %s float64 tensor' % ((nq, 2),))
     if zrow.dtype != torch.float64 or tuple(zrow.shape) != (nq,) or not zrow.is_contiguous():
         raise ValueError('zrow must be a contiguous (nq,) = %s float64 tensor' % ((nq,),))
-    nbytes = _repulse_scratch_bytes(nq, n, blocks)
-    if scratch is None:
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=Q.device)
-    elif scratch.numel() * scratch.element_size() < nbytes:            # (the entry takes no size: it would write past it)
-        raise ValueError('the scratch holds %d bytes, this call needs %d' % (scratch.numel() * scratch.element_size(), nbytes))
+    scratch = _scratch_for(scratch, _repulse_scratch_bytes(nq, n, blocks), Q.device)
     call('oriana_tsne_repulse', ptr(Q) if nq else None, nq, ptr(Y) if n else None, n, ptr(rep) if nq else None,
          ptr(zrow) if nq else None, 1 if accumulate else 0, ptr(scratch), int(blocks), stream_ptr())
     return rep, zrow
@@ -899,22 +906,12 @@ def tsne_plan(n, blocks=0, query_block=None, candidate_chunk=None, budget=None):
     queries halved in whole tiles until the scratch (1,536 bytes per query tile and candidate range) stays within `budget`
     (default SCRATCH_BUDGET)."""
     n = int(n)
-    budget = SCRATCH_BUDGET if budget is None else int(budget)
-    tile = 64
-    chunk = int(candidate_chunk) if candidate_chunk is not None else max(n, 1)
-    qb = int(query_block) if query_block is not None else max(n, 1)
-    if chunk < 1 or qb < 1 or int(blocks) < 0:
-        raise ValueError('blocks >= 0, candidate_chunk >= 1 and query_block >= 1 are required')
+    _check_cuts(blocks, candidate_chunk, query_block)
 
-    def need(q, c):
-        qs = {min(q, n)} | ({n % q} if n > q else set())
-        cs = {min(c, n)} | ({n % c} if n > c else set())
-        return max(_repulse_scratch_bytes(a, b, blocks) for a in qs for b in cs)
+    def scratch(q, c):
+        return max(_repulse_scratch_bytes(a, b, blocks) for a in _block_sizes(n, q) for b in _block_sizes(n, c))
 
-    if query_block is None:
-        while qb > tile and need(qb, chunk) > budget:
-            qb = max(tile, -(-qb // (2 * tile)) * tile)
-    return qb, chunk, need(qb, chunk)
+    return _plan(n, n, candidate_chunk, query_block, budget, scratch)
 
 
 def tsne_gradient(P, Y32, exaggeration=1.0, query_block=None, candidate_chunk=None, blocks=0):

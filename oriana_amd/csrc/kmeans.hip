@@ -2,32 +2,30 @@
 // sums and counts, inertia, the minimum distance.  DESIGN.md section 5i.
 //
 // A work-group owns a contiguous range of 64-row tiles and a group of G restarts, one restart per wave.  The tile is staged in
-// LDS once for the group, feature-major ([k][65]: row stride 65, column 64 stays zero).
+// LDS once for the group, in the layout of rowscan.h (feature-major [k][65], column 64 stays zero); the staging loop is this
+// file's own, because the waves of the group are a run-time number here.
 //   assign      lane = row.  The centres of the wave's restart are wave-uniform: they come through scalar loads from a padded
 //               float32 image ((R, Cp, dp), dp = pad4(d), Cp = C rounded up to 8; written by k_kmeans_pad), 8 centres x 4
 //               features per step; d2 = sum_k (y_k - c_k)^2 by sequential fma over k ascending, the arg-min by a strict < over c
-//               ascending (the smallest index wins a tie).
+//               ascending (the smallest index wins a tie).  The chain is the text of rowscan.h's chain8, kept here as a copy:
+//               called through the header, with row pointers cen + (c0 + j) dq, this kernel parked 38 SGPRs in VGPR lanes
+//               instead of 10.
 //   accumulate  lane = feature.  For every cluster c the rows labelled c (a ballot) are added in ascending row order in a register,
 //               the tile's sum then goes into the wave's own (C, dp) float32 partial in LDS: no atomics, a fixed order.  After
 //               KM_FLUSH tiles the partial is promoted into the work-group's float64 partial in global memory.
 // k_kmeans_reduce adds the work-groups' partials in ascending order.  Nothing depends on which waves share a work-group, so a
 // restart's outputs are the same bit for bit alone or inside any batch, for a given number of work-groups along the rows.
-#include "launch.h"
+#include "rowscan.h"
 
 namespace oriana {
 namespace {
 
-constexpr int KM_ROWS = 64;               // rows of a tile (one per lane)
-constexpr int KM_LD = 65;                 // floats between two features of the LDS tile; column 64 holds 0
 constexpr int KM_G = 4;                   // restarts (waves) of a work-group; 2 where the partials of 4 do not fit
-constexpr int KM_CH = 8;                  // centres per step of the assign phase
 constexpr int KM_FLUSH = 4;               // tiles between two promotions of the float32 partials to float64
 constexpr int64_t KM_LDS = 160 * 1024;    // LDS of a CU
 constexpr int64_t KM_MAX_CD = 8192;       // C * pad4(d) served
-constexpr int64_t KM_MAX_D = 256;
 
-inline int64_t km_pad4(int64_t d) { return (d + 3) / 4 * 4; }
-inline int64_t km_lds_bytes(int64_t dp, int64_t C, int64_t G) { return 4 * (dp * KM_LD + G * C * dp + G * C); }
+inline int64_t km_lds_bytes(int64_t dp, int64_t C, int64_t G) { return 4 * (dp * RS_LD + G * C * dp + G * C); }
 inline int64_t km_group(int64_t dp, int64_t C) { return km_lds_bytes(dp, C, KM_G) <= KM_LDS ? KM_G : 2; }
 
 struct KmPlan {
@@ -38,12 +36,12 @@ struct KmPlan {
 // sizes in range (d, C, R >= 1, n >= 0, C within oriana_kmeans_max_centers(d))
 KmPlan km_plan(int64_t n, int64_t d, int64_t C, int64_t R, int64_t blocks) {
     KmPlan p;
-    p.dp = km_pad4(d);
-    p.Cp = (C + KM_CH - 1) / KM_CH * KM_CH;
+    p.dp = pad4(d);
+    p.Cp = (C + RS_CH - 1) / RS_CH * RS_CH;
     p.G = km_group(p.dp, C);
     p.groups = (R + p.G - 1) / p.G;
-    p.ntiles = (n + KM_ROWS - 1) / KM_ROWS;
-    int64_t bx = blocks > 0 ? blocks : (2 * oriana_device_cus() + p.groups - 1) / p.groups;      // two work-groups per CU
+    p.ntiles = (n + RS_ROWS - 1) / RS_ROWS;
+    int64_t bx = two_per_cu(blocks, p.groups);
     if (bx > p.ntiles) bx = p.ntiles;
     if (bx < 1) bx = 1;
     p.bx = bx;
@@ -98,12 +96,12 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
     const int lane = (int)(threadIdx.x & 63);
     const int CD = C * dp;
     float *tile = lds;
-    float *part = lds + dp * KM_LD + w * CD;
-    int *cnt = reinterpret_cast<int *>(lds + dp * KM_LD + G * CD) + w * C;
+    float *part = lds + dp * RS_LD + w * CD;
+    int *cnt = reinterpret_cast<int *>(lds + dp * RS_LD + G * CD) + w * C;
     const int r = (int)blockIdx.y * G + w;
     const bool live = r < R;                                          // (wave-uniform)
 
-    for (int e = (int)threadIdx.x; e < dp * KM_LD; e += (int)blockDim.x) tile[e] = 0.0f;      // the padding features, column 64
+    for (int e = (int)threadIdx.x; e < dp * RS_LD; e += (int)blockDim.x) tile[e] = 0.0f;      // the padding features, column 64
     if (live) {
         for (int e = lane; e < CD; e += 64) part[e] = 0.0f;
         for (int e = lane; e < C; e += 64) cnt[e] = 0;
@@ -120,11 +118,11 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
     int pending = 0;
 
     for (int64_t t = t0; t < t1; ++t) {
-        const int64_t row0 = t * KM_ROWS;
-        const int nrow = n - row0 < KM_ROWS ? (int)(n - row0) : KM_ROWS;
+        const int64_t row0 = t * RS_ROWS;
+        const int nrow = n - row0 < RS_ROWS ? (int)(n - row0) : RS_ROWS;
         // ---- stage the tile: wave w takes rows w, w + G, ..; lanes over the features; eight loads in flight
         for (int kk = lane; kk < d; kk += 64) {
-            for (int ib = 0; ib < KM_ROWS / G; ib += 16) {          // (KM_ROWS / G is 16 or 32)
+            for (int ib = 0; ib < RS_ROWS / G; ib += 16) {          // (RS_ROWS / G is 16 or 32)
                 float v[16];
                 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
@@ -132,7 +130,7 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
                     v[u] = i < nrow ? Y[(row0 + i) * ldy + kk] : 0.0f;
                 }
                 #pragma unroll
-                for (int u = 0; u < 16; ++u) tile[kk * KM_LD + w + (ib + u) * G] = v[u];
+                for (int u = 0; u < 16; ++u) tile[kk * RS_LD + w + (ib + u) * G] = v[u];
             }
         }
         __syncthreads();
@@ -141,15 +139,15 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
             float best = INFINITY;
             int lab = 0;
             const float *tl = tile + lane;
-            for (int c0 = 0; c0 < C; c0 += KM_CH) {
-                float acc[KM_CH];
+            for (int c0 = 0; c0 < C; c0 += RS_CH) {
+                float acc[RS_CH];
                 #pragma unroll
-                for (int j = 0; j < KM_CH; ++j) acc[j] = 0.0f;
+                for (int j = 0; j < RS_CH; ++j) acc[j] = 0.0f;
                 for (int q = 0; q < dq; ++q) {
-                    const float y0 = tl[(4 * q + 0) * KM_LD], y1 = tl[(4 * q + 1) * KM_LD];
-                    const float y2 = tl[(4 * q + 2) * KM_LD], y3 = tl[(4 * q + 3) * KM_LD];
+                    const float y0 = tl[(4 * q + 0) * RS_LD], y1 = tl[(4 * q + 1) * RS_LD];
+                    const float y2 = tl[(4 * q + 2) * RS_LD], y3 = tl[(4 * q + 3) * RS_LD];
                     #pragma unroll
-                    for (int j = 0; j < KM_CH; ++j) {
+                    for (int j = 0; j < RS_CH; ++j) {
                         const float4 cv = cen[(c0 + j) * dq + q];
                         const float e0 = y0 - cv.x, e1 = y1 - cv.y, e2 = y2 - cv.z, e3 = y3 - cv.w;
                         acc[j] = fmaf(e0, e0, acc[j]);
@@ -159,7 +157,7 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
                     }
                 }
                 #pragma unroll
-                for (int j = 0; j < KM_CH; ++j)
+                for (int j = 0; j < RS_CH; ++j)
                     if (c0 + j < C && acc[j] < best) { best = acc[j]; lab = c0 + j; }
             }
             const bool valid = lane < nrow;
@@ -175,14 +173,14 @@ k_kmeans_step(const float *__restrict__ Y, int64_t n, int d, int64_t ldy, const 
                 if (lane == 0) cnt[c] += __popcll(mask);
                 for (int kb = 0; kb < dp; kb += 64) {
                     const bool on = kb + lane < dp;
-                    const float *tk = tile + (on ? kb + lane : 0) * KM_LD;
+                    const float *tk = tile + (on ? kb + lane : 0) * RS_LD;
                     float a = 0.0f;
                     unsigned long long m = mask;
                     while (m) {
                         const int i0 = __builtin_ctzll(m); m &= m - 1;
-                        const int i1 = m ? __builtin_ctzll(m) : KM_ROWS; m &= m - 1;      // (column 64: + 0)
-                        const int i2 = m ? __builtin_ctzll(m) : KM_ROWS; m &= m - 1;
-                        const int i3 = m ? __builtin_ctzll(m) : KM_ROWS; m &= m - 1;
+                        const int i1 = m ? __builtin_ctzll(m) : RS_ROWS; m &= m - 1;      // (column 64: + 0)
+                        const int i2 = m ? __builtin_ctzll(m) : RS_ROWS; m &= m - 1;
+                        const int i3 = m ? __builtin_ctzll(m) : RS_ROWS; m &= m - 1;
                         const float v0 = tk[i0], v1 = tk[i1], v2 = tk[i2], v3 = tk[i3];
                         a += v0; a += v1; a += v2; a += v3;
                     }
@@ -240,18 +238,18 @@ k_kmeans_reduce(double *__restrict__ sums, int64_t *__restrict__ counts, double 
 using namespace oriana;
 
 extern "C" int64_t oriana_kmeans_max_centers(int64_t d) {
-    if (d < 1 || d > KM_MAX_D) return 0;
-    return KM_MAX_CD / km_pad4(d);
+    if (d < 1 || d > RS_MAX_D) return 0;
+    return KM_MAX_CD / pad4(d);
 }
 
 extern "C" int64_t oriana_kmeans_group(int64_t d, int64_t C) {
     if (d < 1 || C < 1 || C > oriana_kmeans_max_centers(d)) return 0;
-    return km_group(km_pad4(d), C);
+    return km_group(pad4(d), C);
 }
 
-extern "C" int64_t oriana_kmeans_partial_rows(void) { return (int64_t)KM_FLUSH * KM_ROWS; }
+extern "C" int64_t oriana_kmeans_partial_rows(void) { return (int64_t)KM_FLUSH * RS_ROWS; }
 
-extern "C" int64_t oriana_kmeans_tile_rows(void) { return KM_ROWS; }
+extern "C" int64_t oriana_kmeans_tile_rows(void) { return RS_ROWS; }
 
 extern "C" int64_t oriana_kmeans_scratch_bytes(int64_t n, int64_t d, int64_t C, int64_t R, int64_t blocks) {
     if (n < 0 || d < 1 || C < 1 || R < 1 || blocks < 0) return ORIANA_EINVAL;
@@ -266,7 +264,7 @@ extern "C" int oriana_kmeans_step(const float *Y, int64_t n, int64_t d, int64_t 
     if (C > oriana_kmeans_max_centers(d)) return ORIANA_EKRANGE;
     if (!centers || !sums || !counts || !inertia || !scratch || (n > 0 && !Y)) return ORIANA_EINVAL;
     if (labels && (label_restart < 0 || label_restart >= R)) return ORIANA_EINVAL;
-    if (((uintptr_t)scratch & 15) || R > 0x7fffffffLL / (C * km_pad4(d) + 8)) return ORIANA_EINVAL;
+    if (((uintptr_t)scratch & 15) || R > 0x7fffffffLL / (C * pad4(d) + 8)) return ORIANA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         ORIANA_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)(R * C * d) * 8, st));

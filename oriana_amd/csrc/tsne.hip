@@ -10,18 +10,19 @@
 //                    The pair is ONE float32 sequence (tsne_pair below).  Every w is converted to float64 and added to the lane's
 //                    float64 sum (the driver subtracts the n self pairs from Z: a float32 partial sum next to an exact 1 would
 //                    cost Z its digits where Z << n); the two force terms of a step's candidates are added in float32 in
-//                    candidate order, and the step's two sums are converted and added to the lane's float64 running sums.  At the end the four sums of a query are added through LDS in wave order and written as
+//                    candidate order, and the step's two sums are converted and added to the lane's float64
+//                    running sums.  At the end the four sums of a query are added through LDS in wave order and written as
 //                    float64 per (tile, range, component, lane).
-// k_tsne_reduce      lane = query: the ranges are added in range order and written (or, with accumulate, added) to rep / zrow.
-// No atomics; every output has one writer and a fixed order inside a launch.
-#include "launch.h"
+// k_tsne_reduce      lane = query: the ranges are added in range order (rowscan.h: add_ranges) and written (or, with accumulate,
+//                    added) to rep / zrow.
+// No atomics; every output has one writer and a fixed order inside a launch.  From rowscan.h come also the tile and step sizes,
+// the two-work-groups-per-CU rule of the ranges and the limit on the row counts; there is no LDS tile and no d-long chain here.
+#include "rowscan.h"
 
 namespace oriana {
 namespace {
 
-constexpr int TS_ROWS = 64;               // queries of a tile (one per lane)
 constexpr int TS_W = 4;                   // waves of a work-group
-constexpr int TS_CH = 8;                  // candidates per step
 constexpr int64_t TS_MAX_SPLIT = 32767;   // ranges the candidates are cut into (the y extent of the grid)
 constexpr int TS_STEPS = 200;             // evaluations of the entropy per row, at most
 constexpr double TS_HTOL = 1e-9;          // |H - log perplexity| at which the search of a row stops
@@ -125,47 +126,47 @@ struct TsPlan {
 
 TsPlan ts_plan(int64_t nq, int64_t n, int64_t blocks) {
     TsPlan p;
-    p.ntiles = (nq + TS_ROWS - 1) / TS_ROWS;
-    const int64_t steps = (n + TS_CH - 1) / TS_CH;
-    int64_t t = blocks > 0 ? blocks : (2 * oriana_device_cus() + p.ntiles - 1) / (p.ntiles > 0 ? p.ntiles : 1);   // two per CU
+    p.ntiles = (nq + RS_ROWS - 1) / RS_ROWS;
+    const int64_t steps = (n + RS_CH - 1) / RS_CH;
+    int64_t t = two_per_cu(blocks, p.ntiles);
     if (t > TS_MAX_SPLIT) t = TS_MAX_SPLIT;
     if (t > steps) t = steps;
     if (t < 1) t = 1;
     p.sp = steps > 0 ? (steps + t - 1) / t : 1;
     p.nranges = steps > 0 ? (steps + p.sp - 1) / p.sp : 0;       // (no range is empty)
-    p.total = p.ntiles * p.nranges * 3 * TS_ROWS * 8;
+    p.total = p.ntiles * p.nranges * 3 * RS_ROWS * 8;
     return p;
 }
 
 // part: [tile][range][3][64] float64; range r owns the candidates [r sp 8, min((r + 1) sp 8, n))
 __global__ void __launch_bounds__(64 * TS_W)
 k_tsne_repulse(const float2 *__restrict__ Q, int64_t nq, const float2 *__restrict__ Y, int n, int sp, double *__restrict__ part) {
-    __shared__ double red[TS_W * 3 * TS_ROWS];
+    __shared__ double red[TS_W * 3 * RS_ROWS];
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
-    const int64_t q = (int64_t)blockIdx.x * TS_ROWS + lane;
+    const int64_t q = (int64_t)blockIdx.x * RS_ROWS + lane;
     const float2 qv = Q[q < nq ? q : nq - 1];                      // (a lane beyond the queries repeats the last one; never written)
     const float qx = qv.x, qy = qv.y;
 
     // (rows are ints: n <= 2^31 - 9, so r0 + st * 8 + 7 stays an int)
-    const int64_t first = (int64_t)blockIdx.y * sp * TS_CH, last = first + (int64_t)sp * TS_CH;
+    const int64_t first = (int64_t)blockIdx.y * sp * RS_CH, last = first + (int64_t)sp * RS_CH;
     const int r0 = (int)first, r1 = (int)(last < n ? last : n);
-    const int nst = (r1 - r0 + TS_CH - 1) / TS_CH;
+    const int nst = (r1 - r0 + RS_CH - 1) / RS_CH;
     double sx = 0.0, sy = 0.0, sz = 0.0;
 
     for (int st = w; st < nst; st += TS_W) {
-        const int c0 = r0 + st * TS_CH;
+        const int c0 = r0 + st * RS_CH;
         float ax = 0.0f, ay = 0.0f;
-        if (c0 + TS_CH <= r1) {                                    // (wave-uniform) a whole step: 16 consecutive floats
+        if (c0 + RS_CH <= r1) {                                    // (wave-uniform) a whole step: 16 consecutive floats
             const float2 *c = Y + c0;
-            float2 v[TS_CH];
+            float2 v[RS_CH];
             #pragma unroll
-            for (int j = 0; j < TS_CH; ++j) v[j] = c[j];
+            for (int j = 0; j < RS_CH; ++j) v[j] = c[j];
             #pragma unroll
-            for (int j = 0; j < TS_CH; ++j) tsne_pair(qx, qy, v[j].x, v[j].y, ax, ay, sz);
+            for (int j = 0; j < RS_CH; ++j) tsne_pair(qx, qy, v[j].x, v[j].y, ax, ay, sz);
         } else {                                                   // the range's tail re-reads the last point, masked
             #pragma unroll
-            for (int j = 0; j < TS_CH; ++j) {
+            for (int j = 0; j < RS_CH; ++j) {
                 const float2 v = Y[c0 + j < r1 ? c0 + j : r1 - 1];
                 if (c0 + j < r1) tsne_pair(qx, qy, v.x, v.y, ax, ay, sz);
             }
@@ -175,18 +176,18 @@ k_tsne_repulse(const float2 *__restrict__ Q, int64_t nq, const float2 *__restric
     }
 
     // ---- the four sums of a query in wave order
-    red[(w * 3 + 0) * TS_ROWS + lane] = sx;
-    red[(w * 3 + 1) * TS_ROWS + lane] = sy;
-    red[(w * 3 + 2) * TS_ROWS + lane] = sz;
+    red[(w * 3 + 0) * RS_ROWS + lane] = sx;
+    red[(w * 3 + 1) * RS_ROWS + lane] = sy;
+    red[(w * 3 + 2) * RS_ROWS + lane] = sz;
     __syncthreads();
     if (w == 0) {
-        double *out = part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (3 * TS_ROWS) + lane;
+        double *out = part + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (3 * RS_ROWS) + lane;
         #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            double s = red[c * TS_ROWS + lane];
+            double s = red[c * RS_ROWS + lane];
             #pragma unroll
-            for (int v = 1; v < TS_W; ++v) s += red[(v * 3 + c) * TS_ROWS + lane];
-            out[c * TS_ROWS] = s;
+            for (int v = 1; v < TS_W; ++v) s += red[(v * 3 + c) * RS_ROWS + lane];
+            out[c * RS_ROWS] = s;
         }
     }
 }
@@ -195,28 +196,23 @@ __global__ void __launch_bounds__(64)
 k_tsne_reduce(double *__restrict__ rep, double *__restrict__ zrow, int64_t nq, const double *__restrict__ part, int nranges,
               int accumulate) {
     const int lane = (int)threadIdx.x;
-    const int64_t q = (int64_t)blockIdx.x * TS_ROWS + lane;
+    const int64_t q = (int64_t)blockIdx.x * RS_ROWS + lane;
     if (q >= nq) return;
-    const double *p = part + (int64_t)blockIdx.x * nranges * (3 * TS_ROWS) + lane;
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    for (int r = 0; r < nranges; ++r) {
-        sx += p[(int64_t)r * (3 * TS_ROWS)];
-        sy += p[(int64_t)r * (3 * TS_ROWS) + TS_ROWS];
-        sz += p[(int64_t)r * (3 * TS_ROWS) + 2 * TS_ROWS];
-    }
+    double s[3];
+    add_ranges(s, part, nranges, 0, nranges, lane);
     if (accumulate) {
-        sx += rep[2 * q];
-        sy += rep[2 * q + 1];
-        sz += zrow[q];
+        s[0] += rep[2 * q];
+        s[1] += rep[2 * q + 1];
+        s[2] += zrow[q];
     }
-    rep[2 * q] = sx;
-    rep[2 * q + 1] = sy;
-    zrow[q] = sz;
+    rep[2 * q] = s[0];
+    rep[2 * q + 1] = s[1];
+    zrow[q] = s[2];
 }
 
 int ts_check_sizes(int64_t nq, int64_t n, int64_t blocks) {
     if (nq < 0 || n < 0 || blocks < 0) return ORIANA_EINVAL;
-    if (nq > 0x7fffffffLL || n > 0x7fffffffLL - TS_CH) return ORIANA_EINVAL;      // (the last step's c0 + 7 is an int)
+    if (!rows_fit_int(nq, n)) return ORIANA_EINVAL;
     return 0;
 }
 
