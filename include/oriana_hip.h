@@ -1048,6 +1048,44 @@ int oriana_group_stats(const oriana_counts *cm, const oriana_dense *dn, const in
                        const int32_t *labels, const double *scale, int log1p_flag, int64_t C, double *out, void *stream);
 int64_t oriana_group_stats_max_groups(void);
 
+/* ---- tie-aware rank sums of the stored counts per (cluster, gene) (csrc/ranksum.hip, oriana_amd/models/base.py:
+ * cluster_rank_sums, marker_genes(method='wilcoxon'); no counterpart in the reference) ---------------------------
+ * cm, dn, row_perm, col_perm, labels, scale: as oriana_group_stats takes them (col_perm the FULL ordering or NULL; the outputs
+ * go through it).  One call serves one PANEL: the genes [g0, g1) of the packed order, 0 <= g0 <= g1 <= m_all = cm->m + gd, either
+ * inside the dense block (g0, g1 multiples of 32, g1 <= gd) or inside the sliced part (g0 - gd a multiple of 256; g1 - gd too
+ * unless g1 = m_all).
+ *   the key    of a stored count x of cell i: the bit pattern of the float64 v = (double)x * scale[i], ONE IEEE product
+ *              (scale == NULL: v = x).  Precondition: scale[i] > 0 and finite for every cell with a stored count, so v > 0 and the
+ *              unsigned 64-bit patterns order as the values do.  Two entries tie exactly when their patterns are equal.
+ *   outputs    per gene j of the panel (caller's gene order), over its stored counts sorted by key, positions 1-based, a tie
+ *              run occupying the positions [p, q] (t = q - p + 1 records):
+ *                cnt[c, j]  = stored counts of the cells with labels[i] == c
+ *                pos2[c, j] = sum over those entries of (p + q) of the entry's run: twice the sum of their average positions
+ *                ties[j]    = sum over the runs of t^3 - t
+ *              (C, m_all), (C, m_all), (m_all,) int64.  All C rows of the panel's columns and its ties are WRITTEN with plain
+ *              stores (a gene belongs to one work-group); nothing outside the panel's columns is touched.  Every term is an
+ *              integer: the same bits on every run, for every capacity that holds the panel and every lds_cap.  A cell whose
+ *              label lies outside [0, C) is ranked like any other, adds to no cluster and never addresses memory through its label.
+ *   scratch    oriana_rank_sums_scratch_bytes_for(capacity_records, g1 - g0) bytes, 16-byte aligned, contents undefined on entry
+ *              and exit: per gene counts, offsets and cursors, then two buffers of capacity_records {key, label} records.  If
+ *              the panel holds more stored counts than capacity_records, overflow[0] is set to 1, nothing is written outside
+ *              the scratch and the outputs are left as they were; otherwise overflow is not written (the caller zeroes it).
+ *   lds_cap    the longest segment (a gene's stored counts) one work-group sorts inside LDS; longer ones are cut into runs of
+ *              the largest power of two <= lds_cap, sorted in LDS and merged pairwise through global memory.  0 = the default,
+ *              oriana_rank_sums_lds_cap() = 4096, which is also the largest value.
+ * ORIANA_EINVAL for a NULL cm / labels / output / overflow / scratch, a negative size, C < 1, a layout oriana_group_stats
+ * refuses, a misaligned scratch, lds_cap outside [0, oriana_rank_sums_lds_cap()], a panel that is not tile-aligned or straddles
+ * the two layouts; ORIANA_EKRANGE for C above oriana_rank_sums_max_groups() = 1024 or n >= 2^21 (sum (t^3 - t) <= n^3 < 2^63);
+ * all before any HIP call.  0 without a launch for an empty panel or n = 0. */
+int64_t oriana_rank_sums_max_groups(void);
+int64_t oriana_rank_sums_lds_cap(void);
+/* (negative: ORIANA_EINVAL for a negative argument) */
+int64_t oriana_rank_sums_scratch_bytes_for(int64_t records, int64_t genes);
+int oriana_rank_sums(const oriana_counts *cm, const oriana_dense *dn, const int32_t *row_perm, const int32_t *col_perm,
+                     const int32_t *labels, const double *scale, int64_t C, int64_t g0, int64_t g1, void *scratch,
+                     int64_t capacity_records, int64_t lds_cap, int64_t *pos2, int64_t *cnt, int64_t *ties, int32_t *overflow,
+                     void *stream);
+
 /* ---- the exact t-SNE layout of the cells (csrc/tsne.hip, oriana_amd/cluster.py: tsne) --------------------------
  * oriana_tsne_affinities : conditional neighbour probabilities at a perplexity.  sq_distances (n, k) float32 contiguous, what
  *   oriana_knn wrote: every row ascending and padded with +inf.  Per row, over its m finite entries, p_j = exp(-beta (d_j - d_0))

@@ -184,6 +184,11 @@ _SIGS = {
     'oriana_cell_totals': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P]),
     'oriana_group_stats': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P, c_int, _I, _P, _P]),
     'oriana_group_stats_max_groups': (_I, []),
+    'oriana_rank_sums': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _I, _I, _I, _P, _I, _I,
+                                 _P, _P, _P, _P, _P]),
+    'oriana_rank_sums_max_groups': (_I, []),
+    'oriana_rank_sums_lds_cap': (_I, []),
+    'oriana_rank_sums_scratch_bytes_for': (_I, [_I, _I]),
     'oriana_tsne_affinities': (c_int, [_P, _I, _I, c_double, _P, _P, _P]),
     'oriana_tsne_affinity_steps': (_I, []),
     'oriana_tsne_attract': (c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),

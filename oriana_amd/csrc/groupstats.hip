@@ -4,6 +4,7 @@
 // is one walk over the two layouts the model already holds, shaped like k_count_stats / k_dn_metric with a cluster axis added.
 // Counts are read as the layouts hold them (rowrec.x float32, the dense block's uint16); every sum is float64.
 #include "common.h"
+#include "counts_check.h"
 #include "dense_tiles.h"
 
 namespace oriana {
@@ -224,17 +225,6 @@ __global__ __launch_bounds__(256) void k_dn_group_stats(const uint16_t *__restri
 }  // namespace oriana
 
 using namespace oriana;
-
-// the layouts of both entries, checked before any HIP call
-static int gs_check_layouts(const oriana_counts *cm, const oriana_dense *dn) {
-    if (!cm || cm->n < 0 || cm->m < 0 || cm->nrb < 0 || cm->ncb < 0 || cm->rslots < 0) return ORIANA_EINVAL;
-    if (cm->nrb * cm->ncb > 0 && cm->rslots > 0 && (!cm->roff || !cm->rslice || !cm->rowrec)) return ORIANA_EINVAL;
-    if (dn) {
-        if (dn->n < 0 || dn->gd < 0 || dn->nct < 0 || (dn->gd & 31)) return ORIANA_EINVAL;
-        if (dn->gd > 0 && dn->n > 0 && (!dn->x || dn->n != cm->n || dn->nct * 32 < dn->n)) return ORIANA_EINVAL;
-    }
-    return 0;
-}
 
 extern "C" int64_t oriana_group_stats_max_groups(void) { return GS_MAX_GROUPS; }
 

@@ -6,10 +6,13 @@ y^2 over them, y the (log-normalised) count; the zeros of X contribute 0 to both
 moments over all cells of the cluster.  Everything here is float64 NumPy on (C, m) arrays and imports without a GPU.  It is
 scanpy's ``rank_genes_groups(method='t-test')``: each cluster against the rest, Welch's statistic.  p-values are left out on
 purpose: the returned scores and degrees of freedom are all a t distribution needs.
+
+method='wilcoxon' (csrc/ranksum.hip, FactorModel.cluster_rank_sums()) has its host half here too: plan_rank_panels cuts the
+genes into the panels the device sorts one at a time, wilcoxon_from_rank_sums turns exact rank sums into the rank-sum statistic.
 """
 import numpy as np
 
-__all__ = ['welch_from_moments', 'rank']
+__all__ = ['welch_from_moments', 'wilcoxon_from_rank_sums', 'plan_rank_panels', 'rank']
 
 
 def _mean_var(s1, s2, n):
@@ -65,6 +68,76 @@ def welch_from_moments(cnt, s1, s2, sizes, log1p=True):
     out = {'scores': scores, 'df': df, 'logfoldchanges': lfc, 'pct_in': cnt / safe_c,
            'pct_out': (cnt.sum(0)[None, :] - cnt) / n_r, 'mean_in': mean_c, 'mean_out': mean_r, 'var_in': var_c,
            'var_out': var_r}
+    for k in out:
+        out[k] = np.where(live[:, None], out[k], np.nan)
+    return out
+
+
+def plan_rank_panels(nnz_packed, gd, budget_records):
+    """Cut the packed genes into the panels oriana_rank_sums takes: contiguous runs of whole gene tiles (32 genes inside the
+    dense block [0, gd), 256 in the sliced part [gd, m), the last one possibly partial), never across gd, each holding at most
+    `budget_records` stored counts -- except a single tile above the budget, which is a panel of its own (the caller sizes its
+    scratch to the largest panel).  nnz_packed : (m,) stored counts per gene in packed order.  Returns [(g0, g1, records)]."""
+    nnz = np.asarray(nnz_packed, dtype=np.int64)
+    m, gd, budget = int(nnz.shape[0]), int(gd), int(budget_records)
+    if nnz.ndim != 1 or gd < 0 or gd > m or gd % 32 or budget < 0:
+        raise ValueError('nnz_packed must be (m,), gd a multiple of 32 within [0, m] and the budget not negative')
+    panels = []
+    for lo, hi, tile in ((0, gd, 32), (gd, m, 256)):
+        g0, held = lo, 0
+        for t0 in range(lo, hi, tile):
+            t1 = min(hi, t0 + tile)
+            rec = int(nnz[t0:t1].sum())
+            if t0 > g0 and held + rec > budget:
+                panels.append((g0, t0, held))
+                g0, held = t0, 0
+            held += rec
+        if hi > g0:
+            panels.append((g0, hi, held))
+    return panels
+
+
+def wilcoxon_from_rank_sums(rank_sum, tie_term, sizes, tie_correct=False):
+    """Each cluster against the rest, from rank sums: scanpy's ``rank_genes_groups(method='wilcoxon')``.
+
+    rank_sum : (C, m) -- per cluster and gene the sum of the ranks of the cluster's cells, the ranks taken over all N = sum sizes
+    cells with ties averaged (half-integers, exact in float64).  tie_term : (m,) integers T_j = sum over the tie runs of
+    t^3 - t.  sizes : (C,) cells per cluster.  With n_c = sizes, n_r = N - n_c, for every non-empty cluster:
+
+        u      = rank_sum - n_c (n_c + 1) / 2,  auc = u / (n_c n_r)
+        sigma^2 = n_c n_r (N + 1) / 12, times (N^3 - N - T_j) / (N^3 - N) with tie_correct (the numerator formed in exact integers)
+        scores = (rank_sum - n_c (N + 1) / 2) / sigma, exactly 0 where sigma is 0 (every cell tied, under the correction)
+
+    Returns a dict of (C, m) float64 arrays 'scores', 'auc', 'u'.  The rows of an empty cluster are NaN.  ValueError for fewer
+    than 2 non-empty clusters (no rest)."""
+    R = np.asarray(rank_sum, dtype=np.float64)
+    sizes = np.asarray(sizes)
+    T = np.asarray(tie_term)
+    if R.ndim != 2 or sizes.shape != (R.shape[0],) or T.shape != (R.shape[1],):
+        raise ValueError('rank_sum must be (C, m), tie_term (m,) and sizes (C,)')
+    if sizes.dtype.kind not in 'iu' or T.dtype.kind not in 'iuO':
+        raise ValueError('sizes and tie_term must be integers')
+    if (sizes < 0).any():
+        raise ValueError('sizes must not be negative')
+    live = sizes > 0
+    if int(live.sum()) < 2:
+        raise ValueError('a marker test needs at least 2 non-empty clusters, got %d' % int(live.sum()))
+    N = int(sizes.sum())
+    n_c = sizes.astype(np.float64)[:, None]
+    n_r = float(N) - n_c
+    pairs = np.where(live[:, None], n_c * n_r, 1.0)             # (an empty cluster's rows are overwritten below)
+    u = R - n_c * (n_c + 1.0) / 2.0
+    var = pairs * float(N + 1)
+    if tie_correct:
+        # N^3 - N - T_j in Python integers, one conversion each: 1 - T / (N^3 - N) would cancel where nearly every cell is tied
+        full = N ** 3 - N
+        left = np.array([float(full - int(t)) for t in T], dtype=np.float64)
+        var = var * (left / float(full))[None, :]
+    sigma = np.sqrt(var / 12.0)
+    num = R - n_c * float(N + 1) / 2.0                          # (half-integers below 2^53: exact)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        scores = np.where(sigma > 0, num / sigma, 0.0)
+    out = {'scores': scores, 'auc': u / pairs, 'u': u}
     for k in out:
         out[k] = np.where(live[:, None], out[k], np.nan)
     return out

@@ -1012,6 +1012,24 @@ class FactorModel:
         exact for integer counts.  Computed once on the device from the layouts the model holds, then cached."""
         return self._cell_totals_device().cpu().numpy()
 
+    def _cluster_labels(self, labels, n_clusters, target_sum, limit):
+        """The checks cluster_gene_stats() and cluster_rank_sums() share, before any launch: (labels as an int64 tensor on the
+        device, C)."""
+        from .. import cluster
+        lab = cluster._label_tensor(labels, self.n, 'labels')
+        if not float(target_sum) > 0.0:
+            raise ValueError('target_sum must be positive')
+        top = int(lab.max()) + 1 if lab.numel() else 0
+        if n_clusters is None:
+            C = cluster._global_max(top, self.device, self.pg)
+        else:
+            C = int(n_clusters)
+            if top > C:
+                raise ValueError('labels must lie within [0, n_clusters = %d), found %d' % (C, top - 1))
+        if C < 1 or C > limit:
+            raise ValueError('the number of clusters must lie within 1..%d, got %d' % (limit, C))
+        return lab.to(self.device), C
+
     def cluster_gene_stats(self, labels, n_clusters=None, normalize=True, target_sum=1e4, log1p=True):
         """Per cluster and gene the moments of the (log-normalised) counts, on the device.
 
@@ -1024,22 +1042,9 @@ class FactorModel:
         over the ranks in one packed all-reduce and every rank returns the same arrays.  ValueError before any launch for labels
         that are not n_local non-negative integers below n_clusters, target_sum <= 0 or more clusters than
         oriana_group_stats_max_groups().  Nothing of the model's state is written."""
-        from .. import cluster, _lib
+        from .. import _lib
         n, m, dev, ct = self.n, self.m, self.device, self.counts
-        lab = cluster._label_tensor(labels, n, 'labels')
-        if not float(target_sum) > 0.0:
-            raise ValueError('target_sum must be positive')
-        top = int(lab.max()) + 1 if lab.numel() else 0
-        if n_clusters is None:
-            C = cluster._global_max(top, dev, self.pg)
-        else:
-            C = int(n_clusters)
-            if top > C:
-                raise ValueError('labels must lie within [0, n_clusters = %d), found %d' % (C, top - 1))
-        limit = int(_lib.load().oriana_group_stats_max_groups())
-        if C < 1 or C > limit:
-            raise ValueError('the number of clusters must lie within 1..%d, got %d' % (limit, C))
-        lab = lab.to(dev)
+        lab, C = self._cluster_labels(labels, n_clusters, target_sum, int(_lib.load().oriana_group_stats_max_groups()))
         scale = None
         if normalize:
             tot = self._cell_totals_device()
@@ -1055,23 +1060,106 @@ class FactorModel:
         st = host[:3 * C * m].reshape(3, C, m)
         return {'n_expressing': st[0], 'sum': st[1], 'sumsq': st[2], 'sizes': np.rint(host[3 * C * m:]).astype(np.int64)}
 
-    def marker_genes(self, labels, n_top=50, **stats_kw):
-        """The genes that distinguish each cluster of a labelling of the cells: Welch's t statistic of every cluster against the
-        rest on the log-normalised counts -- scanpy's ``rank_genes_groups(method='t-test')`` without a host copy of X.
+    def cluster_rank_sums(self, labels, n_clusters=None, normalize=True, target_sum=1e4, scratch_bytes=1 << 30, sort_cap=None):
+        """Per cluster and gene the sum of the ranks of the cluster's cells, the ranks taken per gene over ALL cells on the
+        normalised counts v_ij = x_ij * scale_i in float64 (normalize=False: on x_ij), ties averaged as
+        ``scipy.stats.rankdata(method='average')`` has them: what a Wilcoxon rank-sum test takes (csrc/ranksum.hip).
+
+        labels, n_clusters, normalize, target_sum : as cluster_gene_stats().  The scale is formed on the host, target_sum /
+        cell_totals() in float64 NumPy (0 for a cell without counts); the device forms one float64 product per stored count and
+        sorts its bit pattern, so a tie is a tie of those float64 values.  log1p is monotone and plays no part.  The stored
+        counts of a gene are sorted panel by panel (markers.plan_rank_panels): scratch_bytes bounds the records of a panel at
+        24 bytes each (a single gene tile above it is still taken, with a scratch of its own size), sort_cap the longest gene
+        sorted inside LDS (default and largest: oriana_rank_sums_lds_cap()).  Neither changes a bit of the result.
+
+        Returns NumPy arrays in the caller's gene order: 'rank_sum' (C, m) float64, exact half-integers; 'tie_term' (m,) int64,
+        sum over the tie runs of t^3 - t, the run of the zeros included; 'n_expressing' (C, m) float64; 'sizes' (C,) int64.
+        ValueError before any launch as cluster_gene_stats() raises it, and for a scratch_bytes or sort_cap out of range; a model
+        sharded over more than one rank raises NotImplementedError before any launch or collective (rank sums do not add up
+        over shards of cells).  Nothing of the model's state is written."""
+        from .. import markers, _lib
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('cluster_rank_sums() is not implemented for a model sharded over more than one rank')
+        n, m, dev, ct = self.n, self.m, self.device, self.counts
+        lib = _lib.load()
+        lab, C = self._cluster_labels(labels, n_clusters, target_sum, int(lib.oriana_rank_sums_max_groups()))
+        cap = int(lib.oriana_rank_sums_lds_cap())
+        if sort_cap is not None and not 1 <= int(sort_cap) <= cap:
+            raise ValueError('sort_cap must lie within 1..%d, got %d' % (cap, int(sort_cap)))
+        sort_cap = 0 if sort_cap is None else int(sort_cap)     # (0: the library's default)
+        if int(scratch_bytes) < 0:
+            raise ValueError('scratch_bytes must not be negative')
+        if n >= 1 << 21:
+            raise ValueError('cluster_rank_sums() takes fewer than 2^21 cells, got %d' % n)
+        scale = None
+        if normalize:
+            tot = self.cell_totals()
+            with np.errstate(divide='ignore'):
+                scale = torch.as_tensor(np.where(tot > 0, float(target_sum) / tot, 0.0), device=dev).contiguous()
+        lab32 = lab.to(torch.int32).contiguous()
+        perm = ct.col_perm.cpu().numpy() if ct.col_perm is not None else np.arange(m)
+        nnz_packed = np.rint(self._count_constants()[1].cpu().numpy()).astype(np.int64)[perm]
+        panels = markers.plan_rank_panels(nnz_packed, ct.gd, int(scratch_bytes) // 24)
+        records = max([p[2] for p in panels] + [0])
+        by = int(lib.oriana_rank_sums_scratch_bytes_for(records, max([p[1] - p[0] for p in panels] + [0])))
+        scratch = torch.empty(max(by, 16), dtype=torch.uint8, device=dev)
+        out = torch.zeros((2 * C + 1) * m, dtype=torch.int64, device=dev)
+        pos2, cnt, ties = out[:C * m], out[C * m:2 * C * m], out[2 * C * m:]
+        overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        for g0, g1, _ in panels:
+            call('oriana_rank_sums', ct.sparse_struct, ct.dense.c_struct if ct.dense is not None else None, ptr(ct.row_perm),
+                 ptr(ct.col_perm), ptr(lab32), ptr(scale), C, g0, g1, ptr(scratch), records, sort_cap, ptr(pos2), ptr(cnt),
+                 ptr(ties), ptr(overflow), stream_ptr())
+        sizes = torch.bincount(lab, minlength=C).cpu().numpy().astype(np.int64)
+        host = out.cpu().numpy()
+        if int(overflow.cpu()[0]) != 0:
+            raise _lib.OrianaHipError('oriana_rank_sums: a panel holds more stored counts than the per-gene counts of the model say')
+        pos2, cnt, ties = host[:C * m].reshape(C, m), host[C * m:2 * C * m].reshape(C, m), host[2 * C * m:]
+        # twice the rank sum in integers (below 2^43): the cluster's zeros tie at (z + 1) / 2, its stored counts stand z positions up
+        z = n - cnt.sum(0)
+        twice = (sizes[:, None] - cnt) * (z + 1)[None, :] + 2 * cnt * z[None, :] + pos2
+        return {'rank_sum': twice.astype(np.float64) / 2.0, 'tie_term': ties + z * z * z - z,
+                'n_expressing': cnt.astype(np.float64), 'sizes': sizes}
+
+    def marker_genes(self, labels, n_top=50, method='t-test', tie_correct=False, **stats_kw):
+        """The genes that distinguish each cluster of a labelling of the cells, every cluster against the rest, without a host
+        copy of X.  method='t-test': Welch's t statistic on the log-normalised counts, scanpy's
+        ``rank_genes_groups(method='t-test')``; method='wilcoxon': the rank-sum statistic on the normalised counts, its
+        ``method='wilcoxon'`` (tie_correct as there; ranks are taken on the float64 values before log1p: cluster_rank_sums()).
 
         labels and the keywords n_clusters, normalize, target_sum, log1p: as cluster_gene_stats().  Returns its arrays plus,
         per cluster and gene ((C, m) float64, caller's gene order; NaN rows for an id without cells): 'scores' (exactly 0 for a
         gene without variance on both sides), 'df' (Welch-Satterthwaite, NaN where undefined), 'logfoldchanges', 'pct_in',
         'pct_out' (markers.welch_from_moments), and 'genes', a (C, min(n_top, m)) int64 array: per cluster the gene indices by
-        decreasing score, ties by index (markers.rank).  p-values are not computed: scores and df are what any t distribution
-        takes.  ValueError for fewer than 2 non-empty clusters.  Nothing of the model's state is written."""
+        decreasing score, ties by index (markers.rank).  With 'wilcoxon' (which also takes scratch_bytes and sort_cap of
+        cluster_rank_sums()) 'scores' is the rank-sum z score (markers.wilcoxon_from_rank_sums; exactly 0 where every cell is
+        tied under the correction), 'auc' = U / (n_c n_r), 'rank_sum' and 'tie_term' come along and there is no 'df'.  p-values
+        are not computed.  ValueError for fewer than 2 non-empty clusters or another method; 'wilcoxon' on a model sharded over
+        more than one rank raises NotImplementedError.  Nothing of the model's state is written."""
         from .. import markers
         if int(n_top) < 0:
             raise ValueError('n_top must not be negative')
+        if method not in ('t-test', 'wilcoxon'):
+            raise ValueError("method must be 't-test' or 'wilcoxon', got %r" % (method,))
+        rank_kw = {}
+        if method == 'wilcoxon':
+            if odist.world_size(self.pg) > 1:
+                raise NotImplementedError("marker_genes(method='wilcoxon') is not implemented for a model sharded over more "
+                                          "than one rank")
+            rank_kw = {k: stats_kw.pop(k) for k in ('scratch_bytes', 'sort_cap') if k in stats_kw}
         out = self.cluster_gene_stats(labels, **stats_kw)
         w = markers.welch_from_moments(out['n_expressing'], out['sum'], out['sumsq'], out['sizes'],
                                        log1p=bool(stats_kw.get('log1p', True)))
-        for k in ('scores', 'df', 'logfoldchanges', 'pct_in', 'pct_out'):
+        if method == 'wilcoxon':
+            rank_kw.update({k: stats_kw[k] for k in ('normalize', 'target_sum') if k in stats_kw})
+            rs = self.cluster_rank_sums(labels, n_clusters=out['sizes'].shape[0], **rank_kw)
+            r = markers.wilcoxon_from_rank_sums(rs['rank_sum'], rs['tie_term'], rs['sizes'], tie_correct=bool(tie_correct))
+            out.update(rank_sum=rs['rank_sum'], tie_term=rs['tie_term'], auc=r['auc'])
+            w = dict(w, scores=r['scores'])
+            keys = ('scores', 'logfoldchanges', 'pct_in', 'pct_out')
+        else:
+            keys = ('scores', 'df', 'logfoldchanges', 'pct_in', 'pct_out')
+        for k in keys:
             out[k] = w[k]
         out['genes'] = markers.rank(w['scores'], n_top)
         return out
