@@ -1134,6 +1134,51 @@ int oriana_tsne_repulse(const float *Q, int64_t nq, const float *Y, int64_t n, d
 /* Bytes of scratch of such a call (negative: the argument error the call would return). */
 int64_t oriana_tsne_repulse_scratch_bytes_for(int64_t nq, int64_t n, int64_t blocks);
 
+/* ---- communities on the neighbour graph (csrc/community.hip, oriana_amd/cluster.py: snn_graph, louvain; no
+ * counterpart in the reference) --------------------------------------------------------------------------------------------------
+ * A graph is symmetric CSR: row_ptr (n + 1) int64, cols int32 ascending inside a row, weights int64 >= 0.
+ * oriana_snn_weights : indices (n, k) int32 contiguous as oriana_knn wrote it.  Nc(i) = the entries of row i inside [0, n) other
+ *   than i (no entry twice: the caller's check), and i itself.  For every stored entry e of row i with column j,
+ *   weights[e] = |Nc(i) & Nc(j)|, an integer whatever the enumeration; a column outside [0, n) gets 0 and addresses nothing.  n < 0
+ *   or beyond 2^31 - 1, k < 1 or beyond oriana_knn_max_neighbors(1), a NULL indices / row_ptr with n > 0 -> ORIANA_EINVAL before
+ *   any HIP call; n = 0 is a no-op.
+ * oriana_louvain_sweep : ONE synchronous local-moving sweep of Louvain's method.  deg[i] = the sum of the weights of row i (a self
+ *   entry, present at aggregated levels, included), two_m = sum deg with two_m^2 < 2^63; the state is comm (n) int32 within
+ *   [0, n), tot[c] = sum of deg over community c (int64), size[c] = its nodes (int32).  For node i with a = comm[i] the
+ *   candidates are a and comm[j] of every stored j != i;
+ *     k_ic = sum of w_ij over j != i with comm[j] = c (the self entry never counts; k_ia may be 0)
+ *     tot'_c = tot[c] - [c = a] deg_i
+ *     g(c) = __dsub_rn((double)(two_m * k_ic), __dmul_rn(resolution, (double)(deg_i * tot'_c)))
+ *   both integer products exact in int64, each converted once, the product and the difference rounded once each.  c* = the
+ *   candidate of the largest g, ties to the smallest id; i moves to c* iff c* != a and g(c*) > g(a); where size[a] = 1 and
+ *   size[c*] = 1 the move is taken only when c* < a.  Every decision reads the OLD comm, tot and size: comm_new (n) and moved[0],
+ *   the number of nodes with comm_new != comm, are all that is written, and they are the same bits for every `blocks`,
+ *   row_cap and scratch that holds the tables.  An entry of comm or cols outside [0, n) addresses nothing.
+ *   row_cap   rows of at most row_cap entries are served by one wave with a table in LDS; 0 = oriana_louvain_row_cap() = 128,
+ *             which is also the largest value.  The longer rows are the caller's list: long_rows (n_long) int32, exactly the
+ *             rows with more than row_cap entries, and long_off (n_long + 1) int64, where the table of long row q starts in the
+ *             scratch, in slots; the table of a row of len entries has T(len) = max(64, the least power of two >= 2 len) slots,
+ *             and long_off[n_long] is their sum.  A listed row that is not long, or whose table would leave the scratch, is
+ *             skipped.
+ *   scratch   scratch_bytes bytes, at least 16, 16-byte aligned, contents undefined on entry and exit: a 16-byte header, then 16
+ *             bytes per slot; oriana_louvain_sweep_scratch_bytes_for(long_off[n_long]) bytes hold every table.  If they do not
+ *             fit, overflow[0] is set to 1 and nothing else is written outside the scratch; otherwise overflow is not written
+ *             (the caller zeroes it).
+ *   `blocks`  work-groups of each launch (0: sized from the device).
+ * ORIANA_EINVAL before any HIP call for n < 0 or beyond 2^31 - 1, two_m < 0 or two_m^2 >= 2^63, a resolution that is not finite
+ * and positive, row_cap outside [0, oriana_louvain_row_cap()], negative blocks or n_long, n_long > n, scratch_bytes < 16, a NULL
+ * or misaligned scratch, a NULL moved / overflow, with n > 0 a NULL row_ptr / deg / comm / tot / size / comm_new, with n_long > 0
+ * a NULL long_rows / long_off. */
+int oriana_snn_weights(const int32_t *indices, int64_t n, int64_t k, const int64_t *row_ptr, const int32_t *cols, int64_t *weights,
+                       void *stream);
+int64_t oriana_louvain_row_cap(void);
+/* (negative: ORIANA_EINVAL for a negative argument) */
+int64_t oriana_louvain_sweep_scratch_bytes_for(int64_t long_slots);
+int oriana_louvain_sweep(int64_t n, const int64_t *row_ptr, const int32_t *cols, const int64_t *weights, const int64_t *deg,
+                         int64_t two_m, double resolution, const int32_t *comm, const int64_t *tot, const int32_t *size,
+                         int64_t row_cap, const int32_t *long_rows, const int64_t *long_off, int64_t n_long, void *scratch,
+                         int64_t scratch_bytes, int32_t *comm_new, int64_t *moved, int32_t *overflow, int64_t blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,10 @@ _SIGS = {
     'oriana_tsne_attract': (c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),
     'oriana_tsne_repulse': (c_int, [_P, _I, _P, _I, _P, _P, c_int, _P, _I, _P]),
     'oriana_tsne_repulse_scratch_bytes_for': (_I, [_I, _I, _I]),
+    'oriana_snn_weights': (c_int, [_P, _I, _I, _P, _P, _P, _P]),
+    'oriana_louvain_row_cap': (_I, []),
+    'oriana_louvain_sweep_scratch_bytes_for': (_I, [_I]),
+    'oriana_louvain_sweep': (c_int, [_I, _P, _P, _P, _P, _I, c_double, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

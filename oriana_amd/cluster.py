@@ -12,7 +12,11 @@ all Euclidean distances of all pairs, added per cluster in float64, no distance 
 Rand index of two labellings.  DESIGN.md section 5k.
 
 tsne() is the exact t-SNE layout of the same rows (csrc/tsne.hip): the neighbour graph of knn(), perplexity-calibrated affinities,
-and a gradient whose repulsive term is all n^2 pairs by brute force -- no tree, no sampling, deterministic.  DESIGN.md section 5m."""
+and a gradient whose repulsive term is all n^2 pairs by brute force -- no tree, no sampling, deterministic.  DESIGN.md section 5m.
+
+louvain() is a deterministic Louvain clustering of the graph snn_graph() forms from the neighbour lists of knn()
+(csrc/community.hip): integer weights, every node of a sweep decides from the old state, so a labelling is a function of the
+graph alone and a NumPy restatement matches it label for label.  DESIGN.md section 5o."""
 import math
 
 import numpy as np
@@ -26,7 +30,8 @@ __all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows
            'knn', 'knn_plan', 'knn_step', 'max_neighbors',
            'silhouette', 'silhouette_plan', 'silhouette_from_sums', 'distance_sums', 'max_clusters', 'adjusted_rand',
            'tsne', 'tsne_plan', 'tsne_default_neighbors', 'tsne_affinities', 'tsne_joint', 'tsne_attract', 'tsne_repulse',
-           'tsne_gradient', 'tsne_pca_init']
+           'tsne_gradient', 'tsne_pca_init',
+           'snn_graph', 'louvain', 'louvain_sweep', 'louvain_plan', 'louvain_row_cap', 'modularity']
 
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
@@ -1063,3 +1068,281 @@ def tsne(Y, perplexity=20.0, n_neighbors=None, n_iter=750, early_exaggeration=12
     _tsne_descend(P, y, n_iter - exaggeration_iter, 1.0, 0.8, lr, plan_kw, trace, check_every, exaggeration_iter)
     _, kl = tsne_gradient(P, y.to(torch.float32), 1.0, **plan_kw)
     return {'embedding': y, 'kl': float(kl), 'kl_trace': trace, 'n_iter': n_iter, 'beta': beta, 'n_neighbors': k}
+
+
+# ---- communities on the neighbour graph (csrc/community.hip) -----------------------------------------------------
+LOUVAIN_MAX_2M = 3037000499       # floor(sqrt(2^63 - 1)): (2m)^2 < 2^63, so every product of a sweep is exact in int64
+
+
+def louvain_row_cap():
+    """The longest row whose table oriana_louvain_sweep keeps in LDS, and the largest `row_cap`."""
+    return int(_lib.load().oriana_louvain_row_cap())
+
+
+def _csr_pointers(rows, n):
+    crow = torch.zeros(n + 1, dtype=torch.int64, device=rows.device)
+    if n:
+        crow[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    return crow
+
+
+def snn_graph(indices, weights='snn'):
+    """The symmetric weighted graph of the neighbour lists `indices`, an (n, k) int32 tensor as knn() / cell_neighbors() return it.
+    N(i) = the entries of row i inside [0, n) other than i (anything else, the -1 padding included, is skipped); {i, j} is an edge
+    iff j is in N(i) or i is in N(j).  weights : 'snn' -- w_ij = |Nc(i) & Nc(j)| with Nc(i) = N(i) and i itself, the
+    shared-neighbour count (oriana_snn_weights; needs a device tensor and k <= max_neighbors(1)); 'count' -- w_ij = [j in N(i)] +
+    [i in N(j)], formed by torch on the tensor's device.  Returns {'crow': (n + 1) int64, 'col': (nnz) int32 ascending inside a
+    row, 'weight': (nnz) int64, 'n': n}, no self entries.  ValueError for a wrong dtype or rank and (one device sort, one host
+    read) for a row that holds a valid entry twice."""
+    if not isinstance(indices, torch.Tensor) or indices.dim() != 2 or indices.dtype != torch.int32:
+        raise ValueError('indices must be an (n, k) int32 torch tensor')
+    if weights not in ('snn', 'count'):
+        raise ValueError("weights must be 'snn' or 'count'")
+    n, k = int(indices.shape[0]), int(indices.shape[1])
+    if k < 1:
+        raise ValueError('indices must hold at least one column')
+    if weights == 'snn':
+        if k > max_neighbors(1):
+            raise ValueError('%d neighbours per row exceed the %d served' % (k, max_neighbors(1)))
+        if not indices.is_cuda:
+            raise ValueError("weights='snn' needs a device tensor")
+    dev = indices.device
+    idx = indices.to(torch.int64)
+    me = torch.arange(n, device=dev, dtype=torch.int64)[:, None]
+    valid = (idx >= 0) & (idx < n) & (idx != me)
+    srt = torch.sort(torch.where(valid, idx, torch.full_like(idx, -1)), dim=1).values
+    if n and k > 1 and bool(((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any()):
+        raise ValueError('a row of indices holds a neighbour twice')
+    r = me.expand(n, k)[valid]
+    c = idx[valid]
+    key, cnt = torch.unique(torch.cat([r * n + c, c * n + r]), return_counts=True)        # (sorted: rows, then columns, ascend)
+    rows = torch.div(key, max(n, 1), rounding_mode='floor')
+    col = (key - rows * n).to(torch.int32).contiguous()
+    crow = _csr_pointers(rows, n)
+    if weights == 'count':
+        w = cnt.to(torch.int64).contiguous()
+    else:
+        w = torch.empty(int(col.numel()), dtype=torch.int64, device=dev)
+        ind = indices.contiguous()
+        nnz = int(col.numel())
+        call('oriana_snn_weights', ptr(ind) if n else None, n, k, ptr(crow), ptr(col) if nnz else None, ptr(w) if nnz else None,
+             stream_ptr())
+    return {'crow': crow, 'col': col, 'weight': w, 'n': n}
+
+
+def _graph_rows(crow, n):
+    return torch.repeat_interleave(torch.arange(n, device=crow.device, dtype=torch.int64), crow[1:] - crow[:-1])
+
+
+def _check_graph(graph):
+    """The validated graph: (crow, col, weight, n, rows, deg, two_m).  One torch check (one host read) for the pointers, the
+    order inside the rows, the symmetry of pattern and weights and the sign of the weights."""
+    if not isinstance(graph, dict) or not all(a in graph for a in ('crow', 'col', 'weight', 'n')):
+        raise ValueError("graph must be a dict with 'crow', 'col', 'weight' and 'n', as snn_graph() returns it")
+    crow, col, w, n = graph['crow'], graph['col'], graph['weight'], int(graph['n'])
+    if not all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in (crow, col, w)):
+        raise ValueError('crow, col and weight must be 1-D torch tensors')
+    if crow.dtype != torch.int64 or col.dtype != torch.int32 or w.dtype != torch.int64:
+        raise ValueError('crow must be int64, col int32 and weight int64')
+    if n < 0 or int(crow.numel()) != n + 1 or col.numel() != w.numel():
+        raise ValueError('crow must hold n + 1 pointers, col and weight one entry per stored pair')
+    if not (crow.device == col.device == w.device):
+        raise ValueError('crow, col and weight must live on one device')
+    if not (crow.is_contiguous() and col.is_contiguous() and w.is_contiguous()):
+        raise ValueError('crow, col and weight must be contiguous')
+    nnz = int(col.numel())
+    lens = crow[1:] - crow[:-1]
+    head = torch.stack([crow[0] != 0, crow[-1] != nnz, (lens < 0).any()]).cpu()
+    if bool(head.any()):
+        raise ValueError('crow must ascend from 0 to the number of stored entries')
+    rows = _graph_rows(crow, n)
+    c64 = col.to(torch.int64)
+    key = rows * n + c64
+    back = c64 * n + rows
+    order = torch.argsort(back)
+    flags = [((c64 < 0) | (c64 >= n)).any(), (key[1:] <= key[:-1]).any(), (back[order] != key).any(), (w[order] != w).any(),
+             (w < 0).any()]
+    deg = torch.zeros(n, dtype=torch.int64, device=w.device).index_add_(0, rows, w) if nnz else \
+        torch.zeros(n, dtype=torch.int64, device=w.device)
+    bad = torch.stack(flags).cpu() if nnz else torch.zeros(5, dtype=torch.bool)
+    if bool(bad[0]):
+        raise ValueError('a column lies outside [0, n)')
+    if bool(bad[1]):
+        raise ValueError('the columns of a row must ascend strictly (an unsorted graph)')
+    if bool(bad[2]) or bool(bad[3]):
+        raise ValueError('the graph must be symmetric in pattern and weights (an asymmetric graph)')
+    if bool(bad[4]):
+        raise ValueError('the weights must not be negative')
+    two_m = int(w.to(torch.float64).sum()) if nnz else 0           # (a first look that cannot wrap)
+    if two_m > LOUVAIN_MAX_2M:
+        raise ValueError('the weights sum to 2m = %d: (2m)^2 must stay below 2^63 (2m <= %d)' % (two_m, LOUVAIN_MAX_2M))
+    two_m = int(deg.sum())
+    return crow, col, w, n, rows, deg, two_m
+
+
+def _check_resolution(resolution):
+    resolution = float(resolution)
+    if not (0.0 < resolution < float('inf')):
+        raise ValueError('resolution must be finite and positive')
+    return resolution
+
+
+def _modularity_value(I, S, two_m, resolution):
+    """Q = I / 2m - resolution S / (2m)^2 in float64 from the exact integers (0.0 for a graph without weight)."""
+    if two_m == 0:
+        return 0.0
+    return I / two_m - resolution * float(S) / float(two_m * two_m)
+
+
+def _partition_sums(rows, col, w, deg, comm, n):
+    """Of a labelling comm (n) with ids in [0, n): tot (n) int64, size (n) int32, I and S as int64 device scalars."""
+    c = comm.to(torch.int64)
+    tot = torch.zeros(n, dtype=torch.int64, device=deg.device).index_add_(0, c, deg)
+    size = torch.bincount(c, minlength=n).to(torch.int32)
+    inside = torch.where(c[rows] == c[col.to(torch.int64)], w, torch.zeros_like(w)).sum()
+    return tot, size, inside, (tot * tot).sum()
+
+
+def modularity(graph, labels, resolution=1.0):
+    """Newman's modularity with resolution, Q = I / 2m - resolution S / (2m)^2, of the labelling `labels` (integer ids >= 0, one
+    per node) on a graph as snn_graph() returns it: I = the weight of the stored entries inside a community (self entries
+    included), S = the sum of the squared community degrees, both exact integers formed by torch on the graph's device; the float64
+    value is formed on the host from the two."""
+    crow, col, w, n, rows, deg, two_m = _check_graph(graph)
+    resolution = _check_resolution(resolution)
+    lab = _label_tensor(labels, n, 'labels').to(crow.device)
+    _, inv = torch.unique(lab, return_inverse=True)
+    _, _, inside, squares = _partition_sums(rows, col, w, deg, inv, n)
+    return _modularity_value(int(inside), int(squares), two_m, resolution)
+
+
+def louvain_plan(graph, row_cap=None):
+    """Which rows of the graph oriana_louvain_sweep serves through tables in the scratch, and where: {'row_cap', 'long_rows'
+    (int32, the rows with more than row_cap entries), 'long_off' (int64, the first slot of each row's table and their total),
+    'slots', 'scratch_bytes'}.  A row of len entries takes max(64, the least power of two >= 2 len) slots.  One host read."""
+    crow = graph['crow']
+    cap = louvain_row_cap() if row_cap is None else int(row_cap)
+    if not 1 <= cap <= louvain_row_cap():
+        raise ValueError('row_cap must lie within 1..%d' % louvain_row_cap())
+    lens = crow[1:] - crow[:-1]
+    long_rows = torch.nonzero(lens > cap).reshape(-1)
+    L = lens[long_rows]
+    T = torch.full_like(L, 64)
+    for _ in range(32):
+        T = torch.where(T < 2 * L, T * 2, T)
+    off = torch.zeros(int(L.numel()) + 1, dtype=torch.int64, device=crow.device)
+    off[1:] = torch.cumsum(T, 0)
+    slots = int(off[-1])
+    return {'row_cap': cap, 'long_rows': long_rows.to(torch.int32).contiguous(), 'long_off': off, 'slots': slots,
+            'scratch_bytes': _scratch_bytes('oriana_louvain_sweep_scratch_bytes_for', slots)}
+
+
+def louvain_sweep(graph, deg, two_m, comm, tot, size, resolution=1.0, plan=None, row_cap=None, blocks=0, scratch=None):
+    """One oriana_louvain_sweep call, nothing checked beyond dtypes and sizes and nothing read on the host: graph as snn_graph()
+    returns it (at aggregated levels with self entries), deg (n) int64 the row sums of the weights, two_m their sum (an int), the
+    state comm (n) int32, tot (n) int64, size (n) int32.  Every node decides from this state (include/oriana_hip.h states the
+    rule).  plan : louvain_plan(graph, row_cap), formed here if absent.  scratch : a uint8 device tensor; one that is too small for
+    the plan sets 'overflow' and leaves everything else as it was.  Returns {'comm': (n) int32 the proposed labelling, 'moved':
+    (1,) int64 the nodes that change, 'overflow': (1,) int32}, device tensors."""
+    crow, col, w, n = graph['crow'], graph['col'], graph['weight'], int(graph['n'])
+    for t, dt, m, what in ((crow, torch.int64, n + 1, 'crow'), (col, torch.int32, None, 'col'), (w, torch.int64, int(col.numel()), 'weight'),
+                           (deg, torch.int64, n, 'deg'), (comm, torch.int32, n, 'comm'), (tot, torch.int64, n, 'tot'),
+                           (size, torch.int32, n, 'size')):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or (m is not None and int(t.numel()) != m) \
+                or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError('%s must be a contiguous 1-D %s device tensor%s' % (what, dt, '' if m is None else ' of %d entries' % m))
+    if plan is None:
+        plan = louvain_plan(graph, row_cap)
+    dev = crow.device
+    if scratch is None:
+        scratch = torch.empty(plan['scratch_bytes'], dtype=torch.uint8, device=dev)
+    out = {'comm': torch.empty(n, dtype=torch.int32, device=dev), 'moved': torch.zeros(1, dtype=torch.int64, device=dev),
+           'overflow': torch.zeros(1, dtype=torch.int32, device=dev)}
+    nnz, nlong = int(col.numel()), int(plan['long_rows'].numel())
+    call('oriana_louvain_sweep', n, ptr(crow), ptr(col) if nnz else None, ptr(w) if nnz else None, ptr(deg) if n else None,
+         int(two_m), float(resolution), ptr(comm) if n else None, ptr(tot) if n else None, ptr(size) if n else None,
+         int(plan['row_cap']), ptr(plan['long_rows']) if nlong else None, ptr(plan['long_off']) if nlong else None, nlong,
+         ptr(scratch), int(scratch.numel() * scratch.element_size()), ptr(out['comm']) if n else None, ptr(out['moved']),
+         ptr(out['overflow']), int(blocks), stream_ptr())
+    return out
+
+
+def louvain(graph, resolution=1.0, max_sweeps=64, max_levels=32, row_cap=None, blocks=0, scratch=None, pg=None):
+    """Deterministic Louvain communities of a graph as snn_graph() returns it (symmetric CSR, integer weights >= 0).
+
+    A level starts from singletons.  A sweep (oriana_louvain_sweep) lets every node choose, from the state before the sweep, the
+    neighbouring community of the largest gain, ties to the smallest id, with the swap guard for two singletons.  If no node moves
+    the level ends; otherwise the sweep is accepted iff float64(2m (I_new - I)) > resolution float64(S_new - S), the exact integers
+    of modularity(), that is iff the modularity rises; a rejected sweep is discarded and ends the level, and so do `max_sweeps`
+    accepted sweeps (reported, not an error).  Between levels the communities are renumbered by ascending id and become the nodes
+    of the coalesced graph, the weight inside a community its self entry.  The run ends when a level accepts no sweep or merges
+    nothing, or after `max_levels`.  The final labels are renumbered by descending size, ties by the smallest member: 0 is the
+    largest community.  Everything but the sweep is integer torch on the device; per sweep the host reads one small tensor (the
+    moved count, I, S and the overflow flag), per level the plan's slot count and the level's own integers.
+
+    row_cap, blocks : of louvain_sweep(); they change no bit.  scratch : a uint8 device tensor for the long rows' tables.
+    Returns {'labels': (n,) int32 device tensor, 'n_communities', 'modularity' (float), 'levels': a list of {'nodes', 'sweeps'
+    (accepted), 'moved' (per accepted sweep), 'modularity' (at the level's end), 'hit_max_sweeps'}}.
+    ValueError before any launch for wrong dtypes, ranks or devices, a graph that is asymmetric or unsorted, negative weights, a
+    resolution that is not finite and positive, or (2m)^2 >= 2^63; NotImplementedError for a process group of more than one
+    rank."""
+    if odist.world_size(pg) > 1:
+        raise NotImplementedError('louvain() is not implemented for a process group of more than one rank: gather the graph first')
+    resolution = _check_resolution(resolution)
+    max_sweeps, max_levels, blocks = int(max_sweeps), int(max_levels), int(blocks)
+    if max_sweeps < 1 or max_levels < 1 or blocks < 0:
+        raise ValueError('max_sweeps >= 1, max_levels >= 1 and blocks >= 0 are required')
+    crow, col, w, n, rows, deg, two_m = _check_graph(graph)
+    if row_cap is not None and not 1 <= int(row_cap) <= louvain_row_cap():
+        raise ValueError('row_cap must lie within 1..%d' % louvain_row_cap())
+    if not crow.is_cuda:
+        raise ValueError('the graph must live on the device')
+    dev = crow.device
+    n0 = n
+    labels = torch.arange(n0, device=dev, dtype=torch.int64)
+    levels = []
+    for _ in range(max_levels):
+        g = {'crow': crow, 'col': col, 'weight': w, 'n': n}
+        comm = torch.arange(n, device=dev, dtype=torch.int32)
+        tot, size, inside, squares = _partition_sums(rows, col, w, deg, comm, n)
+        I, S = int(inside), int(squares)
+        plan = louvain_plan(g, row_cap)
+        moved, hit = [], False
+        for _ in range(max_sweeps):
+            out = louvain_sweep(g, deg, two_m, comm, tot, size, resolution, plan=plan, blocks=blocks, scratch=scratch)
+            tot_n, size_n, inside_n, squares_n = _partition_sums(rows, col, w, deg, out['comm'], n)
+            mv, I_n, S_n, over = (int(v) for v in torch.stack([out['moved'][0], inside_n, squares_n,
+                                                               out['overflow'][0].to(torch.int64)]).cpu())
+            if over:
+                raise _lib.OrianaHipError('the scratch is too small for the tables of the long rows (%d bytes needed)'
+                                          % plan['scratch_bytes'])
+            if mv == 0 or not float(two_m * (I_n - I)) > resolution * float(S_n - S):
+                break
+            comm, tot, size, I, S = out['comm'], tot_n, size_n, I_n, S_n
+            moved.append(mv)
+        else:
+            hit = True
+        levels.append({'nodes': n, 'sweeps': len(moved), 'moved': moved, 'modularity': _modularity_value(I, S, two_m, resolution),
+                       'hit_max_sweeps': hit})
+        if not moved:
+            break
+        uniq, inv = torch.unique(comm.to(torch.int64), return_inverse=True)
+        C = int(uniq.numel())
+        labels = inv[labels]
+        if C == n:
+            break
+        key, kinv = torch.unique(inv[rows] * C + inv[col.to(torch.int64)], return_inverse=True)
+        w = torch.zeros(int(key.numel()), dtype=torch.int64, device=dev).index_add_(0, kinv, w)
+        rows = torch.div(key, C, rounding_mode='floor')
+        col = (key - rows * C).to(torch.int32).contiguous()
+        n = C
+        crow = _csr_pointers(rows, n)
+        deg = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, rows, w)
+    _, labels = torch.unique(labels, return_inverse=True)
+    C = int(labels.max()) + 1 if n0 else 0
+    sizes = torch.bincount(labels, minlength=C)
+    first = torch.full((C,), n0, dtype=torch.int64, device=dev).scatter_reduce_(0, labels, torch.arange(n0, device=dev), 'amin')
+    order = torch.argsort((n0 - sizes) * (n0 + 1) + first)
+    rank = torch.empty(C, dtype=torch.int64, device=dev)
+    rank[order] = torch.arange(C, device=dev)
+    return {'labels': rank[labels].to(torch.int32), 'n_communities': C, 'modularity': levels[-1]['modularity'], 'levels': levels}

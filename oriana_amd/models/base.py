@@ -991,6 +991,37 @@ class FactorModel:
         out['factors'] = cols
         return out
 
+    def cell_communities(self, n_neighbors=15, resolution=1.0, weights='snn', features='log_mean', factors=None, graph=None,
+                         **louvain_kw):
+        """Graph communities of the cells: deterministic Louvain (cluster.louvain; its keywords max_sweeps, max_levels, row_cap,
+        blocks and scratch pass through) on the shared-neighbour graph (cluster.snn_graph, `weights` 'snn' or 'count') of the
+        n_neighbors nearest neighbours on the feature matrix cluster_cells() uses.  No number of clusters is asked for:
+        `resolution` sets the grain.
+
+        graph : ``(indices, sq_distances)`` as cell_neighbors() returned them on the same features, to spare the search (then
+        n_neighbors is the width of `indices`).  Returns the dict of cluster.louvain: 'labels' ((n,) int32 device tensor, 0 the
+        largest community; it feeds cell_silhouette() and marker_genes() as it is), 'n_communities', 'modularity', 'levels'.  A
+        model sharded over more than one rank raises NotImplementedError.  Nothing of the model's state is written."""
+        from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in louvain_kw:
+            raise ValueError('cell_communities() uses the process group of the model')
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('cell_communities() is not implemented for a model sharded over more than one rank')
+        if weights not in ('snn', 'count'):
+            raise ValueError("weights must be 'snn' or 'count'")
+        if graph is None:
+            if int(n_neighbors) < 1:
+                raise ValueError('n_neighbors must be at least 1')
+            F = self._cell_features(features, cols)
+            gi = cluster.knn(F, int(n_neighbors), pg=self.pg)['indices']
+        else:
+            gi = graph[0]
+            if getattr(gi, 'ndim', 0) != 2 or int(gi.shape[0]) != self.n:
+                raise ValueError('graph must be (indices, sq_distances) of the %d fitted cells' % self.n)
+            gi = torch.as_tensor(np.asarray(gi) if not isinstance(gi, torch.Tensor) else gi).to(self.device, torch.int32).contiguous()
+        return cluster.louvain(cluster.snn_graph(gi, weights), resolution=resolution, pg=self.pg, **louvain_kw)
+
     # ---- which genes distinguish a cluster (scanpy's rank_genes_groups(method='t-test') on the counts the model holds) --------
     # Per cluster and gene the test needs the mean, the variance and the expressing fraction of the log-normalised counts
     # y_ij = log1p(x_ij target_sum / total_i).  y = 0 wherever x = 0, so the moments are sums over the non-zero counts only:
