@@ -697,7 +697,8 @@ int oriana_dense_times_factor(double *out, const float *D, const double *W, int6
  * factor the NEXT sweep's cell update multiplies (zigap.py:116: the V_hat just updated; sparse_zigap.py:138:
  * S_hat * Vprime_hat) that sweep has no pass over D_hat left on the cell side.  DV_next must be zeroed first.
  * scratch: oriana_dropout_sweep_scratch_floats(m, K) floats of device scratch (logit(pi_d), float32 copies of V and
- * V_next).  arithmetic: how the float32 products are evaluated --
+ * V_next), 16-byte aligned, contents undefined on entry and exit: every piece of it that a kernel reads has been written by
+ * the same call (tests/test_scratch_contract_gpu.py).  arithmetic: how the float32 products are evaluated --
  *   ORIANA_MATRIX_F32     v_mfma_f32_32x32x2_f32 (a chain of single-rounding float32 FMAs);
  *   ORIANA_MATRIX_BF16X3  each float32 operand split into three bf16, six cross products on the bf16 matrix cores,
  *                         float32 accumulation (K <= 100 when the gene count is a multiple of 4, K <= 64 otherwise;
@@ -735,8 +736,8 @@ int oriana_nzmask_counts(uint32_t *mask, const oriana_counts *cm, int64_t ld, vo
  * K <= 128 (else ORIANA_EKRANGE); the kernel family that serves a K is the one that entry runs for it (the same rule and the
  * same preconditions, minus the D_hat pointer), compiled without the store and the column-sum path.  nzmask (required) and
  * nztiles (optional, as above) describe the cells at hand; scratch: oriana_dropout_sweep_scratch_floats(m, K) floats, 16-byte
- * aligned.  active [n] bytes or NULL (= every cell): a work-group whose cells are all inactive returns at once; rows of U and DV
- * that belong to inactive cells are neither read nor written. */
+ * aligned, contents undefined on entry and exit.  active [n] bytes or NULL (= every cell): a work-group whose cells are all
+ * inactive returns at once; rows of U and DV that belong to inactive cells are neither read nor written. */
 int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
                           const uint32_t *nztiles, const uint8_t *active, float *scratch, int arithmetic, int64_t n, int64_t m,
                           int64_t K, void *stream);
@@ -777,8 +778,8 @@ int64_t oriana_zi_gene_rate_scratch_doubles(int64_t n, int64_t m, int64_t K);
 int oriana_zi_gene_rate(double *G, double *dsum, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
                         double *scratch, int64_t n, int64_t m, int64_t K, void *stream);
 /* out[m, K] += D_hat^T W[n, K] (zigap.py:124), D_hat streamed once; `out` must be initialised.  arithmetic as above;
- * scratch: oriana_dense_t_scratch_floats(n, K) floats (16-byte aligned; the bf16 operand images of W), may be NULL
- * with ORIANA_MATRIX_F32. */
+ * scratch: oriana_dense_t_scratch_floats(n, K) floats (16-byte aligned; the bf16 operand images of W; contents undefined on
+ * entry and exit), may be NULL with ORIANA_MATRIX_F32. */
 int oriana_dense_t_times_factor_f32(double *out, const float *D, const double *W, float *scratch, int arithmetic,
                                     int64_t n, int64_t m, int64_t K, void *stream);
 int64_t oriana_dense_t_scratch_floats(int64_t n, int64_t K);

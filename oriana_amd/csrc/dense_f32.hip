@@ -1562,6 +1562,9 @@ extern "C" int oriana_dropout_sweep_fused(float *D_hat, const double *U, const d
                                             K, stream);
 }
 
+// (One size for every kernel family: the images of the b16 family at NT = 2 plus four chunks, or those of the tiles family at its
+//  largest configuration.  The images a call writes end before it -- a guard band behind a scratch of this size does not see an
+//  overrun of less than that spare room.)
 extern "C" int64_t oriana_dense_t_scratch_floats(int64_t n, int64_t K) {
     if (n < 0 || K < 0) return 0;
     const int64_t a = ((n + 15) / 16 + 4) * (int64_t)(2 * 3 * 64) * 4;       // operand images of W at the b16 family's largest

@@ -193,7 +193,7 @@ def fold_in_zi(ct_new, K, log_V_hat, V_hat, pi_d, alpha1, alpha2, a1, a2, n_iter
         st, perm = stream_ptr(), ptr(ct_new.row_perm)
         nztiles = torch.zeros(max(int(lib.oriana_nzmask_tiles_words(n, mp)), 4), dtype=torch.int32, device=dev)
         call('oriana_nzmask_tiles', ptr(nztiles), ptr(nzmask), n, mp, st)
-        scratch = torch.zeros(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), dtype=_F32, device=dev)   # the call's own
+        scratch = torch.empty(int(lib.oriana_dropout_sweep_scratch_floats(mp, K)), dtype=_F32, device=dev)   # the call's own, undefined contents
         rate, U_hat = torch.empty(n, K, dtype=_F64, device=dev), torch.empty(n, K, dtype=_F64, device=dev)
         def start(lu, active):
             call('oriana_foldin_update_zi', ptr(a1), ptr(a2), ptr(U_hat), ptr(lu), ptr(active), None, None, None, None, None, None,

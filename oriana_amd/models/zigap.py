@@ -71,8 +71,9 @@ class _ZIMixin:
         self._fast_dense = self.k <= 128 and os.environ.get('ORIANA_ZI_EXACT', '0') != '1'
         self._DV_next = None
         self.n_kept_products = 0          # sweeps whose D_hat V came from the previous sweep's D update
-        self._lg_scratch = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(mp, self.k)), dtype=torch.float32, device=dev)
-        self._dt_scratch = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, self.k)), dtype=torch.float32, device=dev)
+        # (contents undefined on entry and exit, include/oriana_hip.h: the entries write what they read)
+        self._lg_scratch = torch.empty(int(_lib.load().oriana_dropout_sweep_scratch_floats(mp, self.k)), dtype=torch.float32, device=dev)
+        self._dt_scratch = torch.empty(int(_lib.load().oriana_dense_t_scratch_floats(n, self.k)), dtype=torch.float32, device=dev)
         # how the float32 products are evaluated (include/oriana_hip.h): 1 = three-way bf16 splits on the bf16 matrix
         # cores (up to Kp = 100; the float32 instruction above), 0 = the float32 matrix instruction
         self._matrix_arith = {'f32': 0, 'bf16x3': 1}[os.environ.get('ORIANA_ZI_MATRIX', 'bf16x3')]

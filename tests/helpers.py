@@ -186,3 +186,51 @@ def dropout_sweep(D, U, V, pi, mask, cs, Vn, DV, scratch, arithmetic, n, m, K):
     call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(U), ptr(V), ptr(pi), ptr(mask), ptr(tiles), ptr(cs), ptr(Vn), ptr(DV),
          ptr(scratch), arithmetic, n, m, K, stream_ptr())
     return tiles
+
+
+# ---- scratch and outputs under a contract (tests/test_scratch_contract_host.py, tests/test_scratch_contract_gpu.py) ---------------
+GUARD_BYTES = 4096
+# variant -> (interior byte, guard byte).  'nan': every byte 0xFF is NaN as float32 and as float64 and -1 as an integer, and a float
+# read past the end meets NaN too.  'stale' starts as 'zero'; the test then makes a valid call of the same sizes on other seeded
+# inputs and hands the buffer over as that call left it (stale_scratch below).
+SCRATCH_VARIANTS = {'zero': (0x00, 0xA5), 'nan': (0xFF, 0xFF), 'stale': (0x00, 0xA5)}
+
+
+def guarded(nbytes, interior=0x00, guard=0xA5, dtype=None, device='cuda'):
+    """(view, check): a view of EXACTLY nbytes bytes as `dtype` (default uint8), its first byte on a multiple of 256, every byte
+    `interior`, inside an allocation whose other bytes -- at least GUARD_BYTES on each side -- are `guard`; check() asserts that
+    every byte outside the view still is."""
+    import torch
+    dtype = torch.uint8 if dtype is None else dtype
+    nbytes = int(nbytes)
+    size = torch.empty((), dtype=dtype).element_size()
+    assert nbytes >= 0 and nbytes % size == 0, (nbytes, dtype)
+    raw = torch.full((nbytes + 2 * GUARD_BYTES + 256,), guard, dtype=torch.uint8, device=device)
+    lo = GUARD_BYTES + (-(raw.data_ptr() + GUARD_BYTES)) % 256
+    hi = lo + nbytes
+    raw[lo:hi] = interior
+    view = raw[lo:hi].view(dtype)
+    assert view.data_ptr() % 256 == 0 and view.numel() * size == nbytes and lo >= GUARD_BYTES and raw.numel() - hi >= GUARD_BYTES
+
+    def check(what=''):
+        for name, band, at in (('before', raw[:lo], -lo), ('behind', raw[hi:], nbytes)):
+            bad = torch.nonzero(band != guard)
+            assert bad.numel() == 0, '%s: %d guard bytes %s the %d-byte buffer were written, the first at byte %d' % (
+                what, bad.numel(), name, nbytes, at + int(bad[0]))
+    return view, check
+
+
+def guarded_variant(nbytes, variant, dtype=None, device='cuda'):
+    interior, guard = SCRATCH_VARIANTS[variant]
+    return guarded(nbytes, interior, guard, dtype, device)
+
+
+def guarded_out(shape, dtype, fill, device='cuda'):
+    """An output tensor of `shape` inside guard bands: `fill` = 'nan' where the entry writes every element (all bytes 0xFF: NaN as
+    a float, -1 as an integer), 'zero' where it adds to what is there."""
+    import torch
+    numel = 1
+    for s in shape:
+        numel *= int(s)
+    view, check = guarded(numel * torch.empty((), dtype=dtype).element_size(), {'nan': 0xFF, 'zero': 0x00}[fill], 0xA5, dtype, device)
+    return view.view(*shape), check

@@ -485,6 +485,14 @@ def test_sparse_row_phase_fused_matches_split(eng, K, weighted, monkeypatch):
         assert err_colrel(got, ref) < RTOL
 
 
+def assert_close_to_oracle(outs, refs):
+    """The comparison of the stateless drop-ins with oracle.cavi_oracle: every output (device tensors) within RTOL of its
+    reference in err_colrel."""
+    assert len(outs) == len(refs)
+    for got, ref in zip(outs, refs):
+        assert err_colrel(got.cpu().numpy(), ref) < RTOL
+
+
 @pytest.mark.parametrize('name', ['ZIGaP', 'SparseGaP', 'SparseZIGaP'])
 def test_variant_dropins_general_D(eng, name):
     """Model.compute_Z_q_expectations(...) with the reference's argument order on dense device
@@ -510,8 +518,7 @@ def test_variant_dropins_general_D(eng, name):
     else:
         M.SparseZIGaP.compute_Z_q_expectations(o[0], o[1], o[2], c(lu), c(lv), c(St), c(Sh), c(D), c(X))
         co.zq_sparse_zigap(r[0], r[1], r[2], lu, lv, St, Sh, D, X)
-    for got, ref in zip(o, r):
-        assert err_colrel(got.cpu().numpy(), ref) < RTOL
+    assert_close_to_oracle(o, r)
 
 
 def test_zigap_dropin_corrected_index_and_edges(eng):
@@ -529,8 +536,7 @@ def test_zigap_dropin_corrected_index_and_edges(eng):
     r = [np.empty((n, K), np.float32), np.empty((m, K), np.float32), np.empty((m, K), np.float32)]
     M.ZIGaP.compute_Z_q_expectations(o[0], o[1], o[2], c(lu), c(lv), c(D), c(X), reference_quirks=False)
     co.zq_zigap(r[0], r[1], r[2], lu, lv, D, X, quirk=False)
-    for got, ref in zip(o, r):
-        assert err_colrel(got.cpu().numpy(), ref) < RTOL
+    assert_close_to_oracle(o, r)
     # all-zero counts: outputs are zero-filled by the callee
     M.ZIGaP.compute_Z_q_expectations(o[0], o[1], o[2], c(lu), c(lv), c(D), c(np.zeros_like(X)))
     assert all(not t.cpu().numpy().any() for t in o)
@@ -653,20 +659,28 @@ def test_dense_t_times_factor_f32(n, m, K, arithmetic):
     bf16 matrix cores for K <= 100) and sums that end in float64, against the float64 product."""
     import torch
     from oriana_amd import _lib
+    scr = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, K)), dtype=torch.float32, device='cuda')
+    check_dense_t(n, m, K, arithmetic, scr)
+
+
+def check_dense_t(n, m, K, arithmetic, scr, out=None, seed=0):
+    """The assertions of test_dense_t_times_factor_f32 on the scratch `scr` (and the zeroed (m, K) float64 `out`, if given); `seed`
+    other than 0: other inputs of the same sizes.  Returns the product of the first call."""
+    import torch
     from oriana_amd._lib import call, ptr, stream_ptr
-    g = torch.Generator(device='cpu').manual_seed(n * 7 + m * 3 + K)
+    g = torch.Generator(device='cpu').manual_seed(n * 7 + m * 3 + K + 1000003 * seed)
     D = torch.rand(n, m, generator=g, dtype=torch.float32)
     D[D < 0.3] = 0.0
     D[torch.rand(n, m, generator=g) < 0.05] *= 1e-6          # some tiny dropout probabilities
     W = torch.rand(n, K, generator=g, dtype=torch.float64) * 3.0
     Dd, Wd = D.cuda(), W.cuda()
-    out = torch.zeros(m, K, dtype=torch.float64, device='cuda')
-    scr = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, K)), dtype=torch.float32, device='cuda')
+    out = torch.zeros(m, K, dtype=torch.float64, device='cuda') if out is None else out
     call('oriana_dense_t_times_factor_f32', ptr(out), ptr(Dd), ptr(Wd), ptr(scr), arithmetic, n, m, K, stream_ptr())
     torch.cuda.synchronize()
+    first = out.cpu().numpy()
     ref = (D.double().t() @ W).numpy()
     # positive terms: relative error of the sums.  256-term float32 chains (3e-7 rms each) averaged over the chunks
-    np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-6, atol=1e-30)
+    np.testing.assert_allclose(first, ref, rtol=1e-6, atol=1e-30)
     if n >= 1000:
         rel = (out.cpu().numpy() - ref) / np.maximum(ref, 1e-300)
         assert np.sqrt(np.mean(rel ** 2)) < 2.5e-7
@@ -674,6 +688,7 @@ def test_dense_t_times_factor_f32(n, m, K, arithmetic):
     call('oriana_dense_t_times_factor_f32', ptr(out), ptr(Dd), ptr(Wd), ptr(scr), arithmetic, n, m, K, stream_ptr())   # accumulates
     torch.cuda.synchronize()
     np.testing.assert_allclose(out.cpu().numpy(), 2.0 * ref, rtol=1e-6, atol=1e-30)
+    return first
 
 
 @pytest.mark.gpu
@@ -685,8 +700,17 @@ def test_dropout_sweep_fused_matches_float64(n, m, K, with_next, arithmetic):
     the float32 matrix instruction and with three-way bf16 splits on the bf16 matrix cores (K <= 100)."""
     import torch
     from oriana_amd import _lib
+    lgs = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(m, K)), dtype=torch.float32, device='cuda')
+    check_dropout_sweep(n, m, K, with_next, arithmetic, lgs)
+
+
+def check_dropout_sweep(n, m, K, with_next, arithmetic, lgs, bufs=None, seed=0):
+    """The assertions of test_dropout_sweep_fused_matches_float64 on the scratch `lgs`; bufs: (D_hat (n, m) float32, colsum [m]
+    float64 zeroed, DV (n, K) float64 zeroed) to write into; `seed` other than 0: other inputs of the same sizes.  Returns
+    (D_hat, colsum, DV or None) as NumPy arrays."""
+    import torch
     from oriana_amd._lib import call, ptr, stream_ptr
-    g = torch.Generator(device='cpu').manual_seed(n + 3 * m + 11 * K)
+    g = torch.Generator(device='cpu').manual_seed(n + 3 * m + 11 * K + 1000003 * seed)
     U = (torch.rand(n, K, generator=g, dtype=torch.float64) * 2.0).cuda()
     V = (torch.rand(m, K, generator=g, dtype=torch.float64) * 2.0).cuda()
     Vn = (torch.rand(m, K, generator=g, dtype=torch.float64) * 3.0).cuda()
@@ -698,10 +722,12 @@ def test_dropout_sweep_fused_matches_float64(n, m, K, with_next, arithmetic):
     X = (torch.rand(n, m, generator=g) < 0.2).float().cuda()
     mask = torch.zeros(((n + 31) // 32) * m, dtype=torch.int32, device='cuda')
     call('oriana_nzmask_f32', ptr(mask), ptr(X), n, m, stream_ptr())
-    D1 = torch.full((n, m), -7.0, dtype=torch.float32, device='cuda')
-    cs1 = torch.zeros(m, dtype=torch.float64, device='cuda')
-    DV = torch.zeros(n, K, dtype=torch.float64, device='cuda')
-    lgs = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(m, K)), dtype=torch.float32, device='cuda')
+    if bufs is None:
+        D1 = torch.full((n, m), -7.0, dtype=torch.float32, device='cuda')
+        cs1 = torch.zeros(m, dtype=torch.float64, device='cuda')
+        DV = torch.zeros(n, K, dtype=torch.float64, device='cuda')
+    else:
+        D1, cs1, DV = bufs
     dropout_sweep(D1, U, V, pi, mask, cs1, Vn if with_next else None, DV if with_next else None, lgs, arithmetic, n, m, K)
     D2 = torch.empty_like(D1)
     cs2 = torch.zeros_like(cs1)
@@ -727,6 +753,7 @@ def test_dropout_sweep_fused_matches_float64(n, m, K, with_next, arithmetic):
             rel = (DV.cpu().numpy() - ref) / np.maximum(ref, 1e-300)
             assert np.sqrt(np.mean(rel ** 2)) < 2.5e-7
             assert abs(np.mean(rel)) < 1e-7
+    return d1, cs1.cpu().numpy(), DV.cpu().numpy() if with_next else None
 
 
 @pytest.mark.gpu
@@ -784,6 +811,14 @@ def test_deterministic_column_pass(eng, K, m):
     (per work item slabs + ordered reduction) instead of float atomics: two runs are bit-identical, and the default
     (atomic) path agrees with it to the order of float32 additions.  K = 96 / 100 take the two-tile kernel (odd and
     even numbers of column tiles), the others the generic one (G = 4, G = 8 with two work-groups per item)."""
+    check_deterministic_column_pass(eng, K, m)
+
+
+def check_deterministic_column_pass(eng, K, m, scratch=None):
+    """The assertions of test_deterministic_column_pass.  scratch(nbytes, install, warm): called once before the runs; it hands
+    install() the float32 tensor of nbytes bytes that oriana_col_pass_det is to run on -- put into engine._det_scratch in the
+    place of the cached one -- and may call warm(), a deterministic nest over the same layout on other inputs.  Returns
+    (Z_i, Z_j) of the first deterministic run."""
     rng = np.random.default_rng(K + m)
     n = 1500
     dens = rng.beta(1.0, 3.0, size=m)
@@ -796,6 +831,21 @@ def test_deterministic_column_pass(eng, K, m):
     tlu, tlv = torch.from_numpy(lu).cuda(), torch.from_numpy(lv).cuda()
     outs = []
     try:
+        if scratch is not None:
+            w = ct.col_work_for(K)
+            key = (ct.device, int(eng._lib.load().oriana_col_pass_det_scratch_bytes(K, int(w.shape[0]))))
+
+            def install(t):
+                eng._det_scratch.clear()
+                eng._det_scratch[key] = t
+
+            def warm():
+                other = torch.from_numpy(np.random.default_rng(K + m + 1).normal(size=(n, K)).astype(np.float32)).cuda()
+                eng.set_deterministic(True)
+                eng.zq_gap(ws, torch.empty(n, K, device='cuda'), torch.empty(m, K, device='cuda'), other, tlv)
+                torch.cuda.synchronize()
+            scratch(key[1], install, warm)
+            held = eng._det_scratch[key]
         for det in (True, True, False):
             eng.set_deterministic(det)
             Zi = torch.empty(n, K, device='cuda'); Zj = torch.empty(m, K, device='cuda')
@@ -803,12 +853,22 @@ def test_deterministic_column_pass(eng, K, m):
             outs.append((Zi.cpu().numpy(), Zj.cpu().numpy()))
     finally:
         eng.set_deterministic(False)
+    if scratch is not None:
+        assert eng._det_scratch.get(key) is held, 'the deterministic passes ran on another scratch'
     assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][0], outs[1][0])
     assert err_colrel(outs[2][1], outs[0][1]) < 1e-6
     from oracle import cavi_oracle as co
-    rZi = np.empty((n, K), np.float32); rZj = np.empty((m, K), np.float32)
-    co.zq_gap(rZi, rZj, lu, lv, np.ascontiguousarray(X.astype(np.float32)))
+    if (K, m) not in _det_oracle:                               # (computed once per case, only read)
+        rZi = np.empty((n, K), np.float32); rZj = np.empty((m, K), np.float32)
+        co.zq_gap(rZi, rZj, lu, lv, np.ascontiguousarray(X.astype(np.float32)))
+        rZi.setflags(write=False); rZj.setflags(write=False)
+        _det_oracle[(K, m)] = (rZi, rZj)
+    rZi, rZj = _det_oracle[(K, m)]
     assert err_colrel(outs[0][1], rZj) < RTOL and err_colrel(outs[0][0], rZi) < RTOL
+    return outs[0]
+
+
+_det_oracle = {}
 
 
 @pytest.mark.parametrize('K', [85, 90, 96, 97, 100])
@@ -858,17 +918,28 @@ def test_dense_zi_kernels_decline_unaligned_buffers():
     instruction's kernels instead (same results to float32 accuracy), through both entries."""
     import torch
     from oriana_amd import _lib
+    n, m, K = UNALIGNED_SHAPE
+    lgs = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(m, K)), dtype=torch.float32, device='cuda')
+    dts = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, K)), dtype=torch.float32, device='cuda')
+    check_unaligned_fallback(lgs, dts)
+
+
+UNALIGNED_SHAPE = (300, 260, 100)
+
+
+def check_unaligned_fallback(lgs, dts, seed=0):
+    """The assertions of test_dense_zi_kernels_decline_unaligned_buffers on the two scratches (`seed` other than 0: other inputs).
+    Returns the outputs of the unaligned run: (D_hat, colsum, DV, D_hat^T U) as NumPy arrays."""
+    import torch
     from oriana_amd._lib import call, ptr, stream_ptr
-    n, m, K = 300, 260, 100
-    g = torch.Generator(device='cpu').manual_seed(3)
+    n, m, K = UNALIGNED_SHAPE
+    g = torch.Generator(device='cpu').manual_seed(3 + 1000003 * seed)
     U = (torch.rand(n, K, generator=g, dtype=torch.float64) * 0.3).cuda()
     V = (torch.rand(m, K, generator=g, dtype=torch.float64) * 0.3).cuda()
     pi = torch.rand(m, generator=g, dtype=torch.float64).cuda()
     X = (torch.rand(n, m, generator=g) < 0.2).float().cuda()
     mask = torch.zeros(((n + 31) // 32) * m, dtype=torch.int32, device='cuda')
     call('oriana_nzmask_f32', ptr(mask), ptr(X), n, m, stream_ptr())
-    lgs = torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(m, K)), dtype=torch.float32, device='cuda')
-    dts = torch.zeros(int(_lib.load().oriana_dense_t_scratch_floats(n, K)), dtype=torch.float32, device='cuda')
     outs = []
     for shift in (0, 1):
         base = torch.zeros(n * m + 4, dtype=torch.float32, device='cuda')
@@ -883,6 +954,7 @@ def test_dense_zi_kernels_decline_unaligned_buffers():
         outs.append((D.clone(), cs, DV, DtU))
     for a, b in zip(outs[0], outs[1]):
         assert torch.allclose(a.double(), b.double(), rtol=2e-6, atol=1e-7)
+    return tuple(t.cpu().numpy() for t in outs[1])
 
 
 @pytest.mark.parametrize('K', [33, 36, 40, 48, 50, 52, 57, 64])

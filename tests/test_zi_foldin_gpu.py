@@ -49,15 +49,15 @@ def _mask_bits(X, mp):
     return np.bitwise_or.reduce(bits.reshape(nw, 32, mp) << np.arange(32, dtype=np.uint32)[None, :, None], axis=1)
 
 
-def _masks(X, sort_rows=False):
+def _masks(X, sort_rows=False, mp=MP):
     from oriana_amd import _lib, engine
     from oriana_amd._lib import call, ptr, stream_ptr
     n = X.shape[0]
     ct = engine.CountTiles.from_dense(X, DEV, sort_rows=sort_rows)
-    mask = torch.zeros(((n + 31) // 32) * MP, dtype=torch.int32, device=DEV)
-    call('oriana_nzmask_counts', ptr(mask), ct.sparse_struct, MP, stream_ptr())
-    tiles = torch.zeros(max(int(_lib.load().oriana_nzmask_tiles_words(n, MP)), 4), dtype=torch.int32, device=DEV)
-    call('oriana_nzmask_tiles', ptr(tiles), ptr(mask), n, MP, stream_ptr())
+    mask = torch.zeros(((n + 31) // 32) * mp, dtype=torch.int32, device=DEV)
+    call('oriana_nzmask_counts', ptr(mask), ct.sparse_struct, mp, stream_ptr())
+    tiles = torch.zeros(max(int(_lib.load().oriana_nzmask_tiles_words(n, mp)), 4), dtype=torch.int32, device=DEV)
+    call('oriana_nzmask_tiles', ptr(tiles), ptr(mask), n, mp, stream_ptr())
     return ct, mask, tiles
 
 
@@ -103,43 +103,50 @@ def rate_case():
 
 
 def _padded(V, pi_d):
-    K = V.shape[1]
-    Vp, pip = torch.zeros(MP, K, dtype=torch.float64, device=DEV), torch.zeros(MP, dtype=torch.float64, device=DEV)
-    Vp[:M_COLS].copy_(_f64(V))
-    pip[:M_COLS].copy_(_f64(pi_d))
+    """V and pi_d with the inert genes (V row 0, pi_d 0) that bring the gene count to a multiple of 4."""
+    m, K = V.shape
+    mp = (m + 3) // 4 * 4
+    Vp, pip = torch.zeros(mp, K, dtype=torch.float64, device=DEV), torch.zeros(mp, dtype=torch.float64, device=DEV)
+    Vp[:m].copy_(_f64(V))
+    pip[:m].copy_(_f64(pi_d))
     return Vp, pip
 
 
-def _scratch(K):
+def _scratch(K, mp=MP):
     from oriana_amd import _lib
-    return torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(MP, K)), dtype=torch.float32, device=DEV)
+    return torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(mp, K)), dtype=torch.float32, device=DEV)
 
 
-def _rate(X, U, V, pi_d, arithmetic, active=None, DV=None):
+def _rate(X, U, V, pi_d, arithmetic, active=None, DV=None, scratch=None):
+    """oriana_zi_foldin_rate on `scratch` (default: zeros of the stated size), adding to DV (default: zeros)."""
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    _, mask, tiles = _masks(X)
     Vp, pip = _padded(V, pi_d)
+    mp = int(Vp.shape[0])
+    _, mask, tiles = _masks(X, mp=mp)
     Ud = _f64(U)
     DV = torch.zeros(n, K, dtype=torch.float64, device=DEV) if DV is None else DV
-    call('oriana_zi_foldin_rate', ptr(DV), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(active), ptr(_scratch(K)),
-         arithmetic, n, MP, K, stream_ptr())
+    scratch = _scratch(K, mp) if scratch is None else scratch
+    call('oriana_zi_foldin_rate', ptr(DV), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(active), ptr(scratch),
+         arithmetic, n, mp, K, stream_ptr())
     torch.cuda.synchronize()
     return DV.cpu().numpy()
 
 
-def _storing(X, U, V, pi_d, arithmetic):
+def _storing(X, U, V, pi_d, arithmetic, scratch=None):
     """DV_next of oriana_dropout_sweep_fused_tiles on a scratch D_hat, and that D_hat."""
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    _, mask, tiles = _masks(X)
     Vp, pip = _padded(V, pi_d)
+    mp = int(Vp.shape[0])
+    _, mask, tiles = _masks(X, mp=mp)
     Ud = _f64(U)
-    D = torch.empty(n, MP, dtype=torch.float32, device=DEV)
-    cs = torch.zeros(MP, dtype=torch.float64, device=DEV)
+    D = torch.empty(n, mp, dtype=torch.float32, device=DEV)
+    cs = torch.zeros(mp, dtype=torch.float64, device=DEV)
     DV = torch.zeros(n, K, dtype=torch.float64, device=DEV)
+    scratch = _scratch(K, mp) if scratch is None else scratch
     call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(cs), ptr(Vp), ptr(DV),
-         ptr(_scratch(K)), arithmetic, n, MP, K, stream_ptr())
+         ptr(scratch), arithmetic, n, mp, K, stream_ptr())
     torch.cuda.synchronize()
     return DV.cpu().numpy(), D.cpu().numpy()
 
@@ -147,10 +154,16 @@ def _storing(X, U, V, pi_d, arithmetic):
 @pytest.mark.parametrize('K,arithmetic', [(20, 1), (50, 1), (50, 0), (100, 1), (128, 1)],
                          ids=['K20-b16', 'K50-tiles', 'K50-f32', 'K100-tiles', 'K128-f32'])
 def test_rate_against_float64(rate_case, K, arithmetic):
-    X, U, V, pi_d, ref = rate_case(K)
-    got = _rate(X, U, V, pi_d, arithmetic)
+    check_rate(*rate_case(K), arithmetic)
+
+
+def check_rate(X, U, V, pi_d, ref, arithmetic, scratch=None, DV=None):
+    """The assertions of test_rate_against_float64 on `scratch` (default: zeros of the stated size), the rate added to the zeroed
+    DV if one is given.  Returns the rate."""
+    K = U.shape[1]
+    got = _rate(X, U, V, pi_d, arithmetic, DV=DV, scratch=scratch)
     e = err_colrel(got, ref)
-    stored, D = _storing(X, U, V, pi_d, arithmetic)
+    stored, D = _storing(X, U, V, pi_d, arithmetic, scratch=scratch)
     e2 = err_colrel(got, stored)
     print('K=%d arithmetic=%d: rate against float64 %.3e (bound %.1e); against the storing entry %.3e (bound 6e-7)'
           % (K, arithmetic, e, RTOL, e2))
@@ -158,6 +171,7 @@ def test_rate_against_float64(rate_case, K, arithmetic):
     assert e <= RTOL
     # the header states the storing entry within 3e-7 relative of float64 on rate terms: two such results agree within 6e-7
     assert e2 <= 6e-7
+    return got
 
 
 def test_rate_k_range():
@@ -179,19 +193,28 @@ def test_rate_skips_inactive_cells(rate_case, K):
     sentinel bit for bit, their U_hat rows (NaN here) reach no active row, and the active rows are those of the all-active
     run up to the order of the float atomics."""
     X, U, V, pi_d, _ = rate_case(K)
-    full = _rate(X, U, V, pi_d, 1)
     act = np.ones(N_ROWS, dtype=np.uint8)
     act[:256] = 0
     act[[300, 511, 512, 513, 700, 804]] = 0
+    check_rate_skips_inactive(X, U, V, pi_d, act, 1)
+
+
+def check_rate_skips_inactive(X, U, V, pi_d, act, arithmetic, scratch=None, DV=None):
+    """The assertions of test_rate_skips_inactive_cells for the active flags `act` on `scratch` (default: zeros of the stated
+    size); DV: an (n, K) float64 tensor to use, filled with the sentinel here.  Returns the rows of the active cells."""
+    n, K = U.shape
+    full = _rate(X, U, V, pi_d, arithmetic, scratch=scratch)
     on = act != 0
     Un = U.copy()
     Un[~on] = np.nan
-    DV = torch.full((N_ROWS, K), SENTINEL, dtype=torch.float64, device=DEV)
-    got = _rate(X, Un, V, pi_d, 1, active=torch.from_numpy(act).to(DEV), DV=DV)
+    DV = torch.empty(n, K, dtype=torch.float64, device=DEV) if DV is None else DV
+    DV.fill_(SENTINEL)
+    got = _rate(X, Un, V, pi_d, arithmetic, active=torch.from_numpy(act).to(DEV), DV=DV, scratch=scratch)
     assert np.array_equal(got[~on], np.full((int((~on).sum()), K), SENTINEL)), 'rows of inactive cells were written'
     e = err_colrel(got[on] - SENTINEL, full[on])
-    print('K=%d: active rows against the all-active run %.3e (bound %.3e)' % (K, e, _twin_bound(N_ROWS, 1)))
-    assert np.isfinite(got).all() and e <= _twin_bound(N_ROWS, 1)
+    print('K=%d: active rows against the all-active run %.3e (bound %.3e)' % (K, e, _twin_bound(n, 1)))
+    assert np.isfinite(got).all() and e <= _twin_bound(n, 1)
+    return got[on] - SENTINEL
 
 
 # ---- 4. one iteration against float64 -----------------------------------------------------------------------------------------
