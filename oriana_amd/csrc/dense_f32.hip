@@ -27,14 +27,22 @@
 //
 // Fragment map of v_mfma_f32_32x32x2_f32: A[m = lane & 31][k = lane >> 5], B[k = lane >> 5][n = lane & 31],
 // D reg v: [m = 8 (v / 4) + 4 (lane >> 5) + v % 4][n = lane & 31].
-#include "dense_tiles.h"
+#include "dense_tiles.h"               // tile types, bf16 x 3 splits, the six-product macro, acc_row, TS, pick_splits: used from there
 // (the ablation switches behind the measurements of DESIGN_HISTORY.md -- ORIANA_ABL32_NOSTORE / _NOSIG / _NOTRANS -- are
 // archived as a patch: tools/experiments/dense_f32_mfma_ablation_switches_r2.diff)
 
 namespace oriana {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
+// the tile pieces of dense_tiles.h (the bf16 x 3 kernels below use its splits and its six-product macro ORIANA_DN_MF6)
+using dn::f16v;
+using dn::f4v;
+using dn::bf8;
+using dn::u4v;
+using dn::mfma_b16;
+using dn::split2;
+using dn::split8;
+using dn::acc_row;
+using dn::TS;
 
 __device__ __forceinline__ f16v mfma32(float a, float b, f16v c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -43,11 +51,6 @@ __device__ __forceinline__ f16v mfma32(float a, float b, f16v c) {
 // Scheduling fence for vector-memory instructions only (everything else may cross): keeps a prefetch where it was
 // written -- left alone, the scheduler sinks such loads down to their first use, i.e. turns them into plain loads.
 #define ORIANA_VMEM_FENCE() __builtin_amdgcn_sched_barrier(0x38F)
-
-// row of the accumulator register v in lane half h
-__device__ __forceinline__ int acc_row(int v, int h) { return 8 * (v >> 2) + 4 * h + (v & 3); }
-
-constexpr int TS = 36;            // row stride of the transpose buffer (floats): 16-byte aligned rows
 
 // LDS carve-up of k_dropout_sweep (floats)
 struct SweepLds {
@@ -523,41 +526,7 @@ __global__ __launch_bounds__(256, (NT < 4) ? 2 : 1) void k_dt_times_factor_f32(d
 // that of the float32 FMA chain (2.9e-7 rms at 512), at 2.7 x the rate of v_mfma_f32_32x32x2_f32 after the six-fold
 // overhead.  K <= 64.  Fragment map of v_mfma_f32_32x32x16_bf16: A[m = lane & 31][k = 8 (lane >> 5) + e],
 // B[k = 8 (lane >> 5) + e][n = lane & 31], e = 0..7 the eight bf16 (four dwords) of the lane; D as for the float32
-// 32 x 32 instructions.
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f16v mfma_b16(u4v a, u4v b, f16v c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
-
-// two floats -> their (hi, mid, lo) bf16 parts, each pair packed in one dword (x0 in the low half)
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t &hi, uint32_t &mid, uint32_t &lo) {
-    const uint32_t b0 = __float_as_uint(x0), b1 = __float_as_uint(x1);
-    const float r0 = x0 - __uint_as_float(b0 & 0xFFFF0000u), r1 = x1 - __uint_as_float(b1 & 0xFFFF0000u);
-    const uint32_t c0 = __float_as_uint(r0), c1 = __float_as_uint(r1);
-    const float s0 = r0 - __uint_as_float(c0 & 0xFFFF0000u), s1 = r1 - __uint_as_float(c1 & 0xFFFF0000u);
-    hi = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-    mid = __builtin_amdgcn_perm(c1, c0, 0x07060302u);
-    lo = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-}
-
-// eight floats -> three operand registers (hi, mid, lo)
-__device__ __forceinline__ void split8(const float (&x)[8], u4v (&o)[3]) {
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {
-        uint32_t a, b, c2;
-        split2(x[2 * w2], x[2 * w2 + 1], a, b, c2);
-        o[0][w2] = a; o[1][w2] = b; o[2][w2] = c2;
-    }
-}
-
-// the six cross products, small terms first
-#define ORIANA_MF6(ACC, A, B)                                                                          \
-    do {                                                                                               \
-        ACC = mfma_b16(A[2], B[0], ACC); ACC = mfma_b16(A[0], B[2], ACC); ACC = mfma_b16(A[1], B[1], ACC); \
-        ACC = mfma_b16(A[1], B[0], ACC); ACC = mfma_b16(A[0], B[1], ACC); ACC = mfma_b16(A[0], B[0], ACC); \
-    } while (0)
+// 32 x 32 instructions.  The splits (split2, split8), mfma_b16 and the macro of the six products are dense_tiles.h's.
 
 // LDS carve-up of k_dropout_sweep_b16 (bytes): operand images are [..][split][lane] x 16 bytes
 struct B16Lds {
@@ -745,7 +714,7 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
             u4v a[3];
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) a[sp] = src[sp * 64];
-            ORIANA_MF6(l0, a, ub[kc]);
+            ORIANA_DN_MF6(l0, a, ub[kc]);
         }
         // ---- sigmoid, overrides
         const int jrem = (je - j0 < 32) ? (int)(je - j0) : 32;
@@ -814,7 +783,7 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
                     u4v b[3];
 #pragma unroll
                     for (int sp = 0; sp < 3; ++sp) b[sp] = src[sp * 64];
-                    ORIANA_MF6(dv[nt], a, b);
+                    ORIANA_DN_MF6(dv[nt], a, b);
                 }
             }
             if (++since_flush == 8) {                            // 256 genes: leave the matrix core
@@ -843,25 +812,6 @@ __global__ __launch_bounds__(256, 2) void k_dropout_sweep_b16(float *__restrict_
     }
 }
 
-// Number of ranges to cut the reduction (or gene) axis into, given `blocks` work-groups along the other axis: the
-// grid runs in rounds of 512 resident work-groups (2 per CU), and a last round that is nearly empty costs as much as a
-// full one -- 1580 groups take 4 rounds at 77 %.  Among 4 to 12 rounds' worth, the count that leaves the last round
-// fullest (fewer ranges on ties: each one ends in a set of float64 atomics).
-static int64_t pick_splits(int64_t blocks, int64_t max_splits) {
-    const int64_t slots = 2 * oriana_device_cus();            // (512 on MI355X)
-    int64_t best = 1;
-    double best_eff = 0.0;
-    for (int64_t sp = 1; sp <= max_splits && sp <= 4096; ++sp) {
-        const int64_t groups = blocks * sp;
-        if (groups > 12 * slots && sp > 1) break;
-        const int64_t rounds = (groups + slots - 1) / slots;
-        double eff = (double)groups / (double)(rounds * slots);
-        if (groups < 4 * slots) eff *= 0.5 + 0.125 * (double)groups / (double)slots;   // too few to hide the tails
-        if (eff > best_eff + 0.02) { best_eff = eff; best = sp; }
-    }
-    return best;
-}
-
 // logit(pi_d) in float32, with the overrides of zigap.py:133-134 encoded as -inf (pi_d <= 0: p_d = 1e-10) and +inf
 // (pi_d >= 1: p_d = 1 - 1e-10, 1 in float32)
 // [r5] lgs (may be NULL): the same as -logit * log2(e) -- the form dn::k_zi_row takes: its sigmoid is
@@ -888,7 +838,7 @@ static int launch_sweep(float *D_hat, const double *U, const double *V, const fl
     const size_t lds = (size_t)L.total * sizeof(float);
     const int64_t rb = (n + 127) / 128;
     // gene ranges: whole tiles of 32, as many per row block as fills the chip's work-group slots evenly
-    const int64_t splits0 = pick_splits(rb, (m + 255) / 256);
+    const int64_t splits0 = dn::pick_splits(rb, (m + 255) / 256, dn::SPLITS_F32);
     int64_t jps = (m + splits0 - 1) / splits0;
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
@@ -999,7 +949,7 @@ __global__ __launch_bounds__(256, 2) void k_dt_times_factor_b16(double *__restri
                 u4v b[3];
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) b[sp] = src[sp * 64];
-                ORIANA_MF6(acc[nt], a, b);
+                ORIANA_DN_MF6(acc[nt], a, b);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1035,7 +985,7 @@ static int launch_dt_b16(double *out, const float *D, const double *W, float *sc
     if (!scratch || !dn::aligned16(scratch)) return ORIANA_EINVAL;
     u4v *img = reinterpret_cast<u4v *>(scratch);
     const int64_t jb = (m + 127) / 128;
-    const int64_t splits0 = pick_splits(jb, (n + 255) / 256);
+    const int64_t splits0 = dn::pick_splits(jb, (n + 255) / 256, dn::SPLITS_F32);
     int64_t ips = (n + splits0 - 1) / splits0;
     ips = (ips + 63) / 64 * 64;                                  // whole staged groups
     const int64_t splits = (n + ips - 1) / ips;
@@ -1059,7 +1009,7 @@ static int launch_sweep_b16(float *D_hat, const double *U, const double *V, cons
     const int rc = launch(k_split_images<NT, KC>, dim3((unsigned)((m + 31) / 32)), dim3(256), 0, st, img1, img2, V, Vn, m, K);
     if (rc) return rc;
     const int64_t rb = (n + 127) / 128;
-    const int64_t splits0 = pick_splits(rb, (m + 255) / 256);
+    const int64_t splits0 = dn::pick_splits(rb, (m + 255) / 256, dn::SPLITS_F32);
     int64_t jps = (m + splits0 - 1) / splits0;
     jps = (jps + 31) / 32 * 32;
     const int64_t splits = (m + jps - 1) / jps;
@@ -1071,7 +1021,7 @@ static int launch_sweep_b16(float *D_hat, const double *U, const double *V, cons
 template <int NT, int GQ>
 static int launch_dt(double *out, const float *D, const double *W, int64_t n, int64_t m, int K, hipStream_t st) {
     const int64_t jb = (m + 128 * GQ - 1) / (128 * GQ);
-    const int64_t splits0 = pick_splits(jb, (n + 255) / 256);
+    const int64_t splits0 = dn::pick_splits(jb, (n + 255) / 256, dn::SPLITS_F32);
     int64_t ips = (n + splits0 - 1) / splits0;
     ips = (ips + 63) / 64 * 64;                                  // whole staged chunks
     const int64_t splits = (n + ips - 1) / ips;

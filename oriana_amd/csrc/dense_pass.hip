@@ -19,10 +19,11 @@
 //             of R += S FV (register v of lane half h is gene 8 (v / 4) + 4 h + v % 4; the reduction visits the
 //             genes in that order).  s goes to HBM through a 32 x 32 LDS transpose, in the register order of k_dn_col.
 //   k_dn_col  (gene side)  wave = 32 genes, a range of cell tiles: reads s (4 B per entry, 16 bytes per lane and
-//             load), C += S^T FU with the FU operand images staged through LDS.
+//             load), C += S^T FU with the FU operand images staged through LDS.  What it shares with dn::k_zi_col
+//             (dense_zi.hip) is in dense_col.h.
 //   entries whose den fails the den >= DEN_MIN test (or that touch a rejected factor row) get the NaN sentinel and
 //   are evaluated exactly by k_dn_fixup, as on the sparse side (passes.hip k_fixup).
-#include "dense_tiles.h"
+#include "dense_col.h"
 // Compile-time ablation switches for the measurements quoted in DESIGN.md (never set in the shipped build; they give
 // wrong results): ORIANA_DN_ABL_NODMA / _NOSTORE / _NOX / _NOBAR drop one ingredient of k_dn_row's loop.
 
@@ -379,8 +380,7 @@ __global__ __launch_bounds__(512) void k_dn_row(const uint16_t *__restrict__ Xd,
         }
     if (TAIL) {
         // lane 4 b + j holds, in register e, the tail sum of cell 4 (b % 8) + e and factor KM + j over its half's genes
-        rt.x += __shfl_xor(rt.x, 32, 64); rt.y += __shfl_xor(rt.y, 32, 64);
-        rt.z += __shfl_xor(rt.z, 32, 64); rt.w += __shfl_xor(rt.w, 32, 64);
+        add_lane_halves(rt);
         if (h == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -398,13 +398,9 @@ __global__ __launch_bounds__(512) void k_dn_row(const uint16_t *__restrict__ Xd,
 // ---- gene side -----------------------------------------------------------------------------------------------------
 // grid.x = nsplit * ngroups, work-group (split, group) = blockIdx.x % nsplit, blockIdx.x / nsplit: the groups of one
 // split -- which stage the same cell images -- are dispatched next to each other.
-// Every global read is an LDS-DMA copy (the cell images shared by the 8 waves: ring of three; the wave's own tile of s:
-// ring of two), issued TWO tiles ahead; the vector-memory counter retires in issue order, so "at most the seven copies
-// of this iteration outstanding" means the previous iteration's have landed.  The partial sums stay on the matrix core
-// for 8 tiles (256 cells: inside the regime where the bf16 x 3 chain carries the float32 chain's error) and then join
-// the running float32 sums; the four tail factors go through v_mfma_f32_4x4x1_16B_f32 (exact float32 FMAs).
-constexpr int COL_FLUSH = 8;
-
+// The pipeline is described in dense_col.h, which holds the pieces shared with dn::k_zi_col (LDS size, flush period, waits,
+// tail block).  Here the tile of s is packed in register order: four 16-byte copies per lane, four 16-byte reads,
+// and no wait of its own between the reads and the refill of their ring slot.
 template <int KC, int TAIL>
 __global__ __launch_bounds__(512) void k_dn_col(const float *__restrict__ S, const u4v *__restrict__ imgU,
                                                 float *__restrict__ Cout, int64_t nct, int ngt, int Kp,
@@ -440,16 +436,10 @@ __global__ __launch_bounds__(512) void k_dn_col(const float *__restrict__ S, con
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + q * 64 + lane),
                                              (__attribute__((address_space(3))) void *)(sbuf + sslot * 2048 + q * 64), 16, 0, 0);
     };
-    constexpr int NCOPY = C::PU / (NW * 64) + 4;                          // LDS-DMA instructions per wave and tile
-    static_assert(NCOPY >= 5 && NCOPY <= 7, "the waits below count the copies of one iteration");
-    auto wait_prev = [&]() {             // the previous iteration's copies have landed, this iteration's may be in flight
-        if (NCOPY == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-        else if (NCOPY == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    };
+    constexpr int NCOPY = col_copies<KC, TAIL>();
     issue(ct0, 0, 0);
     issue(ct0 + 1, 1, 1);
-    wait_prev();
+    col_wait_prev<NCOPY>();
     __builtin_amdgcn_s_barrier();
     int islot = 0, sslot = 0, since = 0;
     for (int64_t ct = ct0; ct < ct1; ++ct) {
@@ -480,15 +470,8 @@ __global__ __launch_bounds__(512) void k_dn_col(const float *__restrict__ S, con
             }
         }
         if (TAIL) {
-            // 16 blocks of 4 genes x 4 factors, one cell per instruction: A[b][i] = s of gene 4 (b % 8) + i (this lane's
-            // value), B[b][j] = FU[cell][KM + j]
             const f4v *t2p = reinterpret_cast<const f4v *>(im + C::P2 + 32) + (h * 4 + (lane & 3)) * 4;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f4v t2 = t2p[q];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cta = __builtin_amdgcn_mfma_f32_4x4x1f32(sc[q][e], t2[e], cta, 0, 0, 0);
-            }
+            col_tail(t2p, sc, cta);
         }
         if (++since == COL_FLUSH) {      // 256 cells: leave the matrix core
             since = 0;
@@ -497,7 +480,7 @@ __global__ __launch_bounds__(512) void k_dn_col(const float *__restrict__ S, con
 #pragma unroll
                 for (int v = 0; v < 16; ++v) { cs[nt][v] += dv[nt][v]; dv[nt][v] = 0.f; }
         }
-        wait_prev();
+        col_wait_prev<NCOPY>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         islot = (islot == 2) ? 0 : islot + 1;
@@ -515,8 +498,7 @@ __global__ __launch_bounds__(512) void k_dn_col(const float *__restrict__ S, con
         }
     if (TAIL) {
         // lane 4 b + j holds, in register e, the tail sum of gene 4 (b % 8) + e and factor KM + j over its half's cells
-        cta.x += __shfl_xor(cta.x, 32, 64); cta.y += __shfl_xor(cta.y, 32, 64);
-        cta.z += __shfl_xor(cta.z, 32, 64); cta.w += __shfl_xor(cta.w, 32, 64);
+        add_lane_halves(cta);
         if (h == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -876,7 +858,6 @@ __global__ __launch_bounds__(256) void k_dn_elbo(const uint16_t *__restrict__ Xd
 }
 
 template <int KC, int TAIL> constexpr int row_lds_bytes() { return 3 * Cfg<KC, TAIL>::PV * 16 + NW * 32 * TS * 4; }
-template <int KC, int TAIL> constexpr int col_lds_bytes() { return 3 * Cfg<KC, TAIL>::PU * 16 + 2 * NW * 256 * 16; }
 
 }  // namespace dn
 }  // namespace oriana

@@ -1,7 +1,8 @@
 // dense_tiles.h -- pieces shared by the matrix-core kernels over dense 32 x 32 tiles (dense_pass.hip: the dense genes of
 // pCMF's responsibility pass, Kp <= 100; dense_zi.hip: the D update and D_hat^T U_hat of the ZI models for the widths
 // zi_candidate below gives them): bf16 x 3 splits, the six-product macro, accumulator geometry, operand image layout, LDS-DMA
-// copies; and, host side, the (KC, TAIL) dispatcher and the rule that says which kernel family serves which ZI product.
+// copies; and, host side, the (KC, TAIL) dispatcher, the rule that says which kernel family serves which ZI product, and
+// pick_splits with its two rules (SplitRule): into how many ranges dense_f32.hip and dense_zi.hip cut an axis.
 #pragma once
 #include "launch.h"
 #include <utility>
@@ -224,6 +225,40 @@ static int zi_first(Ok &&ok, Run &&run) {
     constexpr ZiCand c = zi_candidate(OP, KP, ARITH, I);
     if constexpr (c.fam == ZiFam::none) return ORIANA_EKRANGE;
     else return ok(c.fam) ? run(ZiPick<c.fam, c.a, c.b>{}) : zi_first<OP, KP, ARITH, I + 1>(ok, run);
+}
+
+// ------------------------------------------------------------------------------------------
+// Number of ranges to cut the reduction (or gene) axis into, given `blocks` work-groups along the other axis.  The grid runs in
+// rounds of per_cu x CUs resident work-groups, and a last round that is nearly empty costs as much as a full one: among the counts
+// up to max_ranges whose grid stays within max_rounds rounds' worth, the one that leaves the last round fullest; a larger count
+// wins only by more than `margin` (fewer ranges on ties: each one ends in a set of float64 atomics).
+// ------------------------------------------------------------------------------------------
+struct SplitRule {
+    int per_cu;            // resident work-groups per CU
+    int64_t max_ranges;    // range limit
+    int max_rounds;        // cap on rounds
+    double margin;         // tie margin
+    int small_rounds;      // small-grid penalty: below this many rounds' worth the fill counts 0.5 .. 1 of itself; 0 = none
+};
+// dense_f32.hip: rounds of 512 resident work-groups (2 per CU) on MI355X -- 1580 groups take 4 rounds at 77 %.  Among 4 to 12
+// rounds' worth (below 4 there are too few groups to hide the tails)
+constexpr SplitRule SPLITS_F32 = {2, 4096, 12, 0.02, 4};
+// dense_zi.hip: work-groups of 512 threads, one per CU (256 on MI355X)
+constexpr SplitRule SPLITS_TILES = {1, 64, 16, 0.03, 0};
+
+static int64_t pick_splits(int64_t blocks, int64_t max_splits, const SplitRule &rule) {
+    const int64_t slots = rule.per_cu * oriana_device_cus();
+    int64_t best = 1;
+    double best_eff = 0.0;
+    for (int64_t sp = 1; sp <= max_splits && sp <= rule.max_ranges; ++sp) {
+        const int64_t groups = blocks * sp;
+        if (groups > rule.max_rounds * slots && sp > 1) break;
+        const int64_t rounds = (groups + slots - 1) / slots;
+        double eff = (double)groups / (double)(rounds * slots);
+        if (groups < rule.small_rounds * slots) eff *= 0.5 + 0.5 / rule.small_rounds * (double)groups / (double)slots;
+        if (eff > best_eff + rule.margin) { best_eff = eff; best = sp; }
+    }
+    return best;
 }
 
 // dense_zi.hip, called from the entries of dense_f32.hip

@@ -7,12 +7,13 @@
 //              Lambda^T[gene, cell] = V U^T per 32 x 32 tile, p = sigmoid(logit pi_j - Lambda) + overrides in float32,
 //              D_hat out as 128-byte row pieces, sum_i p_d, DV[cell, k] += D_hat V_next.  Same software pipeline as
 //              dn::k_dn_row (S(t) beside the matrix instructions of Lambda(t + 1), then the product of tile t).
-//   k_zi_col   out[gene, k] += sum_i D_hat[i, gene] W[i, k]  (zigap.py:124): dn::k_dn_col reading D_hat row-major.
+//   k_zi_col   out[gene, k] += sum_i D_hat[i, gene] W[i, k]  (zigap.py:124): dn::k_dn_col reading D_hat row-major (what the two
+//              have in common is in dense_col.h; the number of ranges of both kernels: pick_splits, dense_tiles.h).
 //
 // Which (KC, TAIL) serves which K, and what runs instead: zi_candidate in dense_tiles.h (measured assignment); the entries are in
 // dense_f32.hip, which keeps K <= 32, the float32 matrix instruction for K > 100, and a gene count that is not a multiple of 4
 // (16-byte row pieces).
-#include "dense_tiles.h"
+#include "dense_col.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -432,8 +433,7 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
                     atomicAdd(&DV[cell * K + k], (double)rs[nt][v]);
             }
         if (TAIL && !TIB) {
-            rt.x += __shfl_xor(rt.x, 32, 64); rt.y += __shfl_xor(rt.y, 32, 64);
-            rt.z += __shfl_xor(rt.z, 32, 64); rt.w += __shfl_xor(rt.w, 32, 64);
+            add_lane_halves(rt);
             if (h == 0) {
                 const int k = C::KM + (lane & 3);
 #pragma unroll
@@ -447,12 +447,9 @@ __global__ __launch_bounds__(512) void k_zi_row(float *__restrict__ D_hat, const
 }
 
 // ---- D_hat^T W ------------------------------------------------------------------------------------------------------
-// dn::k_dn_col with the tile of D_hat copied from the row-major matrix: lane l of copy q fetches 16 bytes of cell row
-// 8 q + (s >> 1) + 4 (s & 1), s = l / 8 -- the rows the two lane halves read for one register land in LDS rows of
-// different parity, i.e. on different banks.
-template <int KC, int TAIL>
-constexpr int zi_col_lds_bytes() { return 3 * Cfg<KC, TAIL>::PU * 16 + 2 * NW * 256 * 16; }
-
+// dn::k_dn_col (pipeline and shared pieces: dense_col.h) with the tile of D_hat copied from the row-major matrix: lane l of
+// copy q fetches 16 bytes of cell row 8 q + (s >> 1) + 4 (s & 1), s = l / 8 -- the rows the two lane halves read for one
+// register land in LDS rows of different parity, i.e. on different banks.
 template <int KC, int TAIL>
 __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, const u4v *__restrict__ imgU,
                                                 double *__restrict__ out, int64_t n, int64_t m, int K, int64_t nct,
@@ -497,16 +494,10 @@ __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, con
                                              (__attribute__((address_space(3))) void *)(sbuf + sslot * 2048 + q * 64), 16, 0, 0);
         }
     };
-    constexpr int NCOPY = C::PU / (NW * 64) + 4;                          // LDS-DMA instructions per wave and tile
-    static_assert(NCOPY >= 5 && NCOPY <= 7, "the waits below count the copies of one iteration");
-    auto wait_prev = [&]() {             // the previous iteration's copies have landed, this iteration's may be in flight
-        if (NCOPY == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-        else if (NCOPY == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    };
+    constexpr int NCOPY = col_copies<KC, TAIL>();
     issue(ct0, 0, 0);
     issue(ct0 + 1, 1, 1);
-    wait_prev();
+    col_wait_prev<NCOPY>();
     __builtin_amdgcn_s_barrier();
     int islot = 0, sslot = 0, since = 0;
     // register v = 4 q + e of lane (g, h) is d[cell acc_row(v, h) = 8 q + 4 h + e][gene g]: LDS row 8 q + 2 e + h
@@ -540,21 +531,16 @@ __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, con
         }
         if (TAIL) {
             const f4v *t2p = reinterpret_cast<const f4v *>(im + C::P2 + 32) + (h * 4 + (lane & 3)) * 4;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f4v t2 = t2p[q];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cta = __builtin_amdgcn_mfma_f32_4x4x1f32(sc[q][e], t2[e], cta, 0, 0, 0);
-            }
+            col_tail(t2p, sc, cta);
         }
-        if (++since == 8) {              // 256 cells: leave the matrix core
+        if (++since == COL_FLUSH) {      // 256 cells: leave the matrix core
             since = 0;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) { cs[nt][v] += dv[nt][v]; dv[nt][v] = 0.f; }
         }
-        wait_prev();
+        col_wait_prev<NCOPY>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         islot = (islot == 2) ? 0 : islot + 1;
@@ -571,8 +557,7 @@ __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, con
             if (gene < m && k < C::KM && k < K) atomicAdd(&out[gene * K + k], (double)cs[nt][v] + (double)dv[nt][v]);
         }
     if (TAIL) {
-        cta.x += __shfl_xor(cta.x, 32, 64); cta.y += __shfl_xor(cta.y, 32, 64);
-        cta.z += __shfl_xor(cta.z, 32, 64); cta.w += __shfl_xor(cta.w, 32, 64);
+        add_lane_halves(cta);
         if (h == 0) {
             const int k = C::KM + (lane & 3);
 #pragma unroll
@@ -582,21 +567,6 @@ __global__ __launch_bounds__(512) void k_zi_col(const float *__restrict__ D, con
             }
         }
     }
-}
-
-// work-groups of 512 threads, one per CU: the split count that leaves the last round of the chip fullest (fewer on ties)
-static int64_t zi_pick_splits(int64_t blocks, int64_t max_splits) {
-    const int64_t cus = oriana_device_cus();                 // (256 on MI355X)
-    int64_t best = 1;
-    double best_eff = 0.0;
-    for (int64_t sp = 1; sp <= max_splits && sp <= 64; ++sp) {
-        const int64_t groups = blocks * sp;
-        if (groups > 16 * cus && sp > 1) break;
-        const int64_t rounds = (groups + cus - 1) / cus;
-        const double eff = (double)groups / (double)(rounds * cus);
-        if (eff > best_eff + 0.03) { best_eff = eff; best = sp; }
-    }
-    return best;
 }
 
 // floats of scratch for the gene-side images of m genes / the cell-side images of n cells (largest configuration)
@@ -648,7 +618,7 @@ static int zi_sweep_launch(KcTl cfg, float *D_hat, const double *U, const double
                            float *img_scratch, int64_t n, int64_t m, int K, hipStream_t st) {
     const int ngt = (int)((m + 31) / 32);
     const int64_t blocks = ((n + 31) / 32 + NW - 1) / NW;
-    int64_t splits = zi_pick_splits(blocks, (ngt + 7) / 8);
+    int64_t splits = pick_splits(blocks, (ngt + 7) / 8, SPLITS_TILES);
     const int per = (int)((ngt + splits - 1) / splits);
     splits = (ngt + per - 1) / per;
     if (blocks > 0x7fffffffLL || splits > 65535) return ORIANA_EINVAL;
@@ -680,7 +650,7 @@ int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch
     const int ngt = (int)((m + 31) / 32);
     const int64_t nct = (n + 31) / 32;
     const int64_t groups = (ngt + NW - 1) / NW;
-    int64_t splits = zi_pick_splits(groups, (nct + 15) / 16);
+    int64_t splits = pick_splits(groups, (nct + 15) / 16, SPLITS_TILES);
     const int64_t per = (nct + splits - 1) / splits;
     splits = (nct + per - 1) / per;
     if (splits * groups > 0x7fffffffLL) return ORIANA_EINVAL;
@@ -692,7 +662,7 @@ int zi_dt(KcTl cfg, double *out, const float *D, const double *W, float *scratch
         } else {
             const int rc = launch(k_zi_images<KC, TL, false>, dim3((unsigned)nct), dim3(512), 0, st, img, nullptr, W, n, K);
             if (rc) return rc;
-            return launch(k_zi_col<KC, TL>, dim3((unsigned)(splits * groups)), dim3(512), (size_t)zi_col_lds_bytes<KC, TL>(), st,
+            return launch(k_zi_col<KC, TL>, dim3((unsigned)(splits * groups)), dim3(512), (size_t)col_lds_bytes<KC, TL>(), st,
                           D, img, out, n, m, K, nct, ngt, per, (int)splits);
         }
     });
