@@ -1180,6 +1180,41 @@ int oriana_louvain_sweep(int64_t n, const int64_t *row_ptr, const int32_t *cols,
                          int64_t row_cap, const int32_t *long_rows, const int64_t *long_off, int64_t n_long, void *scratch,
                          int64_t scratch_bytes, int32_t *comm_new, int64_t *moved, int32_t *overflow, int64_t blocks, void *stream);
 
+/* ---- diffusion maps on the neighbour graph (csrc/diffusion.hip, oriana_amd/cluster.py: diffusion_graph, diffusion_map; DESIGN.md
+ * 5p; no counterpart in the reference) -------------------------------------------------------------------------------------------
+ * All float64, no float atomics: every result is the same bits for every `blocks` (0: sized from the device), for whatever a
+ * scratch held, and on repetition.
+ * oriana_csr_spmv_f64 : y = A x, A in CSR (row_ptr (n + 1) int64, cols int32, vals float64; x and y hold n entries).  A row is
+ *   served by an aligned group of 16 lanes: lane l adds the entries l, l + 16, ... of the row as one ascending fma chain starting
+ *   from 0, then the 16 sums are added by lane ^ 1, lane ^ 2 and the two mirrors inside the group.  An entry whose column lies
+ *   outside [0, n) addresses nothing and adds nothing.  n < 0 or beyond 2^31 - 1, negative blocks, with n > 0 a NULL row_ptr / x /
+ *   y -> ORIANA_EINVAL before any HIP call; n = 0 is a no-op.
+ * A basis Q holds its columns contiguously: column c starts at Q + c * ldq, ldq >= n and even, Q 16-byte aligned.
+ * oriana_basis_orthogonalize_f64 : classical Gram-Schmidt of w (n, 16-byte aligned) against the first j columns of Q, `passes`
+ *   (1 or 2) times: c = Q^T w, w <- w - Q c, h <- h + c (h holds j entries and is ADDED to: the caller zeroes it for a new w);
+ *   then beta2[0] = ||w||^2.  Sums over rows run over tiles of oriana_basis_tile_rows() rows (a function of nothing): inside a tile
+ *   each lane adds its rows as an ascending fma chain and the wave's lanes are added in a fixed order; the tiles are added in
+ *   ascending order.  The subtraction is one fma per column, columns ascending.  Q is read twice per pass.
+ *   scratch: oriana_basis_orthogonalize_scratch_bytes_for(n, j) bytes, 16-byte aligned, contents undefined on entry and exit,
+ *   nothing written outside it; a scratch_bytes below that size -> ORIANA_EINVAL.
+ * oriana_basis_append_f64 : column j of Q (j >= 0) = w / sqrt(beta2[0]), the root and the quotients correctly rounded; beta2 is
+ *   read on the device.
+ * oriana_basis_combine_f64 : out = Q S for S (j, m) row-major; out holds its m columns like a basis (ldo >= n and even, 16-byte
+ *   aligned); out[r, c] = an fma chain over k = 0 .. j - 1 ascending, starting from 0.  m = 0 is a no-op.
+ * ORIANA_EINVAL before any HIP call for a negative size or `blocks`, n beyond 2^38, j < 1 (append: j < 0) or j / m beyond 2^20,
+ * ldq < n, ldo < n or either odd, passes outside {1, 2}, and with n > 0 a NULL or misaligned Q / w / out / scratch and a NULL h /
+ * beta2 / S.  n = 0 is a no-op. */
+int oriana_csr_spmv_f64(int64_t n, const int64_t *row_ptr, const int32_t *cols, const double *vals, const double *x, double *y,
+                        int64_t blocks, void *stream);
+int64_t oriana_basis_tile_rows(void);
+/* (negative: ORIANA_EINVAL for sizes the call would refuse) */
+int64_t oriana_basis_orthogonalize_scratch_bytes_for(int64_t n, int64_t j);
+int oriana_basis_orthogonalize_f64(int64_t n, const double *Q, int64_t ldq, int64_t j, double *w, double *h, double *beta2,
+                                   int64_t passes, void *scratch, int64_t scratch_bytes, int64_t blocks, void *stream);
+int oriana_basis_append_f64(int64_t n, double *Q, int64_t ldq, int64_t j, const double *w, const double *beta2, void *stream);
+int oriana_basis_combine_f64(int64_t n, const double *Q, int64_t ldq, int64_t j, const double *S, int64_t m, double *out,
+                             int64_t ldo, int64_t blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,12 @@ _SIGS = {
     'oriana_louvain_row_cap': (_I, []),
     'oriana_louvain_sweep_scratch_bytes_for': (_I, [_I]),
     'oriana_louvain_sweep': (c_int, [_I, _P, _P, _P, _P, _I, c_double, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P]),
+    'oriana_csr_spmv_f64': (c_int, [_I, _P, _P, _P, _P, _P, _I, _P]),
+    'oriana_basis_tile_rows': (_I, []),
+    'oriana_basis_orthogonalize_scratch_bytes_for': (_I, [_I, _I]),
+    'oriana_basis_orthogonalize_f64': (c_int, [_I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P]),
+    'oriana_basis_append_f64': (c_int, [_I, _P, _I, _I, _P, _P, _P]),
+    'oriana_basis_combine_f64': (c_int, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -16,7 +16,11 @@ and a gradient whose repulsive term is all n^2 pairs by brute force -- no tree, 
 
 louvain() is a deterministic Louvain clustering of the graph snn_graph() forms from the neighbour lists of knn()
 (csrc/community.hip): integer weights, every node of a sweep decides from the old state, so a labelling is a function of the
-graph alone and a NumPy restatement matches it label for label.  DESIGN.md section 5o."""
+graph alone and a NumPy restatement matches it label for label.  DESIGN.md section 5o.
+
+diffusion_map() is the diffusion map of the same neighbour graph (csrc/diffusion.hip): the Gaussian affinities of
+diffusion_graph(), and Lanczos with full reorthogonalisation whose sums over rows run in a fixed order, so the eigenpairs are a
+function of the graph and the start vector alone; diffusion_pseudotime() orders the cells from a root.  DESIGN.md section 5p."""
 import math
 
 import numpy as np
@@ -31,7 +35,9 @@ __all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows
            'silhouette', 'silhouette_plan', 'silhouette_from_sums', 'distance_sums', 'max_clusters', 'adjusted_rand',
            'tsne', 'tsne_plan', 'tsne_default_neighbors', 'tsne_affinities', 'tsne_joint', 'tsne_attract', 'tsne_repulse',
            'tsne_gradient', 'tsne_pca_init',
-           'snn_graph', 'louvain', 'louvain_sweep', 'louvain_plan', 'louvain_row_cap', 'modularity']
+           'snn_graph', 'louvain', 'louvain_sweep', 'louvain_plan', 'louvain_row_cap', 'modularity',
+           'diffusion_graph', 'diffusion_map', 'diffusion_pseudotime', 'graph_components', 'csr_spmv', 'basis_tile_rows',
+           'basis_orthogonalize', 'basis_append', 'basis_combine']
 
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
@@ -1086,26 +1092,23 @@ def _csr_pointers(rows, n):
     return crow
 
 
-def snn_graph(indices, weights='snn'):
-    """The symmetric weighted graph of the neighbour lists `indices`, an (n, k) int32 tensor as knn() / cell_neighbors() return it.
-    N(i) = the entries of row i inside [0, n) other than i (anything else, the -1 padding included, is skipped); {i, j} is an edge
-    iff j is in N(i) or i is in N(j).  weights : 'snn' -- w_ij = |Nc(i) & Nc(j)| with Nc(i) = N(i) and i itself, the
-    shared-neighbour count (oriana_snn_weights; needs a device tensor and k <= max_neighbors(1)); 'count' -- w_ij = [j in N(i)] +
-    [i in N(j)], formed by torch on the tensor's device.  Returns {'crow': (n + 1) int64, 'col': (nnz) int32 ascending inside a
-    row, 'weight': (nnz) int64, 'n': n}, no self entries.  ValueError for a wrong dtype or rank and (one device sort, one host
-    read) for a row that holds a valid entry twice."""
+def _check_indices(indices, weights=None):
+    """The refusals snn_graph() (with its `weights`) and diffusion_graph() share, in snn_graph()'s order."""
     if not isinstance(indices, torch.Tensor) or indices.dim() != 2 or indices.dtype != torch.int32:
         raise ValueError('indices must be an (n, k) int32 torch tensor')
-    if weights not in ('snn', 'count'):
+    if weights is not None and weights not in ('snn', 'count'):
         raise ValueError("weights must be 'snn' or 'count'")
-    n, k = int(indices.shape[0]), int(indices.shape[1])
-    if k < 1:
+    if int(indices.shape[1]) < 1:
         raise ValueError('indices must hold at least one column')
-    if weights == 'snn':
-        if k > max_neighbors(1):
-            raise ValueError('%d neighbours per row exceed the %d served' % (k, max_neighbors(1)))
-        if not indices.is_cuda:
-            raise ValueError("weights='snn' needs a device tensor")
+
+
+def _neighbour_pattern(indices):
+    """The symmetric pattern of the neighbour lists `indices` ((n, k) int32, checked by _check_indices), for snn_graph() and
+    diffusion_graph(): N(i) = the entries of row i inside [0, n) other than i; {i, j} is stored iff j is in N(i) or i is in N(j).
+    Returns {'valid': (n, k) bool, 'r', 'c': the (row, neighbour) of every valid entry in row-major order, int64, 'key': the stored
+    pairs as row * n + column, ascending, 'count': per stored pair [j in N(i)] + [i in N(j)], 'rows' int64, 'col' int32, 'crow'}.
+    ValueError (one device sort, one host read) for a row that holds a valid entry twice."""
+    n, k = int(indices.shape[0]), int(indices.shape[1])
     dev = indices.device
     idx = indices.to(torch.int64)
     me = torch.arange(n, device=dev, dtype=torch.int64)[:, None]
@@ -1118,7 +1121,27 @@ def snn_graph(indices, weights='snn'):
     key, cnt = torch.unique(torch.cat([r * n + c, c * n + r]), return_counts=True)        # (sorted: rows, then columns, ascend)
     rows = torch.div(key, max(n, 1), rounding_mode='floor')
     col = (key - rows * n).to(torch.int32).contiguous()
-    crow = _csr_pointers(rows, n)
+    return {'valid': valid, 'r': r, 'c': c, 'key': key, 'count': cnt, 'rows': rows, 'col': col, 'crow': _csr_pointers(rows, n)}
+
+
+def snn_graph(indices, weights='snn'):
+    """The symmetric weighted graph of the neighbour lists `indices`, an (n, k) int32 tensor as knn() / cell_neighbors() return it.
+    N(i) = the entries of row i inside [0, n) other than i (anything else, the -1 padding included, is skipped); {i, j} is an edge
+    iff j is in N(i) or i is in N(j).  weights : 'snn' -- w_ij = |Nc(i) & Nc(j)| with Nc(i) = N(i) and i itself, the
+    shared-neighbour count (oriana_snn_weights; needs a device tensor and k <= max_neighbors(1)); 'count' -- w_ij = [j in N(i)] +
+    [i in N(j)], formed by torch on the tensor's device.  Returns {'crow': (n + 1) int64, 'col': (nnz) int32 ascending inside a
+    row, 'weight': (nnz) int64, 'n': n}, no self entries.  ValueError for a wrong dtype or rank and (one device sort, one host
+    read) for a row that holds a valid entry twice."""
+    _check_indices(indices, weights if weights is not None else '')
+    n, k = int(indices.shape[0]), int(indices.shape[1])
+    if weights == 'snn':
+        if k > max_neighbors(1):
+            raise ValueError('%d neighbours per row exceed the %d served' % (k, max_neighbors(1)))
+        if not indices.is_cuda:
+            raise ValueError("weights='snn' needs a device tensor")
+    dev = indices.device
+    pat = _neighbour_pattern(indices)
+    crow, col, cnt = pat['crow'], pat['col'], pat['count']
     if weights == 'count':
         w = cnt.to(torch.int64).contiguous()
     else:
@@ -1134,16 +1157,18 @@ def _graph_rows(crow, n):
     return torch.repeat_interleave(torch.arange(n, device=crow.device, dtype=torch.int64), crow[1:] - crow[:-1])
 
 
-def _check_graph(graph):
+def _check_graph(graph, weight_dtype=torch.int64):
     """The validated graph: (crow, col, weight, n, rows, deg, two_m).  One torch check (one host read) for the pointers, the
-    order inside the rows, the symmetry of pattern and weights and the sign of the weights."""
+    order inside the rows, the symmetry of pattern and weights and the sign of the weights.  weight_dtype : torch.int64 for the
+    graphs of snn_graph(), torch.float64 for those of diffusion_graph(): their weights must be finite as well, and deg and two_m
+    are None (a float sum by index_add_ has no fixed bits: the row sums of such a graph are oriana_csr_spmv_f64's)."""
     if not isinstance(graph, dict) or not all(a in graph for a in ('crow', 'col', 'weight', 'n')):
         raise ValueError("graph must be a dict with 'crow', 'col', 'weight' and 'n', as snn_graph() returns it")
     crow, col, w, n = graph['crow'], graph['col'], graph['weight'], int(graph['n'])
     if not all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in (crow, col, w)):
         raise ValueError('crow, col and weight must be 1-D torch tensors')
-    if crow.dtype != torch.int64 or col.dtype != torch.int32 or w.dtype != torch.int64:
-        raise ValueError('crow must be int64, col int32 and weight int64')
+    if crow.dtype != torch.int64 or col.dtype != torch.int32 or w.dtype != weight_dtype:
+        raise ValueError('crow must be int64, col int32 and weight %s' % str(weight_dtype).replace('torch.', ''))
     if n < 0 or int(crow.numel()) != n + 1 or col.numel() != w.numel():
         raise ValueError('crow must hold n + 1 pointers, col and weight one entry per stored pair')
     if not (crow.device == col.device == w.device):
@@ -1162,17 +1187,24 @@ def _check_graph(graph):
     order = torch.argsort(back)
     flags = [((c64 < 0) | (c64 >= n)).any(), (key[1:] <= key[:-1]).any(), (back[order] != key).any(), (w[order] != w).any(),
              (w < 0).any()]
-    deg = torch.zeros(n, dtype=torch.int64, device=w.device).index_add_(0, rows, w) if nnz else \
+    exact = weight_dtype == torch.int64
+    if not exact:
+        flags[4] = flags[4] | ~torch.isfinite(w).all()
+    deg = torch.zeros(n, dtype=torch.int64, device=w.device).index_add_(0, rows, w) if nnz and exact else \
         torch.zeros(n, dtype=torch.int64, device=w.device)
     bad = torch.stack(flags).cpu() if nnz else torch.zeros(5, dtype=torch.bool)
     if bool(bad[0]):
         raise ValueError('a column lies outside [0, n)')
     if bool(bad[1]):
         raise ValueError('the columns of a row must ascend strictly (an unsorted graph)')
+    if not exact and bool(bad[4]):                                 # (ahead of the symmetry: NaN differs from itself)
+        raise ValueError('the weights must be finite and not negative')
     if bool(bad[2]) or bool(bad[3]):
         raise ValueError('the graph must be symmetric in pattern and weights (an asymmetric graph)')
     if bool(bad[4]):
         raise ValueError('the weights must not be negative')
+    if not exact:
+        return crow, col, w, n, rows, None, None
     two_m = int(w.to(torch.float64).sum()) if nnz else 0           # (a first look that cannot wrap)
     if two_m > LOUVAIN_MAX_2M:
         raise ValueError('the weights sum to 2m = %d: (2m)^2 must stay below 2^63 (2m <= %d)' % (two_m, LOUVAIN_MAX_2M))
@@ -1346,3 +1378,309 @@ def louvain(graph, resolution=1.0, max_sweeps=64, max_levels=32, row_cap=None, b
     rank = torch.empty(C, dtype=torch.int64, device=dev)
     rank[order] = torch.arange(C, device=dev)
     return {'labels': rank[labels].to(torch.int32), 'n_communities': C, 'modularity': levels[-1]['modularity'], 'levels': levels}
+
+
+# ---- diffusion maps on the neighbour graph (csrc/diffusion.hip) --------------------------------------------------
+def basis_tile_rows():
+    """The rows of one partial sum of oriana_basis_orthogonalize_f64: a constant of the library."""
+    return int(_lib.load().oriana_basis_tile_rows())
+
+
+def _f64_device(t, least, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda \
+            or int(t.numel()) < least:
+        raise ValueError('%s must be a contiguous 1-D float64 device tensor of at least %d entries' % (what, least))
+
+
+def _check_basis(Q, n, j, what='Q'):
+    """A basis is a (columns, ld) float64 device tensor, contiguous: column c is row c of the tensor, ld >= n and even."""
+    if not isinstance(Q, torch.Tensor) or Q.dtype != torch.float64 or Q.dim() != 2 or not Q.is_contiguous() or not Q.is_cuda:
+        raise ValueError('%s must be a contiguous (columns, ld) float64 device tensor' % what)
+    if n < 0 or int(Q.shape[1]) < n or int(Q.shape[1]) % 2 or not 0 <= j <= int(Q.shape[0]):
+        raise ValueError('%s must hold %d columns of ld >= %d entries, ld even' % (what, j, n))
+
+
+def csr_spmv(crow, col, val, x, out=None, blocks=0):
+    """y = A x by oriana_csr_spmv_f64 for the CSR matrix (crow (n + 1) int64, col int32, val float64) and x of at least n entries,
+    device tensors; nothing of the matrix is checked.  A row's sum depends on the row alone: `blocks` changes no bit.  Returns y
+    ((n,) float64; `out` if given)."""
+    n = int(crow.numel()) - 1
+    if crow.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float64 or col.numel() != val.numel() or n < 0 \
+            or not (crow.is_cuda and crow.is_contiguous() and col.is_contiguous() and val.is_contiguous()) or int(blocks) < 0:
+        raise ValueError('crow must be int64, col int32 and val float64, contiguous device tensors, and blocks >= 0')
+    _f64_device(x, n, 'x')
+    y = torch.empty(n, dtype=torch.float64, device=crow.device) if out is None else out
+    _f64_device(y, n, 'out')
+    nnz = int(col.numel())
+    call('oriana_csr_spmv_f64', n, ptr(crow), ptr(col) if nnz else None, ptr(val) if nnz else None, ptr(x) if n else None,
+         ptr(y) if n else None, int(blocks), stream_ptr())
+    return y
+
+
+def basis_orthogonalize(Q, n, j, w, h, beta2, passes=2, blocks=0, scratch=None):
+    """One oriana_basis_orthogonalize_f64 call: `passes` (1 or 2) rounds of c = Q[:j] w, w -= Q[:j]^T c, h[:j] += c in place, then
+    beta2[0] = ||w||^2, everything on the device.  Q : a basis as _check_basis() states it (column c is Q[c]); w at least n
+    entries, h at least j (ADDED to: zero it for a new w), beta2 at least one.  scratch : a uint8 device tensor of at least
+    oriana_basis_orthogonalize_scratch_bytes_for(n, j) bytes, contents undefined.  `blocks` changes no bit."""
+    n, j = int(n), int(j)
+    _check_basis(Q, n, j)
+    if j < 1 or int(passes) not in (1, 2) or int(blocks) < 0:
+        raise ValueError('j >= 1, passes 1 or 2 and blocks >= 0 are required')
+    _f64_device(w, n, 'w')
+    _f64_device(h, j, 'h')
+    _f64_device(beta2, 1, 'beta2')
+    need = _scratch_bytes('oriana_basis_orthogonalize_scratch_bytes_for', n, j)
+    scratch = _scratch_for(scratch, need, Q.device)
+    call('oriana_basis_orthogonalize_f64', n, ptr(Q), int(Q.shape[1]), j, ptr(w), ptr(h), ptr(beta2), int(passes), ptr(scratch),
+         int(scratch.numel() * scratch.element_size()), int(blocks), stream_ptr())
+
+
+def basis_append(Q, n, j, w, beta2):
+    """Q[j] = w / sqrt(beta2[0]) by oriana_basis_append_f64; beta2 is read on the device."""
+    n, j = int(n), int(j)
+    _check_basis(Q, n, j + 1)
+    _f64_device(w, n, 'w')
+    _f64_device(beta2, 1, 'beta2')
+    call('oriana_basis_append_f64', n, ptr(Q), int(Q.shape[1]), j, ptr(w), ptr(beta2), stream_ptr())
+
+
+def basis_combine(Q, n, j, S, out=None, blocks=0):
+    """out[c] = sum_k S[k, c] Q[k] over k = 0 .. j - 1 ascending (one fma chain per element) by oriana_basis_combine_f64: S a
+    (j, m) float64 device tensor, out a basis of m columns (a new one of ld = Q's if absent).  Returns out."""
+    n, j = int(n), int(j)
+    _check_basis(Q, n, j)
+    if not isinstance(S, torch.Tensor) or S.dtype != torch.float64 or S.dim() != 2 or int(S.shape[0]) != j or not S.is_contiguous() \
+            or not S.is_cuda or j < 1 or int(blocks) < 0:
+        raise ValueError('S must be a contiguous (j, m) float64 device tensor with j >= 1, and blocks >= 0')
+    m = int(S.shape[1])
+    if out is None:
+        out = torch.empty(m, int(Q.shape[1]), dtype=torch.float64, device=Q.device)
+    _check_basis(out, n, m, 'out')
+    call('oriana_basis_combine_f64', n, ptr(Q), int(Q.shape[1]), j, ptr(S) if m else None, m, ptr(out) if m else None,
+         int(out.shape[1]), int(blocks), stream_ptr())
+    return out
+
+
+def diffusion_graph(indices, sq_distances, blocks=0):
+    """The symmetric diffusion transition matrix of the neighbour lists (indices, sq_distances), (n, k) int32 / float32 device
+    tensors as knn() / cell_neighbors() return them (padded with -1 / inf), after Haghverdi et al. 2016 (scanpy's
+    ``method='gauss'``), everything in float64.
+
+    Pattern : that of snn_graph(): {i, j} is stored iff j is in N(i) or i is in N(j), no self entries, columns ascending.
+    d2{i, j} : the value row min(i, j) stores for the other node if it lists it, else the value of row max(i, j): the same bits
+        in both directions for any input.
+    sigma_i^2 : np.median of the valid squared distances of row i (an even count: the mean of the two middle values); a zero
+        median is replaced by the row's smallest positive valid value.
+    W_ij = sqrt(2 sigma_i sigma_j / (sigma_i^2 + sigma_j^2)) exp(-d2_ij / (sigma_i^2 + sigma_j^2)); q = W 1, K_ij = W_ij /
+    (q_i q_j); z = K 1, T_ij = K_ij / sqrt(z_i z_j).  The elementwise steps are float64 torch; the two row sums are
+    oriana_csr_spmv_f64 applied to ones (no atomics: fixed bits; `blocks` changes none).
+
+    Returns {'crow': (n + 1) int64, 'col': (nnz) int32, 'weight': (nnz) float64 the entries of T, bit-symmetric, 'n', 'z': (n)
+    float64}.  ValueError for wrong dtypes, shapes or devices, a row that holds a neighbour twice, a valid entry whose distance is
+    negative or not finite, and (stating their number) for rows without any positive valid distance."""
+    _check_indices(indices)
+    if not isinstance(sq_distances, torch.Tensor) or sq_distances.dtype != torch.float32 or sq_distances.shape != indices.shape \
+            or sq_distances.device != indices.device:
+        raise ValueError('sq_distances must be a float32 torch tensor of the shape and on the device of indices')
+    if not indices.is_cuda:
+        raise ValueError('diffusion_graph() needs device tensors')
+    if int(blocks) < 0:
+        raise ValueError('blocks >= 0 is required')
+    n, k = int(indices.shape[0]), int(indices.shape[1])
+    dev = indices.device
+    pat = _neighbour_pattern(indices)
+    valid, r, c, key, rows, col, crow = (pat[a] for a in ('valid', 'r', 'c', 'key', 'rows', 'col', 'crow'))
+    d = sq_distances.to(torch.float64)
+    inf = torch.full_like(d, float('inf'))
+    shown = torch.where(valid, d, inf)
+    cnt = valid.sum(1)
+    srt = torch.sort(shown, dim=1).values
+    lo = torch.gather(srt, 1, (torch.clamp(cnt - 1, min=0) // 2)[:, None])[:, 0]
+    hi = torch.gather(srt, 1, torch.clamp(cnt // 2, max=k - 1)[:, None])[:, 0]
+    med = (lo + hi) / 2
+    pos = torch.where(valid & (d > 0), d, inf).min(1).values if n else med
+    sig2 = torch.where((cnt > 0) & (med > 0), med, pos)
+    dv = d[valid]
+    flags = torch.stack([(~torch.isfinite(dv) | (dv < 0)).sum(), (~torch.isfinite(sig2)).sum()]).cpu()
+    if int(flags[0]):
+        raise ValueError('%d valid entries hold a squared distance that is negative or not finite' % int(flags[0]))
+    if int(flags[1]):
+        raise ValueError('%d rows hold no positive valid squared distance: their local scale is undefined' % int(flags[1]))
+    nnz = int(col.numel())
+    own = torch.zeros(nnz, dtype=torch.float64, device=dev)        # the value row i stores for j, per stored (i, j)
+    other = torch.zeros(nnz, dtype=torch.float64, device=dev)      # the value row j stores for i
+    has_own = torch.zeros(nnz, dtype=torch.bool, device=dev)
+    has_other = torch.zeros(nnz, dtype=torch.bool, device=dev)
+    fpos, bpos = torch.searchsorted(key, r * n + c), torch.searchsorted(key, c * n + r)
+    own[fpos] = dv
+    has_own[fpos] = True
+    other[bpos] = dv
+    has_other[bpos] = True
+    c64 = col.to(torch.int64)
+    low = rows < c64                                               # row min(i, j) is this entry's own row
+    d2 = torch.where(torch.where(low, has_own, has_other), torch.where(low, own, other), torch.where(low, other, own))
+    sig = torch.sqrt(sig2)
+    den = sig2[rows] + sig2[c64]
+    W = (torch.sqrt(2 * sig[rows] * sig[c64] / den) * torch.exp(-d2 / den)).contiguous()
+    ones = torch.ones(n, dtype=torch.float64, device=dev)
+    q = csr_spmv(crow, col, W, ones, blocks=blocks)
+    K = (W / (q[rows] * q[c64])).contiguous()
+    z = csr_spmv(crow, col, K, ones, blocks=blocks)
+    T = (K / torch.sqrt(z[rows] * z[c64])).contiguous()
+    return {'crow': crow, 'col': col, 'weight': T, 'n': n, 'z': z}
+
+
+def graph_components(graph):
+    """The connected components of a symmetric graph as snn_graph() or diffusion_graph() returns it, an entry of weight zero
+    counting as absent: minimum-label propagation with pointer jumping in integer torch on the graph's device (one host read per
+    round).  Returns {'labels': (n,) int64, the components numbered by their smallest member, 'n_components'}."""
+    w = graph.get('weight') if isinstance(graph, dict) else None
+    floats = isinstance(w, torch.Tensor) and w.dtype == torch.float64
+    crow, col, w, n, rows, _, _ = _check_graph(graph, torch.float64 if floats else torch.int64)
+    keep = w != 0
+    a, b = rows[keep], col.to(torch.int64)[keep]
+    lab = torch.arange(n, device=crow.device, dtype=torch.int64)
+    while n:
+        new = lab.clone().scatter_reduce_(0, a, lab[b], 'amin')                     # the least label among a node and its neighbours
+        new = torch.minimum(new, lab.clone().scatter_reduce_(0, lab, new, 'amin')[lab])     # ... handed to the node's representative
+        new = new[new]
+        if bool((new == lab).all()):
+            break
+        lab = new
+    uniq, inv = torch.unique(lab, return_inverse=True)                              # (ascending: by the smallest member)
+    return {'labels': inv, 'n_components': int(uniq.numel())}
+
+
+def _ritz(alpha, beta, m):
+    """Of the Lanczos matrix (diagonal alpha, off-diagonal beta[:-1]): the m largest Ritz values, descending, their vectors
+    (steps, m) and the residual estimates |beta[-1] s_last|."""
+    steps = alpha.size
+    Tm = np.diag(alpha)
+    if steps > 1:
+        Tm += np.diag(beta[:-1], 1) + np.diag(beta[:-1], -1)
+    theta, S = np.linalg.eigh(Tm)
+    top = np.argsort(-theta, kind='stable')[:m]
+    return theta[top], np.ascontiguousarray(S[:, top]), np.abs(beta[-1] * S[-1, top])
+
+
+def diffusion_map(graph, n_comps=15, tol=1e-8, max_steps=None, check_every=10, seed=0, start=None, blocks=0, pg=None):
+    """The n_comps leading eigenpairs of the symmetric transition matrix T of diffusion_graph(): Lanczos with full
+    reorthogonalisation, no restarts, float64 on the device (csrc/diffusion.hip).
+
+    q_0 is `start` ((n,) float64) normalised, or without one ``torch.randn(n, float64)`` of a CPU generator seeded with `seed`.
+    Step j: w = T q_j (oriana_csr_spmv_f64), w is orthogonalised against q_0 .. q_j by classical Gram-Schmidt applied twice
+    (oriana_basis_orthogonalize_f64; alpha_j is the coefficient on q_j, beta_j = ||w||), q_{j+1} = w / beta_j is appended; nothing
+    is read on the host.  Every `check_every` steps, and at the last, the host reads alpha and beta, takes numpy.linalg.eigh of the
+    tridiagonal matrix and stops when |beta_j s_{last,l}| <= tol for the n_comps largest Ritz pairs.  The Ritz vectors are Q S
+    (oriana_basis_combine_f64).  Every sum over rows has a fixed order: the result is a function of the graph and the start alone,
+    the same bits for every `blocks` and on repetition.
+
+    max_steps : default min(n, 1000), never more than n; the basis takes 8 ld (max_steps + 1) bytes (ld = n rounded up to even).
+        The step count GROWS with n -- seeded blobs on the CPU: n = 2,000: 160 steps to tol 1e-6 / 180 to 1e-9; 20,000: 320 /
+        360; 60,000: 430 / 480; a path of 20,000 nodes needs 150.  Not converged at max_steps is reported, not an error.
+    A single vector cannot see the multiplicity of the eigenvalue 1 on a disconnected graph: graph_components() runs first (an
+    entry of weight zero counts as absent) and more than one component is a ValueError that states their number.
+
+    Returns {'eigenvalues': (m,) float64 NumPy, descending, 'components': (n, m) float64 device tensor, each column of unit norm
+    (to the orthonormality of the basis) with its entry of largest magnitude positive (the smallest index on ties), 'residuals':
+    (m,) the estimates of the last check, 'steps', 'converged'}.
+    ValueError for a graph _check_graph() refuses or that lives on the host, n_comps outside [1, min(n, max_steps)], a start of
+    the wrong shape or one that is zero or not finite; NotImplementedError for a process group of more than one rank."""
+    if odist.world_size(pg) > 1:
+        raise NotImplementedError('diffusion_map() is not implemented for a process group of more than one rank: gather the graph first')
+    crow, col, w, n, rows, _, _ = _check_graph(graph, torch.float64)
+    if not crow.is_cuda:
+        raise ValueError('the graph must live on the device')
+    if n < 1:
+        raise ValueError('the graph has no nodes')
+    dev = crow.device
+    max_steps = min(n, 1000) if max_steps is None else int(max_steps)
+    n_comps, check_every, blocks, tol = int(n_comps), int(check_every), int(blocks), float(tol)
+    if max_steps < 1 or check_every < 1 or blocks < 0 or not tol >= 0.0:
+        raise ValueError('max_steps >= 1, check_every >= 1, blocks >= 0 and tol >= 0 are required')
+    max_steps = min(max_steps, n)
+    if not 1 <= n_comps <= max_steps:
+        raise ValueError('n_comps must lie within [1, min(n, max_steps)] = [1, %d]' % max_steps)
+    if start is None:
+        gen = torch.Generator()
+        gen.manual_seed(int(seed))
+        v = torch.randn(n, dtype=torch.float64, generator=gen).to(dev)
+    else:
+        v = torch.as_tensor(start)
+        if v.dim() != 1 or int(v.numel()) != n:
+            raise ValueError('start must hold %d entries' % n)
+        v = v.to(dev, torch.float64).contiguous().clone()
+        if not bool(torch.isfinite(v).all()) or not bool((v != 0).any()):
+            raise ValueError('start must be finite and not zero')
+    comps = graph_components(graph)['n_components']
+    if comps > 1:
+        raise ValueError('the graph has %d connected components: a diffusion map is defined on a connected graph' % comps)
+    ld = n + (n & 1)
+    Q = torch.empty(max_steps + 1, ld, dtype=torch.float64, device=dev)
+    scratch = torch.empty(_scratch_bytes('oriana_basis_orthogonalize_scratch_bytes_for', n, max_steps), dtype=torch.uint8, device=dev)
+    alpha = torch.zeros(max_steps, dtype=torch.float64, device=dev)
+    beta2 = torch.zeros(max_steps + 1, dtype=torch.float64, device=dev)
+    # q_0: against a zero column the orthogonalisation changes nothing and leaves ||start||^2 in the kernels' own order
+    Q[0].zero_()
+    basis_orthogonalize(Q, n, 1, v, torch.zeros(1, dtype=torch.float64, device=dev), beta2[max_steps:], passes=1, blocks=blocks,
+                        scratch=scratch)
+    basis_append(Q, n, 0, v, beta2[max_steps:])
+    wv = torch.empty(ld, dtype=torch.float64, device=dev)
+    theta = S = res = None
+    steps, converged = 0, False
+    for s in range(max_steps):
+        s0 = s - s % check_every
+        if s == s0:
+            H = torch.zeros(min(check_every, max_steps - s0), max_steps, dtype=torch.float64, device=dev)    # the h of each step
+        csr_spmv(crow, col, w, Q[s], out=wv, blocks=blocks)
+        basis_orthogonalize(Q, n, s + 1, wv, H[s - s0], beta2[s:], passes=2, blocks=blocks, scratch=scratch)
+        basis_append(Q, n, s + 1, wv, beta2[s:])
+        if s + 1 - s0 < int(H.shape[0]):
+            continue
+        at = torch.arange(int(H.shape[0]), device=dev)
+        alpha[s0:s + 1] = H[at, s0 + at]
+        a, b2 = alpha[:s + 1].cpu().numpy(), beta2[:s + 1].cpu().numpy()
+        steps = s + 1
+        broke = np.flatnonzero(~(b2 > 0))                          # (beta = 0, or not a number: the Krylov space ended there)
+        if broke.size:
+            steps = int(broke[0]) + 1
+            b2 = np.where(b2 > 0, b2, 0.0)
+        if steps < n_comps:
+            if broke.size:
+                raise ValueError('the Krylov space of the start vector has %d dimensions, fewer than n_comps' % steps)
+            continue
+        theta, S, res = _ritz(a[:steps], np.sqrt(b2[:steps]), n_comps)
+        converged = bool((res <= tol).all())
+        if converged or broke.size:
+            break
+    out = basis_combine(Q, n, steps, torch.as_tensor(S).to(dev), blocks=blocks)
+    psi = out[:, :n].t().contiguous()
+    mag = psi.abs()
+    first = torch.where(mag == mag.max(0).values, torch.arange(n, device=dev)[:, None], n).min(0).values
+    sign = torch.where(psi.gather(0, first[None, :]) < 0, -1.0, 1.0).to(torch.float64)
+    return {'eigenvalues': theta, 'components': psi * sign, 'residuals': res, 'steps': steps, 'converged': converged}
+
+
+def diffusion_pseudotime(eigenvalues, components, root):
+    """Diffusion pseudotime from the cell `root` (Haghverdi et al. 2016): dpt(i) = sqrt(sum over l >= 1 with lambda_l < 1 of
+    (lambda_l / (1 - lambda_l))^2 (psi_l(i) - psi_l(root))^2), the terms added for l ascending in float64, each formed as
+    ((lambda_l / (1 - lambda_l))^2) * (d * d) with every product rounded: torch on the device of `components`, one small step per
+    term, no reduction whose order is open.  eigenvalues (m,), components (n, m) as diffusion_map() returns them.  Returns
+    {'dpt': (n,) float64, 'pseudotime': dpt / max dpt (dpt itself where that is 0)}."""
+    lam = np.asarray(eigenvalues, dtype=np.float64)
+    if not isinstance(components, torch.Tensor) or components.dtype != torch.float64 or components.dim() != 2 or lam.ndim != 1 \
+            or int(components.shape[1]) != lam.size:
+        raise ValueError('eigenvalues must be (m,) and components an (n, m) float64 torch tensor')
+    n = int(components.shape[0])
+    if isinstance(root, bool) or not isinstance(root, (int, np.integer)) or not 0 <= int(root) < n:
+        raise ValueError('root must be a cell index within [0, %d)' % n)
+    acc = torch.zeros(n, dtype=torch.float64, device=components.device)
+    for l in range(1, lam.size):
+        if not lam[l] < 1.0:
+            continue
+        wl = lam[l] / (1.0 - lam[l])
+        d = components[:, l] - components[int(root), l]
+        acc = acc + (d * d) * float(wl * wl)
+    dpt = torch.sqrt(acc)
+    top = dpt.max() if n else None
+    return {'dpt': dpt, 'pseudotime': dpt / top if n and float(top) > 0 else dpt.clone()}

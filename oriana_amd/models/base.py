@@ -1022,6 +1022,65 @@ class FactorModel:
             gi = torch.as_tensor(np.asarray(gi) if not isinstance(gi, torch.Tensor) else gi).to(self.device, torch.int32).contiguous()
         return cluster.louvain(cluster.snn_graph(gi, weights), resolution=resolution, pg=self.pg, **louvain_kw)
 
+    def cell_diffusion(self, n_comps=15, n_neighbors=15, features='log_mean', factors=None, graph=None, **diffusion_kw):
+        """The diffusion map of the cells (scanpy's ``diffmap``): the n_comps leading eigenpairs of the symmetric transition
+        matrix (cluster.diffusion_graph) of the n_neighbors nearest neighbours on the feature matrix cluster_cells() uses, by
+        Lanczos on the device (cluster.diffusion_map; its keywords tol, max_steps, check_every, seed, start and blocks pass
+        through).  Deterministic: a function of the features and the start vector alone.
+
+        graph : ``(indices, sq_distances)`` as cell_neighbors() returned them on the same features, to spare the search (then
+        n_neighbors is the width of `indices`).  Returns the dict of cluster.diffusion_map -- 'eigenvalues' ((m,) float64 NumPy,
+        descending; the first is 1), 'components' ((n, m) float64 device tensor), 'residuals', 'steps', 'converged' -- plus
+        'features' (the (n, d) float32 matrix, NumPy) and 'factors' as cluster_cells() returns them.  A neighbour graph that is not
+        connected is a ValueError that states the number of components.  A model sharded over more than one rank raises
+        NotImplementedError.  Nothing of the model's state is written."""
+        from .. import cluster
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in diffusion_kw:
+            raise ValueError('cell_diffusion() uses the process group of the model')
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('cell_diffusion() is not implemented for a model sharded over more than one rank')
+        F = self._cell_features(features, cols)
+        if graph is None:
+            if int(n_neighbors) < 1:
+                raise ValueError('n_neighbors must be at least 1')
+            nb = cluster.knn(F, int(n_neighbors), pg=self.pg)
+            gi, gd = nb['indices'], nb['sq_distances']
+        else:
+            gi, gd = graph
+            if getattr(gi, 'ndim', 0) != 2 or int(gi.shape[0]) != self.n or tuple(getattr(gd, 'shape', ())) != tuple(gi.shape):
+                raise ValueError('graph must be (indices, sq_distances) of the %d fitted cells' % self.n)
+            gi, gd = (torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).to(self.device, dt).contiguous()
+                      for t, dt in ((gi, torch.int32), (gd, torch.float32)))
+        out = cluster.diffusion_map(cluster.diffusion_graph(gi, gd), n_comps=n_comps, pg=self.pg, **diffusion_kw)
+        out['features'] = F.cpu().numpy()
+        out['factors'] = cols
+        return out
+
+    def cell_pseudotime(self, root, diffusion=None, **diffusion_kw):
+        """Diffusion pseudotime of the cells from the cell `root` (scanpy's ``dpt`` without branch detection;
+        cluster.diffusion_pseudotime): how far along the fit's main directions of variation a cell lies from the root.
+
+        root : a cell index within [0, n).  diffusion : a cell_diffusion() result to reuse; without one cell_diffusion() is
+        called with the remaining keywords.  Returns 'dpt' and 'pseudotime' (dpt divided by its maximum), (n,) float64 device
+        tensors, 'root', and 'diffusion' (the map that was used).  A model sharded over more than one rank raises
+        NotImplementedError.  Nothing of the model's state is written."""
+        from .. import cluster
+        if 'pg' in diffusion_kw:
+            raise ValueError('cell_pseudotime() uses the process group of the model')
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('cell_pseudotime() is not implemented for a model sharded over more than one rank')
+        if isinstance(root, bool) or not isinstance(root, (int, np.integer)) or not 0 <= int(root) < self.n:
+            raise ValueError('root must be a cell index within [0, %d)' % self.n)
+        if diffusion is None:
+            diffusion = self.cell_diffusion(**diffusion_kw)
+        elif diffusion_kw:
+            raise ValueError('with diffusion= no keyword of cell_diffusion() applies: %s' % ', '.join(sorted(diffusion_kw)))
+        out = cluster.diffusion_pseudotime(diffusion['eigenvalues'], diffusion['components'], int(root))
+        out['root'] = int(root)
+        out['diffusion'] = diffusion
+        return out
+
     # ---- which genes distinguish a cluster (scanpy's rank_genes_groups(method='t-test') on the counts the model holds) --------
     # Per cluster and gene the test needs the mean, the variance and the expressing fraction of the log-normalised counts
     # y_ij = log1p(x_ij target_sum / total_i).  y = 0 wherever x = 0, so the moments are sums over the non-zero counts only:
