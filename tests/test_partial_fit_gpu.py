@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import gamma_update_reference as gr
 import svi_reference as svi
 from helpers import RTOL, err_colrel
 from test_elbo_gpu import DENSE_DENSITY, HYBRID_KS, KS, M_COLS, N_ROWS, _counts, _model, _planted
@@ -15,7 +16,10 @@ pytestmark = pytest.mark.gpu
 
 F64, F32 = torch.float64, torch.float32
 ZERO_ROW = 17                     # the all-zero row of the kernel tests' Z
-KERNEL_KS = KS + (50,)             # ... and a K that takes two factors per lane (even, no multiple of 4)
+# ... and every K of gamma_update_reference.VEC_K (each k_svi_gene_update_vec<FIN, VEC, LPR>: four, two and one factor per lane at
+# 8, 16, 32 and 64 lanes per row) with 101 and 127, odd above 64: the element-per-lane kernel, as 129
+KERNEL_KS = tuple(sorted(set(KS) | set(gr.VEC_K[4] + gr.VEC_K[2] + gr.VEC_K[1]) | {101, 127}))
+MAT_KS = (100, 50, 33, 101)        # the matrix entry: once per VEC, and the element-per-lane kernel
 
 
 # ---- 1. the kernel alone ------------------------------------------------------------------------------------------------------
@@ -30,8 +34,9 @@ def _operands(K, m=M_COLS, seed=0):
     return host, {k: torch.from_numpy(v).cuda() for k, v in host.items()}
 
 
-def _svi(d, scale, rho, F=None, R=None, nslab=1, idx=None, into=None):
-    """One oriana_svi_gene_update on clones of d's b1, b2, Z: (b1, b2, E, Elog, sums (2, K), Z)."""
+def _svi(d, scale, rho, F=None, R=None, nslab=1, idx=None, into=None, rate=None):
+    """One oriana_svi_gene_update on clones of d's b1, b2, Z: (b1, b2, E, Elog, sums (2, K), Z).  rate: an (m, K) float64 matrix
+    in place of sum_u, through oriana_svi_gene_update_mat."""
     from oriana_amd._lib import call, ptr, stream_ptr
     m, K = d['b1'].shape
     if into is None:
@@ -39,8 +44,9 @@ def _svi(d, scale, rho, F=None, R=None, nslab=1, idx=None, into=None):
     b1, b2, E, sums = into
     El = torch.empty(m, K, dtype=F32, device='cuda')
     Z = d['Z'].clone()
-    call('oriana_svi_gene_update', ptr(b1), ptr(b2), ptr(E), ptr(El), ptr(sums[0]), ptr(sums[1]), ptr(d['beta1']), ptr(d['beta2']),
-         ptr(Z), ptr(F), ptr(R), nslab, ptr(idx), ptr(d['sum_u']), float(scale), float(rho), m, K, stream_ptr())
+    call('oriana_svi_gene_update' if rate is None else 'oriana_svi_gene_update_mat', ptr(b1), ptr(b2), ptr(E), ptr(El), ptr(sums[0]),
+         ptr(sums[1]), ptr(d['beta1']), ptr(d['beta2']), ptr(Z), ptr(F), ptr(R), nslab, ptr(idx), ptr(d['sum_u'] if rate is None else rate),
+         float(scale), float(rho), m, K, stream_ptr())
     torch.cuda.synchronize()
     return b1, b2, E, El, sums, Z
 
@@ -96,6 +102,35 @@ def test_kernel_against_float64(K):
     assert torch.equal(E, E0) and torch.equal(El, El0)
     _sums_close(sums, sums0, 'K=%d' % K)
     assert torch.isfinite(E).all() and torch.isfinite(El).all()
+
+
+@pytest.mark.parametrize('K', MAT_KS)
+def test_matrix_rate_entry(K):
+    """oriana_svi_gene_update_mat: a matrix whose every row is sum_u gives the bits of the vector entry, plain and finalize form;
+    a matrix of its own gives b2 against NumPy float64 within the bound of the vector entry, and the expectations of that pair."""
+    from oriana_amd import engine
+    scale, rho = 3.7, 0.3
+    h, d = _operands(K)
+    m, Kp = M_COLS, engine.kpad(K)
+    rows = d['sum_u'][None, :].expand(m, K).contiguous()
+    g = torch.Generator(device='cuda').manual_seed(K)
+    F = torch.rand(m, Kp, device='cuda', generator=g)
+    R = torch.rand(3, m, Kp, device='cuda', generator=g) * 50
+    idx = torch.randperm(m, device='cuda', generator=g).to(torch.int32)
+    for fin in ((None, None, 1, None), (F, R, 3, idx)):
+        got, ref = _svi(d, scale, rho, *fin, rate=rows), _svi(d, scale, rho, *fin)
+        for x, y in zip(got[:4] + got[5:], ref[:4] + ref[5:]):
+            assert torch.equal(x, y)
+        _sums_close(got[4], ref[4], 'K=%d rows of sum_u' % K)
+    rate_h = np.random.default_rng(900 + K).random((m, K)) * 100
+    b1, b2, E, El, sums, Z = _svi(d, scale, rho, rate=torch.from_numpy(rate_h).cuda())
+    ref2 = np.maximum(1e-15, (1 - rho) * h['b2'] + rho * (h['beta2'][None, :] + scale * rate_h))
+    e2 = float(np.max(np.abs(b2.cpu().numpy() - ref2) / ref2))
+    print('K=%d: b2 %.3e relative to NumPy float64 (bound 1e-14)' % (K, e2))
+    assert e2 <= 1e-14 and torch.equal(b1, _svi(d, scale, rho)[0])
+    E0, El0, sums0 = _stored_pair_expectations(b1, b2)
+    assert torch.equal(E, E0) and torch.equal(El, El0)
+    _sums_close(sums, sums0, 'K=%d matrix rate' % K)
 
 
 @pytest.mark.parametrize('K', KS)

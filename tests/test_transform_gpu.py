@@ -50,12 +50,13 @@ def _check_one_update(G, Xq, a1_0, what):
 
 # ---- 1. one iteration against float64 -----------------------------------------------------------------------------------------
 
-def _cases():
+def _cases(more=()):
     return [pytest.param(K, dd, id='K%d-%s' % (K, 'hybrid' if dd else 'sliced'))
-            for K in KS for dd in ([None, DENSE_DENSITY] if K in HYBRID_KS else [None])]
+            for K in KS + tuple(more) for dd in ([None, DENSE_DENSITY] if K in HYBRID_KS else [None])]
 
 
-@pytest.mark.parametrize('K,dd', _cases())
+# (33, 50, 126: the fold-in update with one and two factors per lane -- every K of KS but 1 takes four, or the element kernel)
+@pytest.mark.parametrize('K,dd', _cases(more=(33, 50, 126)))
 def test_one_iteration_against_float64(K, dd):
     G = _fitted(K, dd)
     Xq = _counts(K + 50)
