@@ -1049,6 +1049,28 @@ int oriana_group_stats(const oriana_counts *cm, const oriana_dense *dn, const in
                        const int32_t *labels, const double *scale, int log1p_flag, int64_t C, double *out, void *stream);
 int64_t oriana_group_stats_max_groups(void);
 
+/* ---- gene-set scores: the transformed counts times a weight matrix (csrc/groupstats.hip, oriana_amd/models/base.py:
+ * gene_scores, score_genes; no counterpart in the reference) ----------------------------------------------------
+ * cm, dn, row_perm, col_perm, scale, log1p_flag: exactly as oriana_group_stats takes them.  W (m_all, S) float64, row-major, in
+ * the caller's gene order, m_all = cm->m + (dn ? dn->gd : 0); out (n, S) float64, row-major, in the caller's row order.
+ *   out[i, s] = sum over the stored counts x of cell i, gene j, of W[j, s] * y,  y as oriana_group_stats forms it,
+ * every term one acc = fma(W[j, s], y, acc) in float64.  out is WRITTEN (the caller need not zero it): every element of the
+ * (n, S) array, exactly 0 in every column for a cell without a stored count; nothing outside it.  W and out need 8-byte
+ * alignment only.  No scratch.
+ * The order of the additions is a fixed function of the two layouts and of S -- per cell: each of the 4 lanes of the sliced
+ * kernel that hold the row over its slots in tile and slot order, the 4 lanes by a butterfly; then the dense block's 8 threads
+ * of the cell, each over its genes in tile order, in thread order -- with no floating-point atomic anywhere and one writer per
+ * element and launch: the same call gives the same bits on every run, whatever the grid does.
+ *   oriana_gene_scores_max_sets  : the largest S (1024).
+ *   oriana_gene_scores_set_chunk : the sets one work-group carries (8); the chunks of a larger S are one extent of the grid, the
+ *                                  last one may be partial.
+ * ORIANA_EINVAL for a NULL cm / W / out, S < 1, a layout oriana_group_stats refuses, or a grid beyond 2^31 - 1; ORIANA_EKRANGE
+ * for S above the limit; all before any HIP call.  0 without a launch for n = 0. */
+int oriana_gene_scores(const oriana_counts *cm, const oriana_dense *dn, const int32_t *row_perm, const int32_t *col_perm,
+                       const double *scale, int log1p_flag, const double *W, int64_t S, double *out, void *stream);
+int64_t oriana_gene_scores_max_sets(void);
+int64_t oriana_gene_scores_set_chunk(void);
+
 /* ---- tie-aware rank sums of the stored counts per (cluster, gene) (csrc/ranksum.hip, oriana_amd/models/base.py:
  * cluster_rank_sums, marker_genes(method='wilcoxon'); no counterpart in the reference) ---------------------------
  * cm, dn, row_perm, col_perm, labels, scale: as oriana_group_stats takes them (col_perm the FULL ordering or NULL; the outputs

@@ -184,6 +184,9 @@ _SIGS = {
     'oriana_cell_totals': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P]),
     'oriana_group_stats': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P, c_int, _I, _P, _P]),
     'oriana_group_stats_max_groups': (_I, []),
+    'oriana_gene_scores': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, c_int, _P, _I, _P, _P]),
+    'oriana_gene_scores_max_sets': (_I, []),
+    'oriana_gene_scores_set_chunk': (_I, []),
     'oriana_rank_sums': (c_int, [ctypes.POINTER(OrianaCounts), ctypes.POINTER(OrianaDense), _P, _P, _P, _P, _I, _I, _I, _P, _I, _I,
                                  _P, _P, _P, _P, _P]),
     'oriana_rank_sums_max_groups': (_I, []),

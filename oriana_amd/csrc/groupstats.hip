@@ -222,9 +222,180 @@ __global__ __launch_bounds__(256) void k_dn_group_stats(const uint16_t *__restri
     }
 }
 
+// ---- gene-set scores: out (n, S) = Y W, Y the transformed counts, W (m_all, S) float64 (oriana_gene_scores) ---------
+// The transpose of k_group_stats: the sums run over the genes of a cell, so a cell's sums have one owner and nothing here is an
+// atomic.  The order of every sum is a function of the layouts and S alone.
+
+// The sliced layout: one work-group of 256 threads per (row block, chunk of CH sets; the chunk is the fastest index of the grid),
+// walking the ncb column tiles of the row block in order.  Per tile the 256 rows of W of the tile's genes are staged in LDS
+// through col_perm for the chunk (zeros past m and past S).  Wave w owns the slices w, w + 4, w + 8, w + 12 of every tile and
+// walks each of them 64 slots at a time (slot = iteration * 64 + row_in_slice * 4 + u: the lane's row is the same in every
+// iteration), so a lane stays with FOUR rows of the row block for the whole walk and keeps their 4 x CH accumulators in
+// registers across all tiles (acc_s = fma(W[j, s], y, acc_s)): a row has one wave, its four lanes meet by the butterfly ONCE, at
+// the end, and there is no table, no partial sum and no barrier between the waves beyond the two per tile around the staging of W.
+// The sums then pass through LDS (the buffer of W) so that thread r WRITES the row r, out[i, s0 .. s0 + cw), through row_perm.
+// walk = 0 (a layout without a stored count): zeros are written.  Static LDS: 256 * CH * 8 bytes.
+template <int CH>
+__global__ __launch_bounds__(256) void k_gene_scores(oriana_counts cm, const double *__restrict__ scale, int lg,
+                                                     const double *__restrict__ W, int64_t S, int64_t joff, int nchunk, int walk,
+                                                     double *__restrict__ out) {
+    __shared__ __align__(16) double wl[TILE * CH];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), rl = (tid & 63) >> 2, u = tid & 3;
+    const int chunk = (int)(blockIdx.x % (unsigned)nchunk);
+    const int64_t rb = blockIdx.x / (unsigned)nchunk;
+    const int64_t s0c = (int64_t)chunk * CH;
+    const int cw = (int)min((int64_t)CH, S - s0c);
+    double sc[4], acc[4][CH];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t ip = rb * TILE + (4 * q + wave) * 16 + rl;
+        sc[q] = 1.0;
+        if (scale && ip < cm.n) sc[q] = scale[cm.row_perm ? (int64_t)cm.row_perm[ip] : ip];
+#pragma unroll
+        for (int s = 0; s < CH; ++s) acc[q][s] = 0.0;
+    }
+    const int64_t ncb = walk ? cm.ncb : 0;
+    for (int64_t cb = 0; cb < ncb; ++cb) {
+        __syncthreads();                                         // (the last tile's rows of W are done with)
+        {
+            const int64_t jp = cb * TILE + tid;
+            const double *w = nullptr;
+            if (jp < cm.m) w = W + (cm.col_perm ? (int64_t)cm.col_perm[jp] : jp + joff) * S + s0c;
+#pragma unroll
+            for (int s = 0; s < CH; ++s) wl[tid * CH + s] = (w && s < cw) ? w[s] : 0.0;
+        }
+        __syncthreads();
+        const int64_t t = rb * cm.ncb + cb;
+        const int64_t rbase = cm.roff[t];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int sl = 4 * q + wave;
+            const uint32_t s0 = cm.rslice[t * 17 + sl], s1 = cm.rslice[t * 17 + sl + 1];
+            // (a slice's length is a multiple of 64: the lanes of the wave leave the loop together)
+            for (uint32_t slot = s0 + (tid & 63); slot < s1; slot += 64) {
+                const oriana_rowrec rec = cm.rowrec[rbase + slot];
+                if (rec.x == 0.f) continue;
+                const double y = gs_value((double)rec.x, scale, sc[q], lg);
+                const double *w = wl + (int)rec.col * CH;
+#pragma unroll
+                for (int s = 0; s < CH; ++s) acc[q][s] = fma(w[s], y, acc[q][s]);
+            }
+        }
+    }
+    __syncthreads();                                             // (W is done with: its buffer takes the sums)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int s = 0; s < CH; ++s) {
+            double a = acc[q][s];
+            a += __shfl_xor(a, 1, 64);
+            a += __shfl_xor(a, 2, 64);
+            if (u == 0) wl[((4 * q + wave) * 16 + rl) * CH + s] = a;
+        }
+    }
+    __syncthreads();
+    const int64_t ip = rb * TILE + tid;
+    if (ip >= cm.n) return;
+    const int64_t i = cm.row_perm ? (int64_t)cm.row_perm[ip] : ip;
+    for (int s = 0; s < cw; ++s) out[i * S + s0c + s] = wl[tid * CH + s];
+}
+
+// The dense block: one work-group per (cell tile of 32 cells, chunk of CH sets), walking ALL gene tiles in order.  A thread holds
+// the four counts 4 tid .. 4 tid + 3 of a block as k_dn_cell_totals does -- one cell c = (tid / 2) % 32, the genes gbase + q of
+// k_dn_group_stats -- and keeps the chunk's accumulators in registers over the whole walk; the tile's 32 rows of W are staged in
+// LDS through col_perm, in two buffers (one barrier per tile).  At the end the 8 threads of a cell (k = tid % 2 + 2 (tid / 64))
+// meet in LDS and thread (c, s) adds their sums in the order k = 0 .. 7, then ADDS the result to out[i, s0 + s]: this kernel runs
+// second in stream order, after k_gene_scores has written every element, and is the only writer of the element in its launch.
+template <int CH>
+__global__ __launch_bounds__(256) void k_dn_gene_scores(const uint16_t *__restrict__ Xd, const int32_t *__restrict__ row_perm,
+                                                        const int32_t *__restrict__ col_perm, const double *__restrict__ scale,
+                                                        int lg, const double *__restrict__ W, int64_t S, int64_t n, int ngt,
+                                                        int nchunk, double *__restrict__ out) {
+    __shared__ __align__(16) double wl[2][32 * CH];
+    __shared__ double part[8 * 32 * CH];
+    const int tid = threadIdx.x;
+    const int chunk = (int)(blockIdx.x % (unsigned)nchunk);
+    const int64_t ct = blockIdx.x / (unsigned)nchunk;
+    const int64_t s0c = (int64_t)chunk * CH;
+    const int cw = (int)min((int64_t)CH, S - s0c);
+    const int c = (tid >> 1) & 31, h = (tid >> 6) & 1, k = (tid & 1) + 2 * (tid >> 6);
+    const int gbase = dn::acc_row(8 * (tid >> 7) + 4 * (tid & 1), h);      // gene of q = 0; q adds to it (acc_row: v % 4)
+    const int64_t ipc = ct * 32 + c;
+    double sv = 1.0;
+    if (scale && ipc < n) sv = scale[row_perm ? (int64_t)row_perm[ipc] : ipc];
+    double acc[CH];
+#pragma unroll
+    for (int s = 0; s < CH; ++s) acc[s] = 0.0;
+    for (int gt = 0; gt < ngt; ++gt) {
+        double *wb = wl[gt & 1];
+        for (int e = tid; e < 32 * CH; e += 256) {               // (the buffer was last read two tiles ago: a barrier lies between)
+            const int64_t jp = (int64_t)gt * 32 + e / CH;
+            const int s = e % CH;
+            const int64_t j = col_perm ? (int64_t)col_perm[jp] : jp;
+            wb[e] = s < cw ? W[j * S + s0c + s] : 0.0;
+        }
+        __syncthreads();
+        if (ipc >= n) continue;                                  // (a cell past the end; its thread still meets the barriers)
+        const uint2 w = *reinterpret_cast<const uint2 *>(Xd + (ct * ngt + gt) * 1024 + 4 * tid);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t xi = ((q & 2 ? w.y : w.x) >> (16 * (q & 1))) & 0xFFFFu;
+            if (xi == 0u) continue;
+            const double y = gs_value((double)xi, scale, sv, lg);
+            const double *wr = wb + (gbase + q) * CH;
+#pragma unroll
+            for (int s = 0; s < CH; ++s) acc[s] = fma(wr[s], y, acc[s]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < CH; ++s) part[(k * 32 + c) * CH + s] = acc[s];
+    __syncthreads();
+    for (int e = tid; e < 32 * CH; e += 256) {
+        const int64_t ip = ct * 32 + e / CH;
+        const int s = e % CH;
+        if (ip >= n || s >= cw) continue;
+        double a = part[e];
+#pragma unroll
+        for (int kk = 1; kk < 8; ++kk) a += part[kk * 32 * CH + e];
+        const int64_t i = row_perm ? (int64_t)row_perm[ip] : ip;
+        out[i * S + s0c + s] += a;
+    }
+}
+
+constexpr int GSC_CH = 8;              // oriana_gene_scores_set_chunk(): sets one work-group carries (4 x CH accumulators per lane: 182 VGPRs at 16)
+constexpr int GSC_MAX_SETS = 1024;     // oriana_gene_scores_max_sets()
+
 }  // namespace oriana
 
 using namespace oriana;
+
+extern "C" int64_t oriana_gene_scores_max_sets(void) { return GSC_MAX_SETS; }
+extern "C" int64_t oriana_gene_scores_set_chunk(void) { return GSC_CH; }
+
+extern "C" int oriana_gene_scores(const oriana_counts *cm, const oriana_dense *dn, const int32_t *row_perm,
+                                  const int32_t *col_perm, const double *scale, int log1p_flag, const double *W, int64_t S,
+                                  double *out, void *stream) {
+    if (!cm || !W || !out || S < 1) return ORIANA_EINVAL;
+    if (const int rc = gs_check_layouts(cm, dn)) return rc;
+    if (S > GSC_MAX_SETS) return ORIANA_EKRANGE;
+    const int64_t gd = dn ? dn->gd : 0, nchunk = (S + GSC_CH - 1) / GSC_CH;
+    const int64_t nrb = (cm->n + TILE - 1) / TILE;
+    const int64_t ngt = gd / 32, nct = dn && dn->n > 0 ? (dn->n + 31) / 32 : 0;
+    const int64_t nwg = nrb * nchunk, ndwg = ngt > 0 ? nct * nchunk : 0;
+    if (nwg > 0x7fffffffLL || ndwg > 0x7fffffffLL || ngt > 0x7fffffffLL) return ORIANA_EINVAL;
+    const int walk = cm->nrb == nrb && cm->ncb > 0 && cm->rslots > 0;
+    if (nwg > 0) {
+        hipLaunchKernelGGL(k_gene_scores<GSC_CH>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, *cm, scale,
+                           log1p_flag ? 1 : 0, W, S, gd, (int)nchunk, walk, out);
+        ORIANA_LAUNCH_CHECK();
+    }
+    if (ndwg > 0) {
+        hipLaunchKernelGGL(k_dn_gene_scores<GSC_CH>, dim3((unsigned)ndwg), dim3(256), 0, (hipStream_t)stream, dn->x, row_perm,
+                           col_perm, scale, log1p_flag ? 1 : 0, W, S, dn->n, (int)ngt, (int)nchunk, out);
+        ORIANA_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 extern "C" int64_t oriana_group_stats_max_groups(void) { return GS_MAX_GROUPS; }
 

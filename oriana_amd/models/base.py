@@ -1254,6 +1254,93 @@ class FactorModel:
         out['genes'] = markers.rank(w['scores'], n_top)
         return out
 
+    # ---- how strongly a cell expresses a gene set (scanpy's score_genes(), Seurat's AddModuleScore()) ------------------------------
+    # score_is = sum_j W_js y_ij over the stored counts of cell i: the product of the packed matrix of the log-normalised counts
+    # with an (m, S) weight matrix, one walk over both layouts with a fixed summation order (csrc/groupstats.hip);
+    # which genes carry which weight is decided on the host (signatures.py).
+    def gene_scores(self, weights, normalize=True, target_sum=1e4, log1p=True, as_tensor=False):
+        """Linear read-outs of the (log-normalised) counts of every local cell: ``Y @ weights`` without forming Y.
+
+        weights : (m,) or (m, S) array or tensor of finite values in the caller's gene order, taken as float64 (a column per
+        read-out: signatures.score_weights(), a signature with real weights, loadings from elsewhere).  normalize, target_sum,
+        log1p : as cluster_gene_stats(), with the same scale.  Returns the (n_local, S) float64 result in the caller's row order
+        ((n_local, 1) for 1-D weights): a NumPy array, or with as_tensor=True the device tensor.  A cell without a count scores
+        exactly 0.  Every sum is taken in an order fixed by the layouts and S: the same call returns the same bits.  A cell's
+        score is local, so under row sharding there is no collective.  ValueError before any launch for a wrong shape, entries
+        that are not finite, S outside 1..oriana_gene_scores_max_sets() or target_sum <= 0.  Nothing of the model's state is
+        written."""
+        from .. import _lib
+        n, m, dev, ct = self.n, self.m, self.device, self.counts
+        W = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+        if W.is_complex() or W.dtype == torch.bool:
+            raise ValueError('weights must be real numbers, got %s' % W.dtype)
+        if W.ndim == 1:
+            W = W.reshape(-1, 1)
+        if W.ndim != 2 or int(W.shape[0]) != m:
+            raise ValueError('weights must be (%d,) or (%d, S), got %s' % (m, m, tuple(weights.shape) if hasattr(weights, 'shape')
+                                                                            else tuple(W.shape)))
+        S, limit = int(W.shape[1]), int(_lib.load().oriana_gene_scores_max_sets())
+        if S < 1 or S > limit:
+            raise ValueError('the number of weight columns must lie within 1..%d, got %d' % (limit, S))
+        if not float(target_sum) > 0.0:
+            raise ValueError('target_sum must be positive')
+        W = W.to(device=dev, dtype=torch.float64).contiguous()
+        if not bool(torch.isfinite(W).all()):
+            raise ValueError('weights must be finite')
+        scale = None
+        if normalize:
+            tot = self._cell_totals_device()
+            scale = torch.where(tot > 0, float(target_sum) / tot, torch.zeros_like(tot)).contiguous()
+        out = torch.empty((n, S), dtype=torch.float64, device=dev)
+        if n > 0:
+            call('oriana_gene_scores', ct.sparse_struct, ct.dense.c_struct if ct.dense is not None else None, ptr(ct.row_perm),
+                 ptr(ct.col_perm), ptr(scale), 1 if log1p else 0, ptr(W), S, ptr(out), stream_ptr())
+        return out if as_tensor else out.cpu().numpy()
+
+    def score_genes(self, gene_sets, ctrl_size=50, n_bins=25, seed=0, gene_pool=None, control_genes=None, **kw):
+        """The score of every local cell for each of S gene sets: the mean log-normalised expression of the set minus the mean of
+        control genes drawn from the same expression bins (signatures.control_genes; scanpy's ``score_genes()``), on the device.
+
+        gene_sets : a sequence of integer index arrays, or a dict name -> array.  ctrl_size, n_bins, seed : the draw of the
+        controls (set s uses the generator of (seed, s)); gene_pool : the genes that define the bins and may be drawn (default:
+        all).  The gene means come from cluster_gene_stats() with a single cluster -- all-reduced under row sharding, so every
+        rank draws the same controls.  control_genes : the 'control_genes' of an earlier result instead of a draw (another
+        model, a shard or held-out cells scored against the same controls); no means are computed then and 'gene_means' is None.
+        Further keywords: normalize, target_sum, log1p, as_tensor of gene_scores().
+
+        Returns 'scores' (n_local, S) float64, 'control_genes' (a list of sorted int64 arrays), 'gene_means' (m,) float64,
+        'names' (the dict's keys, or 0 .. S - 1) and 'weights', the (m, S) matrix that was multiplied.  ValueError before any
+        launch for an empty set, indices outside [0, m) or repeated within a set, ctrl_size < 1, n_bins < 2, target_sum <= 0,
+        control_genes that do not match the sets or hold an empty list (TypeError for a keyword gene_scores() does not take);
+        after the means for a set whose bins hold no other gene.  Nothing of the model's state is written."""
+        from .. import signatures, _lib
+        unknown = sorted(set(kw) - {'normalize', 'target_sum', 'log1p', 'as_tensor'})
+        if unknown:
+            raise TypeError('score_genes() takes no keyword %s' % ', '.join(unknown))
+        m = self.m
+        names, sets = signatures.named_sets(m, gene_sets)
+        limit = int(_lib.load().oriana_gene_scores_max_sets())
+        if len(sets) > limit:
+            raise ValueError('at most %d gene sets per call, got %d' % (limit, len(sets)))
+        ctrl_size, n_bins = signatures.check_draw(ctrl_size, n_bins)
+        if not float(kw.get('target_sum', 1e4)) > 0.0:
+            raise ValueError('target_sum must be positive')
+        pool = None if gene_pool is None else signatures.check_set(m, gene_pool, 'gene_pool')
+        means = None
+        if control_genes is not None:
+            controls = list(control_genes)
+            if len(controls) != len(sets):
+                raise ValueError('%d gene sets but %d control sets' % (len(sets), len(controls)))
+            controls = [signatures.check_set(m, c, 'control set %r' % (nm,)) for nm, c in zip(names, controls)]
+        else:
+            stats_kw = {k: v for k, v in kw.items() if k != 'as_tensor'}
+            st = self.cluster_gene_stats(np.zeros(self.n, dtype=np.int64), n_clusters=1, **stats_kw)
+            means = st['sum'][0] / max(int(st['sizes'][0]), 1)
+            controls = [signatures.control_genes(means, g, ctrl_size=ctrl_size, n_bins=n_bins, seed=seed, set_index=s, pool=pool)
+                        for s, g in enumerate(sets)]
+        W = signatures.score_weights(m, sets, controls)
+        return {'scores': self.gene_scores(W, **kw), 'control_genes': controls, 'gene_means': means, 'names': names, 'weights': W}
+
     # ---- state I/O (tests, checkpoints) ---------------------------------------------------------------
     _PARAMS =('alpha1', 'alpha2', 'beta1', 'beta2', 'a1', 'a2', 'b1', 'b2', 'pi_d', 'p_d', 'pi_s', 'p_s')
 
