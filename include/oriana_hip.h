@@ -1237,6 +1237,47 @@ int oriana_basis_append_f64(int64_t n, double *Q, int64_t ldq, int64_t j, const 
 int oriana_basis_combine_f64(int64_t n, const double *Q, int64_t ldq, int64_t j, const double *S, int64_t m, double *out,
                              int64_t ldo, int64_t blocks, void *stream);
 
+/* ---- Harmony batch correction of the cell features (csrc/harmony.hip, oriana_amd/cluster.py: harmony; no counterpart
+ * in the reference) ----------------------------------------------------------------------------------------------------------------
+ * Rows are float32 with a row stride >= d and unit column stride; batch (n) int32 within [0, B) (a value outside addresses nothing:
+ * the row then belongs to no batch); R (n, K) float32 contiguous; K <= oriana_harmony_max_clusters(d), B <=
+ * oriana_harmony_max_batches(), d <= 256, else ORIANA_EKRANGE.  No float atomics: for a given `blocks` (0: sized from the device)
+ * every output is the same bits on repetition and for whatever the scratch held.  scratch: the entry's *_scratch_bytes(n, d, K, B,
+ * blocks) bytes, 16-byte aligned, contents undefined on entry and exit.  ORIANA_EINVAL before any HIP call for a negative size or
+ * `blocks`, d, K or B < 1, a row stride < d, n beyond 2^31 - 65, a NULL or misaligned scratch, a NULL required pointer.
+ * oriana_harmony_assign : for the n rows at Z (a row range of the caller's matrix; batch and R point at the same first row)
+ *   THE PAIR, all float32, one rounding per step, c = float32(-inv_sigma * log2(e)):
+ *     dot_k  = fl(acc + cmp) after a compensated chain over the features ascending from 0 (y: centers (K, d) float32): per
+ *              feature p = fl(z_f y_kf), ep = fmaf(z_f, y_kf, -p), s = fl(acc + p), bb = fl(s - acc),
+ *              es = fl(fl(acc - fl(s - bb)) + fl(p - bb)), acc = s, cmp = fl(cmp + fl(ep + es))
+ *     dist_k = fmaf(-2, dot_k, 2);  m = min_k dist_k
+ *     e_k    = exp2(fl(fl(dist_k - m) * c)) * P[k, batch]     (exp2: v_exp_f32, 1 ulp; P (K, B) float32, positive)
+ *     s      = e_0 + e_1 + ... ascending;  R_k = e_k * fl(1 / s)                  (1 / s correctly rounded)
+ *   A row's R depends on nothing but the row, the centres, P and c.  Also, in float64 and in a fixed order given `blocks`:
+ *   O_blk[k, b] = sum over the range's rows of batch b of R_k; sums[0] = sum R_k dist_k; sums[1] = sum R_k logf(R_k) over
+ *   R_k > 0 (each product exact in float64).  inv_sigma must be finite and positive.  n = 0: O_blk and sums are zeroed.
+ * oriana_harmony_moments : S[k, b, :] = sum_{batch_i = b} R_ik x_i (K, B, d) and O[k, b] = sum_{batch_i = b} R_ik, float64.  The rows
+ *   of one batch inside a tile of 64 rows are taken in ascending order, oriana_harmony_partial_rows() at a time: those as one float32
+ *   fmaf chain from 0, the chains' values then in float64, groups ascending, tiles ascending inside a range, ranges ascending.  One
+ *   writer per partial sum.  n = 0: zeroed.
+ * oriana_harmony_correct : Zcorr[i, f] = z_if - s, s = the fmaf chain over k ascending from 0 of R_ik * W[k, batch_i, f] (W (K, B, d)
+ *   float32); Zcos[i, :] = Zcorr[i, :] / sqrt(a), a = the fmaf chain over f ascending of Zcorr_if^2 (root and quotient correctly
+ *   rounded); a = 0 writes a zero row.  Zcorr and Zcos are (n, d) contiguous.  n = 0 is a no-op. */
+int64_t oriana_harmony_max_clusters(int64_t d);      /* 0: d is not served */
+int64_t oriana_harmony_max_batches(void);
+int64_t oriana_harmony_partial_rows(void);
+/* (negative: the argument error the call would return) */
+int64_t oriana_harmony_assign_scratch_bytes(int64_t n, int64_t d, int64_t K, int64_t B, int64_t blocks);
+int64_t oriana_harmony_moments_scratch_bytes(int64_t n, int64_t d, int64_t K, int64_t B, int64_t blocks);
+int64_t oriana_harmony_correct_scratch_bytes(int64_t n, int64_t d, int64_t K, int64_t B, int64_t blocks);
+int oriana_harmony_assign(const float *Z, int64_t n, int64_t d, int64_t ldz, const int32_t *batch, const float *centers, int64_t K,
+                          const float *P, int64_t B, double inv_sigma, float *R, double *O_blk, double *sums, void *scratch,
+                          int64_t blocks, void *stream);
+int oriana_harmony_moments(const float *X, int64_t n, int64_t d, int64_t ldx, const float *R, int64_t K, const int32_t *batch,
+                           int64_t B, double *S, double *O, void *scratch, int64_t blocks, void *stream);
+int oriana_harmony_correct(const float *Z, int64_t n, int64_t d, int64_t ldz, const float *R, int64_t K, const int32_t *batch,
+                           const float *W, int64_t B, float *Zcorr, float *Zcos, void *scratch, int64_t blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

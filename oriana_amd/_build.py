@@ -10,11 +10,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-SOURCES = ['pack.hip', 'passes.hip', 'updates.hip', 'dense.hip', 'dense_mfma.hip', 'dense_f32.hip', 'dense_pass.hip', 'dense_zi.hip', 'metrics.hip', 'stateless.hip', 'resident.hip', 'kmeans.hip', 'knn.hip', 'silhouette.hip', 'groupstats.hip', 'ranksum.hip', 'tsne.hip', 'community.hip', 'diffusion.hip']
+SOURCES = ['pack.hip', 'passes.hip', 'updates.hip', 'dense.hip', 'dense_mfma.hip', 'dense_f32.hip', 'dense_pass.hip', 'dense_zi.hip', 'metrics.hip', 'stateless.hip', 'resident.hip', 'kmeans.hip', 'knn.hip', 'silhouette.hip', 'groupstats.hip', 'ranksum.hip', 'tsne.hip', 'community.hip', 'diffusion.hip', 'harmony.hip']
 LIB = os.path.join(CSRC, 'liboriana_hip.so')
 # dense_zi.hip: the loop body of k_zi_row<6, 1> is ONE fully unrolled basic block of ~2700 instructions (a hand-placed
 # slot plan of matrix and vector instructions); it exceeds the default size limit of `#pragma unroll`
-EXTRA_FLAGS = {'dense_zi.hip': ['-mllvm', '-pragma-unroll-threshold=65536']}
+# harmony.hip: its float32 sequences are stated operation by operation (include/oriana_hip.h): only what is written as fmaf may
+# fuse.  hipcc's default is -ffp-contract=fast, and a file-scope pragma did not reach the device code.
+EXTRA_FLAGS = {'dense_zi.hip': ['-mllvm', '-pragma-unroll-threshold=65536'], 'harmony.hip': ['-ffp-contract=off']}
 ARCH = 'gfx950'
 
 

@@ -207,6 +207,15 @@ _SIGS = {
     'oriana_basis_orthogonalize_f64': (c_int, [_I, _P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P]),
     'oriana_basis_append_f64': (c_int, [_I, _P, _I, _I, _P, _P, _P]),
     'oriana_basis_combine_f64': (c_int, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    'oriana_harmony_max_clusters': (_I, [_I]),
+    'oriana_harmony_max_batches': (_I, []),
+    'oriana_harmony_partial_rows': (_I, []),
+    'oriana_harmony_assign_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_harmony_moments_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_harmony_correct_scratch_bytes': (_I, [_I, _I, _I, _I, _I]),
+    'oriana_harmony_assign': (c_int, [_P, _I, _I, _I, _P, _P, _I, _P, _I, c_double, _P, _P, _P, _P, _I, _P]),
+    'oriana_harmony_moments': (c_int, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P]),
+    'oriana_harmony_correct': (c_int, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

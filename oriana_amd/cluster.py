@@ -20,7 +20,11 @@ graph alone and a NumPy restatement matches it label for label.  DESIGN.md secti
 
 diffusion_map() is the diffusion map of the same neighbour graph (csrc/diffusion.hip): the Gaussian affinities of
 diffusion_graph(), and Lanczos with full reorthogonalisation whose sums over rows run in a fixed order, so the eigenpairs are a
-function of the graph and the start vector alone; diffusion_pseudotime() orders the cells from a root.  DESIGN.md section 5p."""
+function of the graph and the start vector alone; diffusion_pseudotime() orders the cells from a root.  DESIGN.md section 5p.
+
+harmony() is Harmony batch correction of the same rows (csrc/harmony.hip): soft k-means under a batch-diversity penalty, then a
+per-cluster ridge correction in closed form; one permutation per run and a fixed block order make a run a function of its
+arguments, and a NumPy restatement follows it step for step.  DESIGN.md section 5r."""
 import math
 
 import numpy as np
@@ -37,7 +41,9 @@ __all__ = ['kmeans', 'lloyd_step', 'max_centers', 'restart_group', 'partial_rows
            'tsne_gradient', 'tsne_pca_init',
            'snn_graph', 'louvain', 'louvain_sweep', 'louvain_plan', 'louvain_row_cap', 'modularity',
            'diffusion_graph', 'diffusion_map', 'diffusion_pseudotime', 'graph_components', 'csr_spmv', 'basis_tile_rows',
-           'basis_orthogonalize', 'basis_append', 'basis_combine']
+           'basis_orthogonalize', 'basis_append', 'basis_combine',
+           'harmony', 'harmony_assign', 'harmony_moments', 'harmony_correct', 'harmony_max_clusters', 'harmony_max_batches',
+           'harmony_partial_rows', 'harmony_default_clusters', 'harmony_block_cuts', 'harmony_ridge_weights']
 
 SCRATCH_BUDGET = 1 << 30          # bytes a launch may take for scratch, minimum distances and their cumulative sums
 
@@ -1288,7 +1294,9 @@ def louvain_sweep(graph, deg, two_m, comm, tot, size, resolution=1.0, plan=None,
     dev = crow.device
     if scratch is None:
         scratch = torch.empty(plan['scratch_bytes'], dtype=torch.uint8, device=dev)
-    out = {'comm': torch.empty(n, dtype=torch.int32, device=dev), 'moved': torch.zeros(1, dtype=torch.int64, device=dev),
+    # ('comm' starts as the labelling it was given: a sweep that overflows writes nothing, and louvain() sums over the proposed
+    #  labelling before the host reads the flag -- with undefined entries those sums indexed out of bounds)
+    out = {'comm': comm.clone(), 'moved': torch.zeros(1, dtype=torch.int64, device=dev),
            'overflow': torch.zeros(1, dtype=torch.int32, device=dev)}
     nnz, nlong = int(col.numel()), int(plan['long_rows'].numel())
     call('oriana_louvain_sweep', n, ptr(crow), ptr(col) if nnz else None, ptr(w) if nnz else None, ptr(deg) if n else None,
@@ -1684,3 +1692,300 @@ def diffusion_pseudotime(eigenvalues, components, root):
     dpt = torch.sqrt(acc)
     top = dpt.max() if n else None
     return {'dpt': dpt, 'pseudotime': dpt / top if n and float(top) > 0 else dpt.clone()}
+
+
+# ---- Harmony batch correction (csrc/harmony.hip) --------------------------------------------------------------
+def harmony_max_clusters(d):
+    """The largest number of clusters harmony() serves at feature width d (0: d is not served)."""
+    return int(_lib.load().oriana_harmony_max_clusters(int(d)))
+
+
+def harmony_max_batches():
+    return int(_lib.load().oriana_harmony_max_batches())
+
+
+def harmony_partial_rows():
+    """Rows of one batch that harmony_moments() adds in float32 before the sum is promoted to float64."""
+    return int(_lib.load().oriana_harmony_partial_rows())
+
+
+def harmony_default_clusters(n):
+    """harmonypy's default: min(round(n / 30), 100), at least 1 (halves round up)."""
+    return max(1, min(int(math.floor(n / 30.0 + 0.5)), 100))
+
+
+def harmony_block_cuts(n, n_blocks=20):
+    """The row cuts of the blocks of a round: block j is the permuted rows [cuts[j], cuts[j + 1]), min(n_blocks, n) blocks."""
+    nb = min(int(n_blocks), int(n))
+    return [(j * int(n)) // nb for j in range(nb + 1)]
+
+
+def _harmony_rows(X, R, batch, what):
+    """(n, d, K, row stride) of float32 rows X, their responsibilities R (n, K) and batches (n,) int32, checked."""
+    _check_rows(X, what)
+    n, ld = _rows_ld(X)
+    d = int(X.shape[1])
+    if not isinstance(R, torch.Tensor) or R.dim() != 2 or R.dtype != torch.float32 or not R.is_contiguous() or int(R.shape[0]) != n:
+        raise ValueError('R must be a contiguous float32 (n, K) tensor with the rows of %s' % what)
+    if not isinstance(batch, torch.Tensor) or batch.dtype != torch.int32 or tuple(batch.shape) != (n,) or not batch.is_contiguous():
+        raise ValueError('batch must be a contiguous int32 (n,) tensor')
+    if d < 1 or int(R.shape[1]) < 1:
+        raise ValueError('%s and R need at least one column' % what)
+    return n, d, int(R.shape[1]), ld
+
+
+def _harmony_out(t, shape, dtype, device, what):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous %s tensor of shape %s' % (what, dtype, tuple(shape)))
+    return t
+
+
+def harmony_assign(Zcos, batch, centers, P, inv_sigma, R, rows=None, blocks=0, scratch=None, O_blk=None, sums=None):
+    """One oriana_harmony_assign: the responsibilities of the rows [rows[0], rows[1]) of Zcos (n, d) float32 (default: all) under
+    centers (K, d) float32 and the penalty table P (K, B) float32, written into those rows of R (n, K) float32; batch (n,) int32.
+    Returns (O_blk (K, B), sums (2,)) float64 device tensors of the range: the responsibilities per cluster and batch, and
+    sum R dist, sum R log R."""
+    n, d, K, ld = _harmony_rows(Zcos, R, batch, 'Zcos')
+    if (centers.dtype != torch.float32 or P.dtype != torch.float32 or not centers.is_contiguous() or not P.is_contiguous()
+            or tuple(centers.shape) != (K, d) or P.dim() != 2 or int(P.shape[0]) != K or int(P.shape[1]) < 1):
+        raise ValueError('harmony_assign needs contiguous float32 centers (K, d) and P (K, B)')
+    B = int(P.shape[1])
+    a, b = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= a <= b <= n:
+        raise ValueError('rows must be a range within [0, %d]' % n)
+    if not (float(inv_sigma) > 0 and math.isfinite(float(inv_sigma))):
+        raise ValueError('inv_sigma must be finite and positive')
+    dev = R.device
+    m = b - a
+    nbytes = _scratch_bytes('oriana_harmony_assign_scratch_bytes', m, d, K, B, int(blocks))
+    scratch = _scratch_for(scratch, nbytes, dev)
+    O_blk = _harmony_out(O_blk, (K, B), torch.float64, dev, 'O_blk')
+    sums = _harmony_out(sums, (2,), torch.float64, dev, 'sums')
+    call('oriana_harmony_assign', ptr(Zcos) + 4 * a * ld if m else None, m, d, ld, ptr(batch) + 4 * a if m else None, ptr(centers), K,
+         ptr(P), B, float(inv_sigma), ptr(R) + 4 * a * K if m else None, ptr(O_blk), ptr(sums), ptr(scratch), int(blocks), stream_ptr())
+    return O_blk, sums
+
+
+def harmony_moments(X, R, batch, n_batches, blocks=0, scratch=None, S=None, O=None):
+    """One oriana_harmony_moments: S[k, b, :] = sum_{batch_i = b} R_ik x_i (K, B, d) and O[k, b] = sum_{batch_i = b} R_ik (K, B),
+    float64 device tensors, from X (n, d) float32, R (n, K) float32 and batch (n,) int32."""
+    n, d, K, ld = _harmony_rows(X, R, batch, 'X')
+    B = int(n_batches)
+    if B < 1:
+        raise ValueError('n_batches must be at least 1')
+    dev = R.device
+    nbytes = _scratch_bytes('oriana_harmony_moments_scratch_bytes', n, d, K, B, int(blocks))
+    scratch = _scratch_for(scratch, nbytes, dev)
+    S = _harmony_out(S, (K, B, d), torch.float64, dev, 'S')
+    O = _harmony_out(O, (K, B), torch.float64, dev, 'O')
+    call('oriana_harmony_moments', ptr(X) if n else None, n, d, ld, ptr(R) if n else None, K, ptr(batch) if n else None, B, ptr(S),
+         ptr(O), ptr(scratch), int(blocks), stream_ptr())
+    return S, O
+
+
+def harmony_correct(Z, R, batch, W, blocks=0, scratch=None, Zcorr=None, Zcos=None):
+    """One oriana_harmony_correct: Zcorr = Z - sum_k R_ik W[k, batch_i, :] and its cosine-normalised rows Zcos, (n, d) float32
+    device tensors, from Z (n, d) float32, R (n, K) float32, batch (n,) int32 and W (K, B, d) float32."""
+    n, d, K, ld = _harmony_rows(Z, R, batch, 'Z')
+    if W.dtype != torch.float32 or not W.is_contiguous() or W.dim() != 3 or int(W.shape[0]) != K or int(W.shape[2]) != d or int(W.shape[1]) < 1:
+        raise ValueError('harmony_correct needs a contiguous float32 W (K, B, d)')
+    B = int(W.shape[1])
+    dev = R.device
+    nbytes = _scratch_bytes('oriana_harmony_correct_scratch_bytes', n, d, K, B, int(blocks))
+    scratch = _scratch_for(scratch, nbytes, dev)
+    Zcorr = _harmony_out(Zcorr, (n, d), torch.float32, dev, 'Zcorr')
+    Zcos = _harmony_out(Zcos, (n, d), torch.float32, dev, 'Zcos')
+    call('oriana_harmony_correct', ptr(Z) if n else None, n, d, ld, ptr(R) if n else None, K, ptr(batch) if n else None, ptr(W), B,
+         ptr(Zcorr) if n else None, ptr(Zcos) if n else None, ptr(scratch), int(blocks), stream_ptr())
+    return Zcorr, Zcos
+
+
+def harmony_ridge_weights(S, O, ridge):
+    """The closed form of harmonypy's per-cluster ridge system with an unpenalised intercept, elementwise in float64: from
+    S (K, B, d), O (K, B) and ridge (B,) > 0 (torch tensors on one device), W (K, B, d) with
+    w0 = sum_b l_b S_b / (O_b + l_b) / sum_b l_b O_b / (O_b + l_b) and W_kb = (S_b - O_b w0) / (O_b + l_b); 0 where the
+    denominator of w0 is 0.  The intercept w0 is not returned."""
+    den = O + ridge[None, :]
+    g = ridge[None, :] / den                                        # (K, B)
+    num = (g[:, :, None] * S).sum(1)                                # (K, d)
+    c = (g * O).sum(1)                                              # (K,)
+    ok = c > 0
+    w0 = num / torch.where(ok, c, torch.ones_like(c))[:, None]
+    W = (S - O[:, :, None] * w0[:, None, :]) / den[:, :, None]
+    return torch.where(ok[:, None, None], W, torch.zeros_like(W))
+
+
+def _harmony_vector(v, B, what, positive):
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(B, float(a))
+    if a.shape != (B,) or not np.isfinite(a).all() or (positive and not (a > 0).all()) or (not positive and (a < 0).any()):
+        raise ValueError('%s must be a %s scalar or (%d,) vector' % (what, 'positive' if positive else 'non-negative', B))
+    return a
+
+
+def harmony(Y, batch, n_clusters=None, theta=2.0, sigma=0.1, ridge=1.0, n_blocks=20, max_iter=10, max_rounds=20, eps_cluster=1e-5,
+            eps_harmony=1e-4, centers=None, seed=0, blocks=0, pg=None):
+    """Harmony batch correction (Korsunsky et al. 2019; harmonypy's algorithm) of the rows of Y, an (n, d) float32 C-contiguous
+    device tensor, given batch (n,) integers within [0, B) with every batch present.  DESIGN.md section 5r defines every step.
+
+    The two deliberate differences from harmonypy, both for determinism: ONE permutation ``torch.randperm(n, generator=
+    manual_seed(seed))`` per run, whose min(n_blocks, n) blocks every round visits in ascending order (harmonypy reshuffles every
+    round); and the ridge correction in closed form (harmony_ridge_weights) instead of a matrix inverse per cluster.
+
+    theta, ridge : scalars or (B,) vectors (theta >= 0, ridge > 0); sigma > 0.  n_clusters : default harmony_default_clusters(n).
+    centers : optional (K, d) start centres (their rows are normalised), else kmeans(Zcos, K, n_init=10, max_iter=25, seed=seed).
+    eps_cluster : a round's stopping rule, from the fifth round of an iteration on: (old - new) / |old| < eps_cluster with old /
+    new the sums of the three objectives before the last one / the last three; None: exactly max_rounds rounds.  eps_harmony :
+    iterations stop when the last objectives of two successive iterations differ by less than eps_harmony relatively; None: all
+    max_iter iterations.  Between the block launches only small float64 device operations on (K, B) run; the host reads the
+    round objectives once per round from the fifth round on and once per iteration.
+
+    Returns a dict: 'corrected' (n, d) float32, 'responsibilities' (n, K) float32 and 'centers' (K, d) float32 device tensors in
+    the caller's row order; 'objective' (the start first, then one per iteration), 'objective_rounds' (every round of every
+    iteration), 'rounds' (per iteration), 'n_iter', 'converged', 'batch_sizes' (B,) int64 NumPy.
+    ValueError before any launch for arguments out of range, a batch that occurs nowhere, a non-finite entry or a zero row;
+    NotImplementedError for a process group of more than one rank."""
+    if odist.world_size(pg) > 1:
+        raise NotImplementedError('harmony() does not shard its rows: gather the features on one rank')
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2:
+        raise ValueError('Y must be a 2-D torch tensor')
+    if Y.dtype != torch.float32:
+        raise ValueError('Y must be float32, got %s' % Y.dtype)
+    if not Y.is_contiguous():
+        raise ValueError('Y must be C-contiguous')
+    n, d = int(Y.shape[0]), int(Y.shape[1])
+    if n < 1 or d < 1:
+        raise ValueError('Y needs at least one row and one column')
+    bh = batch.detach().cpu().numpy() if isinstance(batch, torch.Tensor) else np.asarray(batch)
+    if bh.ndim != 1 or bh.shape[0] != n or bh.dtype.kind not in 'iu':
+        raise ValueError('batch must be (n,) integers')
+    bh = bh.astype(np.int64)
+    if bh.min() < 0:
+        raise ValueError('batch must be non-negative')
+    B = int(bh.max()) + 1
+    if B > harmony_max_batches():
+        raise ValueError('%d batches are beyond the %d served' % (B, harmony_max_batches()))
+    sizes = np.bincount(bh, minlength=B).astype(np.int64)
+    if (sizes == 0).any():
+        raise ValueError('batch %d occurs nowhere: number the batches 0 .. B - 1' % int(np.nonzero(sizes == 0)[0][0]))
+    K = harmony_default_clusters(n) if n_clusters is None else int(n_clusters)
+    if K < 1 or K > n:
+        raise ValueError('n_clusters must lie within [1, n]')
+    if d > 256 or K > harmony_max_clusters(d):
+        raise ValueError('n_clusters = %d is beyond the %d served at %d features' % (K, harmony_max_clusters(d) if d <= 256 else 0, d))
+    th = _harmony_vector(theta, B, 'theta', False)
+    lam = _harmony_vector(ridge, B, 'ridge', True)
+    sigma = float(sigma)
+    if not (sigma > 0 and math.isfinite(sigma)):
+        raise ValueError('sigma must be finite and positive')
+    n_blocks, max_iter, max_rounds, blocks = int(n_blocks), int(max_iter), int(max_rounds), int(blocks)
+    if n_blocks < 1 or max_iter < 1 or max_rounds < 1 or blocks < 0:
+        raise ValueError('n_blocks >= 1, max_iter >= 1, max_rounds >= 1 and blocks >= 0 are required')
+    for e, what in ((eps_cluster, 'eps_cluster'), (eps_harmony, 'eps_harmony')):
+        if e is not None and not float(e) >= 0:
+            raise ValueError('%s must be None or non-negative' % what)
+    c0 = None
+    if centers is not None:
+        c0 = np.asarray(centers.detach().cpu() if isinstance(centers, torch.Tensor) else centers, dtype=np.float64)
+        if c0.shape != (K, d) or not np.isfinite(c0).all() or not (np.abs(c0).sum(1) > 0).all():
+            raise ValueError('centers must be finite non-zero rows of shape (n_clusters, d) = %s' % ((K, d),))
+    if c0 is None and K > max_centers(d):
+        raise ValueError('the k-means start serves %d clusters at %d features: pass centers= for n_clusters = %d' % (max_centers(d), d, K))
+    ok = torch.isfinite(Y).all() & (Y != 0).any(dim=1).all()
+    if not bool(ok.item()):
+        raise ValueError('Y has non-finite entries or a zero row (cosine normalisation of a zero row is undefined)')
+    if not Y.is_cuda:
+        raise ValueError('Y must be a device tensor')
+
+    dev = Y.device
+    f64 = torch.float64
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=g).to(dev)
+    Z = Y.index_select(0, perm).contiguous()
+    bt = torch.as_tensor(bh[perm.cpu().numpy()].astype(np.int32), device=dev)
+    cuts = harmony_block_cuts(n, n_blocks)
+    nb = len(cuts) - 1
+    Pr = torch.as_tensor(sizes / float(n), dtype=f64, device=dev)
+    th_d, lam_d = torch.as_tensor(th, dtype=f64, device=dev), torch.as_tensor(lam, dtype=f64, device=dev)
+    inv_sigma = 1.0 / sigma
+    lib = _lib.load()
+    sc_assign = _scratch_for(None, max(int(lib.oriana_harmony_assign_scratch_bytes(m, d, K, B, blocks))
+                                       for m in {cuts[j + 1] - cuts[j] for j in range(nb)}), dev)
+    sc_moments = _scratch_for(None, _scratch_bytes('oriana_harmony_moments_scratch_bytes', n, d, K, B, blocks), dev)
+    sc_correct = _scratch_for(None, _scratch_bytes('oriana_harmony_correct_scratch_bytes', n, d, K, B, blocks), dev)
+
+    R = torch.zeros(n, K, dtype=torch.float32, device=dev)
+    # the cosine-normalised rows: the correction with W = 0
+    _, Zcos = harmony_correct(Z, R, bt, torch.zeros(K, B, d, dtype=torch.float32, device=dev), blocks=blocks, scratch=sc_correct)
+    Zcorr = Z
+    if c0 is None:
+        c0 = np.asarray(kmeans(Zcos, K, n_init=10, max_iter=25, seed=seed)['centers'], dtype=np.float64)
+        if not (np.abs(c0).sum(1) > 0).all():
+            raise ValueError('k-means returned a zero centre')
+    c0 = c0 / np.sqrt((c0 * c0).sum(1, keepdims=True))
+    cen64 = torch.as_tensor(c0, dtype=f64, device=dev)
+    cen = cen64.to(torch.float32)
+
+    O_blk = torch.zeros(nb, K, B, dtype=f64, device=dev)
+    sums = torch.zeros(nb, 2, dtype=f64, device=dev)
+    ones = torch.ones(K, B, dtype=torch.float32, device=dev)
+
+    def assign(j, P):
+        harmony_assign(Zcos, bt, cen, P, inv_sigma, R, rows=(cuts[j], cuts[j + 1]), blocks=blocks, scratch=sc_assign,
+                       O_blk=O_blk[j], sums=sums[j])
+
+    def objective(O, E):
+        return sums[:, 0].sum() + sigma * sums[:, 1].sum() + sigma * (th_d[None, :] * O * torch.log((O + 1.0) / (E + 1.0))).sum()
+
+    for j in range(nb):
+        assign(j, ones)
+    O = O_blk.sum(0)
+    E = O.sum(1)[:, None] * Pr[None, :]
+    obj_iter = [float(objective(O, E).item())]
+    obj_rounds, rounds = [], []
+    converged = False
+    n_iter = 0
+    for it in range(max_iter):
+        robj = []
+        nr = 0
+        while nr < max_rounds:
+            S, _ = harmony_moments(Zcos, R, bt, B, blocks=blocks, scratch=sc_moments)
+            C = S.sum(1)
+            cn = torch.sqrt((C * C).sum(1, keepdim=True))
+            cen64 = torch.where(cn > 0, C / torch.where(cn > 0, cn, torch.ones_like(cn)), cen64)
+            cen = cen64.to(torch.float32)
+            for j in range(nb):
+                O = O - O_blk[j]
+                E = E - O_blk[j].sum(1)[:, None] * Pr[None, :]
+                P = torch.pow((E + 1.0) / (O + 1.0), th_d[None, :]).to(torch.float32)
+                assign(j, P)
+                O = O + O_blk[j]
+                E = E + O_blk[j].sum(1)[:, None] * Pr[None, :]
+            robj.append(objective(O, E))
+            nr += 1
+            if eps_cluster is not None and nr >= 5:
+                h = torch.stack(robj[-4:]).cpu().numpy()              # (the one host read of the round)
+                old, new = float(h[0] + h[1] + h[2]), float(h[1] + h[2] + h[3])
+                if (old - new) / abs(old) < float(eps_cluster):
+                    break
+        h = [float(v) for v in torch.stack(robj).cpu().numpy()]
+        obj_rounds.extend(h)
+        rounds.append(nr)
+        obj_iter.append(h[-1])
+        S, Om = harmony_moments(Z, R, bt, B, blocks=blocks, scratch=sc_moments)
+        W = harmony_ridge_weights(S, Om, lam_d).to(torch.float32)
+        Zcorr, Zcos = harmony_correct(Z, R, bt, W, blocks=blocks, scratch=sc_correct)
+        n_iter = it + 1
+        if eps_harmony is not None and abs(obj_iter[-2] - obj_iter[-1]) / abs(obj_iter[-2]) < float(eps_harmony):
+            converged = True
+            break
+    corrected = torch.empty_like(Zcorr)
+    corrected[perm] = Zcorr
+    resp = torch.empty_like(R)
+    resp[perm] = R
+    return {'corrected': corrected, 'responsibilities': resp, 'centers': cen, 'objective': obj_iter, 'objective_rounds': obj_rounds,
+            'rounds': rounds, 'n_iter': n_iter, 'converged': converged, 'batch_sizes': sizes}

@@ -888,6 +888,30 @@ class FactorModel:
         out['factors'] = cols
         return out
 
+    def integrate_cells(self, batch, features='log_mean', factors=None, as_tensor=False, **harmony_kw):
+        """Harmony batch correction of the feature matrix cluster_cells() uses, on the device (cluster.harmony; its keywords pass
+        through).  batch : (n,) integers within [0, B), the sample of origin of every cell, every batch present.
+
+        Returns the dict of cluster.harmony plus 'features' (the (n, d) float32 matrix that was corrected) and 'factors' (the
+        column indices, int64); 'corrected', 'responsibilities', 'centers' and 'features' are NumPy arrays, or with
+        ``as_tensor=True`` device tensors, so that ``out['corrected']`` feeds cluster.knn, cluster.kmeans, cluster.tsne,
+        cluster.snn_graph + cluster.louvain and cluster.diffusion_* without a host copy.  A model sharded over more than one rank
+        raises NotImplementedError.  Nothing of the model's state is written."""
+        from .. import cluster
+        if odist.world_size(self.pg) > 1:
+            raise NotImplementedError('integrate_cells() does not shard the cells: fit on one rank, or gather the features')
+        cols = self._cell_feature_columns(features, factors)
+        if 'pg' in harmony_kw:
+            raise ValueError('integrate_cells() uses the process group of the model')
+        F = self._cell_features(features, cols)
+        out = cluster.harmony(F, batch, pg=self.pg, **harmony_kw)
+        out['features'] = F
+        out['factors'] = cols
+        if not as_tensor:
+            for key in ('corrected', 'responsibilities', 'centers', 'features'):
+                out[key] = out[key].cpu().numpy()
+        return out
+
     def _cell_feature_columns(self, features, factors):
         """The validated `features` / `factors` arguments of cluster_cells() and cell_neighbors(): the column indices, int64."""
         if features not in ('log_mean', 'mean_log'):
