@@ -741,6 +741,16 @@ int oriana_nzmask_counts(uint32_t *mask, const oriana_counts *cm, int64_t ld, vo
 int oriana_zi_foldin_rate(double *DV, const double *U, const double *V, const double *pi_d, const uint32_t *nzmask,
                           const uint32_t *nztiles, const uint8_t *active, float *scratch, int arithmetic, int64_t n, int64_t m,
                           int64_t K, void *stream);
+/* Which kernel serves a dense ZI product of width K: the answer of the dispatch chain the entries themselves run (csrc/
+ * dense_tiles.h, zi_candidate), without a launch -- no device is needed.  op 0: the D update (oriana_dropout_sweep_fused_tiles)
+ * and its rate-only twin (oriana_zi_foldin_rate); op 1: D_hat^T W (oriana_dense_t_times_factor_f32).  tiles_ok: the run-time
+ * preconditions of the csrc/dense_zi.hip family hold (a gene count that is a multiple of 4, 16-byte aligned pointers, and for
+ * op 0 the per-lane flags of oriana_nzmask_tiles; for op 1 a scratch).  Returns (family << 16) | (a << 8) | b >= 0 with
+ *   family 1  csrc/dense_zi.hip, k_zi_row / k_zi_col<KC = a, TAIL = b>;
+ *   family 2  the bf16 x 3 kernels of csrc/dense_f32.hip, k_dropout_sweep_b16<NT = a, KC = b> / k_dt_times_factor_b16<NT = a>;
+ *   family 3  the float32 matrix instruction, k_dropout_sweep<NT = a> / k_dt_times_factor_f32<NT = a, GQ = b>;
+ * ORIANA_EKRANGE for K > 128, ORIANA_EINVAL for K <= 0, another op or another arithmetic, as the entries. */
+int oriana_zi_dispatch(int op, int64_t K, int arithmetic, int tiles_ok);
 /* The dropout term of a held-out cell's bound under a ZI model with the gene side frozen (ZIGaP.fold_in_score_samples,
  * engine.zi_cell_bounds), the dropout posterior collapsed at its optimum and never stored:
  *   out[i] = sum_{j < m_real, x_ij != 0} z_ij + sum_{j < m_real, x_ij == 0} softplus(z_ij),   z_ij = logit(pi~_j) - U_i . V_j,

@@ -125,6 +125,7 @@ _SIGS = {
     'oriana_nzmask_tiles': (c_int, [_P, _P, _I, _I, _P]),
     'oriana_nzmask_counts': (c_int, [_P, ctypes.POINTER(OrianaCounts), _I, _P]),
     'oriana_zi_foldin_rate': (c_int, [_P] * 8 + [c_int, _I, _I, _I, _P]),
+    'oriana_zi_dispatch': (c_int, [c_int, _I, c_int, c_int]),
     'oriana_zi_cell_bound_scratch_doubles': (_I, [_I, _I, _I]),
     'oriana_zi_cell_bound': (c_int, [_P] * 6 + [_I, _I, _I, _I, _P]),
     'oriana_zi_gene_rate_ranges': (_I, [_I, _I, _I]),

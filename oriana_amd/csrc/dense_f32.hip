@@ -1504,6 +1504,32 @@ extern "C" int oriana_zi_foldin_rate(double *DV, const double *U, const double *
     });
 }
 
+// Which kernel the entries above (op 0: the D update and its rate-only twin) and oriana_dense_t_times_factor_f32 (op 1) launch
+// for K under `arithmetic`, asked through the chain they dispatch with -- with_variant, with_cfg, zi_first over zi_candidate --
+// so the answer cannot drift from the launch: (family << 16) | (a << 8) | b of the ZiPick that would run.  tiles_ok stands for
+// the run-time preconditions of the tiles family (zi_update_ok / zi_dt_ok); the other families have none.  Host only: nothing
+// is launched, no device is touched.
+template <dn::ZiOp OP>
+static int zi_dispatch(int64_t K, int arithmetic, int tiles_ok) {
+    return with_variant<ORIANA_MATRIX_F32, ORIANA_MATRIX_BF16X3>(arithmetic, [&](auto A) {
+        return dn::with_cfg<1, dn::ZI_KP_MAX / 16>(dn::kc_tail(oriana_kpad(K)), [&](auto c) {
+            return dn::zi_first<OP, decltype(c)::KP, decltype(A)::value>(
+                [&](dn::ZiFam f) { return f != dn::ZiFam::tiles || tiles_ok != 0; },
+                [&](auto p) {
+                    using P = decltype(p);
+                    return ((int)P::fam << 16) | (P::a << 8) | P::b;
+                });
+        });
+    });
+}
+
+extern "C" int oriana_zi_dispatch(int op, int64_t K, int arithmetic, int tiles_ok) {
+    if (K <= 0 || (op != 0 && op != 1)) return ORIANA_EINVAL;
+    if (K > 128) return ORIANA_EKRANGE;
+    if (arithmetic != ORIANA_MATRIX_F32 && arithmetic != ORIANA_MATRIX_BF16X3) return ORIANA_EINVAL;
+    return op == 0 ? zi_dispatch<dn::ZiOp::update>(K, arithmetic, tiles_ok) : zi_dispatch<dn::ZiOp::dt>(K, arithmetic, tiles_ok);
+}
+
 // the round-2 entry: without the per-lane flags (oriana_nzmask_tiles) the tiles family does not apply (dn::zi_update_ok)
 extern "C" int oriana_dropout_sweep_fused(float *D_hat, const double *U, const double *V, const double *pi_d64,
                                           const uint32_t *nzmask, double *colsum, const double *V_next, double *DV_next,

@@ -648,7 +648,10 @@ F32_SHAPES = [(1, 1, 1), (37, 53, 3), (300, 517, 20), (1000, 260, 50), (513, 102
               (33, 36, 65), (3000, 2080, 84), (700, 5000, 96), (257, 132, 100), (9000, 420, 80), (31, 4, 100),
               (513, 1022, 100), (300, 520, 40), (2000, 132, 48), (77, 64, 33), (640, 96, 52), (700, 520, 68),
               # Kp = 64 (round 6: the D update on k_zi_row<4, 0>, D^T U on k_zi_col<4, 0>), K = 49 .. 52 with the tail in the last tile
-              (2100, 520, 64), (300, 132, 57), (5000, 2080, 60), (1030, 1028, 49), (290, 260, 51)]
+              (2100, 520, 64), (300, 132, 57), (5000, 2080, 60), (1030, 1028, 49), (290, 260, 51),
+              # the factor loop of k_dropout_sweep (KS = ceil(K / 2) steps): its pipelined form with a body that runs zero times and
+              # three steps left over (K = 13), and three steps left over behind a running body (K = 30, 78)
+              (161, 131, 13), (161, 132, 30), (300, 292, 78)]
 
 
 @pytest.mark.gpu

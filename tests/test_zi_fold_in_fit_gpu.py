@@ -4,8 +4,10 @@ restatement of tests/zi_svi_reference.py.
 
 Shapes are those of tests/test_zi_foldin_gpu.py: 805 x 301, mp = 304 -- a partial last cell tile, inert genes, an all-zero cell, a
 gene expressed everywhere; its rate_case (Lambda of order 1, one pi_d at 0, one at 1, more than 20 % of the entries in the
-sigmoid's middle).  K = 20, 50, 100, 128: 1, 2, 4, 4 factor tiles of the new kernel.  The end-to-end stream is the planted
-293 x 131, K = 3 case of tests/test_zi_fold_in_fit_host.py."""
+sigmoid's middle).  K = 20, 50, 100, 128: 1, 2, 4, 4 factor tiles of the new kernel -- not 3, and at 805 cells (13 ranges of 64) a
+range neither leaves the matrix core nor float32: k_gene_rate<3>, the other forms of its factor loop, the flush at 256 cells and the
+spill at 4096 are run by tests/test_zi_heldout_forms_gpu.py.  The end-to-end stream is the planted 293 x 131, K = 3 case of
+tests/test_zi_fold_in_fit_host.py."""
 import numpy as np
 import pytest
 import torch
@@ -30,23 +32,24 @@ STATE_KEYS = zsvi.PRIORS + ('b1', 'b2', 'pi_d', 'V_hat', 'log_V_hat')
 
 # ---- 1. the rate entry against float64 ----------------------------------------------------------------------------------------
 
-def _ranges(n, K):
+def _ranges(n, K, mp=MP):
     from oriana_amd import _lib
-    return int(_lib.load().oriana_zi_gene_rate_ranges(n, MP, K))
+    return int(_lib.load().oriana_zi_gene_rate_ranges(n, mp, K))
 
 
-def _gene_rate(X, U, V, pi_d):
-    """oriana_zi_gene_rate into NaN-filled outputs with NaN-filled scratch: (G (MP, K), dsum [MP]) on the device."""
+def _gene_rate(X, U, V, pi_d, mp=MP):
+    """oriana_zi_gene_rate into NaN-filled outputs with NaN-filled scratch: (G (mp, K), dsum [mp]) on the device; mp: the gene
+    count the entry is given (the genes of V, then inert ones)."""
     from oriana_amd import _lib
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    _, mask, _ = _masks(X)
-    Vp, pip = _padded(V, pi_d)
+    _, mask, _ = _masks(X, mp=mp)
+    Vp, pip = _padded(V, pi_d, mp)
     Ud = _f64(U)
-    scratch = torch.full((int(_lib.load().oriana_zi_gene_rate_scratch_doubles(n, MP, K)),), float('nan'), dtype=F64, device=DEV)
-    G = torch.full((MP, K), float('nan'), dtype=F64, device=DEV)
-    dsum = torch.full((MP,), float('nan'), dtype=F64, device=DEV)
-    call('oriana_zi_gene_rate', ptr(G), ptr(dsum), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(scratch), n, MP, K, stream_ptr())
+    scratch = torch.full((int(_lib.load().oriana_zi_gene_rate_scratch_doubles(n, mp, K)),), float('nan'), dtype=F64, device=DEV)
+    G = torch.full((mp, K), float('nan'), dtype=F64, device=DEV)
+    dsum = torch.full((mp,), float('nan'), dtype=F64, device=DEV)
+    call('oriana_zi_gene_rate', ptr(G), ptr(dsum), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(scratch), n, mp, K, stream_ptr())
     torch.cuda.synchronize()
     return G, dsum
 

@@ -4,6 +4,8 @@
 Shapes are those of tests/test_elbo_gpu.py: 805 x 301 -- a partial last cell tile, m % 4 != 0 (so inert genes exist), four
 256-cell work-groups; an all-zero cell, an all-zero gene, a gene expressed everywhere.  K is one per kernel family of the
 rate entry: 20 (bf16 x 3 without tiles), 50 and 100 (tiles, with and without the tail factors), 128 (the float32 instruction).
+That is five of the sixteen instantiations the rule can pick for the rate entry, and every gene count here is a multiple of 4 (no
+fallback from the tiles family): tests/test_zi_heldout_forms_gpu.py runs the entry once per instantiation and route.
 The bound on one update is helpers.RTOL, the project's stated bound for variational parameters."""
 import numpy as np
 import pytest
@@ -102,10 +104,11 @@ def rate_case():
     return get
 
 
-def _padded(V, pi_d):
-    """V and pi_d with the inert genes (V row 0, pi_d 0) that bring the gene count to a multiple of 4."""
+def _padded(V, pi_d, mp=None):
+    """V and pi_d with the inert genes (V row 0, pi_d 0) that bring the gene count to mp (default: the next multiple of 4)."""
     m, K = V.shape
-    mp = (m + 3) // 4 * 4
+    mp = (m + 3) // 4 * 4 if mp is None else mp
+    assert mp >= m
     Vp, pip = torch.zeros(mp, K, dtype=torch.float64, device=DEV), torch.zeros(mp, dtype=torch.float64, device=DEV)
     Vp[:m].copy_(_f64(V))
     pip[:m].copy_(_f64(pi_d))
@@ -117,27 +120,28 @@ def _scratch(K, mp=MP):
     return torch.zeros(int(_lib.load().oriana_dropout_sweep_scratch_floats(mp, K)), dtype=torch.float32, device=DEV)
 
 
-def _rate(X, U, V, pi_d, arithmetic, active=None, DV=None, scratch=None):
-    """oriana_zi_foldin_rate on `scratch` (default: zeros of the stated size), adding to DV (default: zeros)."""
+def _rate(X, U, V, pi_d, arithmetic, active=None, DV=None, scratch=None, mp=None, with_tiles=True):
+    """oriana_zi_foldin_rate on `scratch` (default: zeros of the stated size), adding to DV (default: zeros).  mp: the gene count
+    the entry is given (default: the next multiple of 4); with_tiles = False: without the per-lane flags (nztiles = NULL)."""
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    Vp, pip = _padded(V, pi_d)
+    Vp, pip = _padded(V, pi_d, mp)
     mp = int(Vp.shape[0])
     _, mask, tiles = _masks(X, mp=mp)
     Ud = _f64(U)
     DV = torch.zeros(n, K, dtype=torch.float64, device=DEV) if DV is None else DV
     scratch = _scratch(K, mp) if scratch is None else scratch
-    call('oriana_zi_foldin_rate', ptr(DV), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(active), ptr(scratch),
-         arithmetic, n, mp, K, stream_ptr())
+    call('oriana_zi_foldin_rate', ptr(DV), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles if with_tiles else None), ptr(active),
+         ptr(scratch), arithmetic, n, mp, K, stream_ptr())
     torch.cuda.synchronize()
     return DV.cpu().numpy()
 
 
-def _storing(X, U, V, pi_d, arithmetic, scratch=None):
-    """DV_next of oriana_dropout_sweep_fused_tiles on a scratch D_hat, and that D_hat."""
+def _storing(X, U, V, pi_d, arithmetic, scratch=None, mp=None, with_tiles=True):
+    """DV_next of oriana_dropout_sweep_fused_tiles on a scratch D_hat, and that D_hat (mp, with_tiles: as _rate)."""
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    Vp, pip = _padded(V, pi_d)
+    Vp, pip = _padded(V, pi_d, mp)
     mp = int(Vp.shape[0])
     _, mask, tiles = _masks(X, mp=mp)
     Ud = _f64(U)
@@ -145,8 +149,8 @@ def _storing(X, U, V, pi_d, arithmetic, scratch=None):
     cs = torch.zeros(mp, dtype=torch.float64, device=DEV)
     DV = torch.zeros(n, K, dtype=torch.float64, device=DEV)
     scratch = _scratch(K, mp) if scratch is None else scratch
-    call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles), ptr(cs), ptr(Vp), ptr(DV),
-         ptr(scratch), arithmetic, n, mp, K, stream_ptr())
+    call('oriana_dropout_sweep_fused_tiles', ptr(D), ptr(Ud), ptr(Vp), ptr(pip), ptr(mask), ptr(tiles if with_tiles else None), ptr(cs),
+         ptr(Vp), ptr(DV), ptr(scratch), arithmetic, n, mp, K, stream_ptr())
     torch.cuda.synchronize()
     return DV.cpu().numpy(), D.cpu().numpy()
 
@@ -157,14 +161,16 @@ def test_rate_against_float64(rate_case, K, arithmetic):
     check_rate(*rate_case(K), arithmetic)
 
 
-def check_rate(X, U, V, pi_d, ref, arithmetic, scratch=None, DV=None):
+def check_rate(X, U, V, pi_d, ref, arithmetic, scratch=None, DV=None, mp=None, with_tiles=True, report=None):
     """The assertions of test_rate_against_float64 on `scratch` (default: zeros of the stated size), the rate added to the zeroed
-    DV if one is given.  Returns the rate."""
+    DV if one is given; mp, with_tiles: as _rate, for both entries.  Returns the rate; report: a dict that receives the errors."""
     K = U.shape[1]
-    got = _rate(X, U, V, pi_d, arithmetic, DV=DV, scratch=scratch)
+    got = _rate(X, U, V, pi_d, arithmetic, DV=DV, scratch=scratch, mp=mp, with_tiles=with_tiles)
     e = err_colrel(got, ref)
-    stored, D = _storing(X, U, V, pi_d, arithmetic, scratch=scratch)
+    stored, D = _storing(X, U, V, pi_d, arithmetic, scratch=scratch, mp=mp, with_tiles=with_tiles)
     e2 = err_colrel(got, stored)
+    if report is not None:
+        report.update(float64=e, storing=e2, stored_float64=err_colrel(stored, ref))
     print('K=%d arithmetic=%d: rate against float64 %.3e (bound %.1e); against the storing entry %.3e (bound 6e-7)'
           % (K, arithmetic, e, RTOL, e2))
     assert np.isfinite(got).all()
@@ -199,20 +205,24 @@ def test_rate_skips_inactive_cells(rate_case, K):
     check_rate_skips_inactive(X, U, V, pi_d, act, 1)
 
 
-def check_rate_skips_inactive(X, U, V, pi_d, act, arithmetic, scratch=None, DV=None):
+def check_rate_skips_inactive(X, U, V, pi_d, act, arithmetic, scratch=None, DV=None, mp=None, with_tiles=True, report=None):
     """The assertions of test_rate_skips_inactive_cells for the active flags `act` on `scratch` (default: zeros of the stated
-    size); DV: an (n, K) float64 tensor to use, filled with the sentinel here.  Returns the rows of the active cells."""
+    size); DV: an (n, K) float64 tensor to use, filled with the sentinel here; mp, with_tiles: as _rate.  Returns the rows of the
+    active cells; report: a dict that receives the error and its bound."""
     n, K = U.shape
-    full = _rate(X, U, V, pi_d, arithmetic, scratch=scratch)
+    full = _rate(X, U, V, pi_d, arithmetic, scratch=scratch, mp=mp, with_tiles=with_tiles)
     on = act != 0
     Un = U.copy()
     Un[~on] = np.nan
     DV = torch.empty(n, K, dtype=torch.float64, device=DEV) if DV is None else DV
     DV.fill_(SENTINEL)
-    got = _rate(X, Un, V, pi_d, arithmetic, active=torch.from_numpy(act).to(DEV), DV=DV, scratch=scratch)
+    got = _rate(X, Un, V, pi_d, arithmetic, active=torch.from_numpy(act).to(DEV), DV=DV, scratch=scratch, mp=mp,
+                with_tiles=with_tiles)
     assert np.array_equal(got[~on], np.full((int((~on).sum()), K), SENTINEL)), 'rows of inactive cells were written'
     e = err_colrel(got[on] - SENTINEL, full[on])
     print('K=%d: active rows against the all-active run %.3e (bound %.3e)' % (K, e, _twin_bound(n, 1)))
+    if report is not None:
+        report.update(active=e, active_bound=_twin_bound(n, 1))
     assert np.isfinite(got).all() and e <= _twin_bound(n, 1)
     return got[on] - SENTINEL
 

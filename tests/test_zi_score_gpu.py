@@ -4,8 +4,9 @@ the float64 reference of tests/zi_score_reference.py.
 
 Shapes are those of tests/test_zi_foldin_gpu.py: 805 x 301 -- a partial last cell tile, m % 4 != 0 (so inert genes exist), an
 all-zero cell, an all-zero gene, a gene expressed everywhere; K = 20, 50, 100, 128 are NT = 1, 2, 4, 4 of k_dropout_sweep with 20,
-50 (odd pairs: K / 2 = 25 steps), 100 and the full 128 factors.  The bound on the entry is zi_score_reference.dropout_bound, derived
-from the kernel's operation sequence; data, lgamma and kl keep score_reference's bounds."""
+50 (odd pairs: K / 2 = 25 steps), 100 and the full 128 factors -- NT = 3 and the factor loop's other forms (fewer than four steps, a
+body that runs zero times, three steps left over) are run by tests/test_zi_heldout_forms_gpu.py.  The bound on the entry is
+zi_score_reference.dropout_bound, derived from the kernel's operation sequence; data, lgamma and kl keep score_reference's bounds."""
 import numpy as np
 import pytest
 import torch
@@ -24,24 +25,25 @@ TERMS = ('score', 'data', 'lgamma', 'dropout', 'kl', 'a1', 'a2', 'froze_at', 'lo
 
 # ---- 1. the entry against float64 ---------------------------------------------------------------------------------------------
 
-def _splits(n, K):
-    """The number of gene ranges the entry cuts (n, MP) into on this device, from the documented size of its scratch."""
+def _splits(n, K, mp=MP):
+    """The number of gene ranges the entry cuts (n, mp) into on this device, from the documented size of its scratch."""
     from oriana_amd import _lib
-    sd = int(_lib.load().oriana_zi_cell_bound_scratch_doubles(n, MP, K))
-    rest = sd - 32 * ((MP + 63) // 64)
+    sd = int(_lib.load().oriana_zi_cell_bound_scratch_doubles(n, mp, K))
+    rest = sd - 32 * ((mp + 63) // 64)
     assert rest > 0 and rest % n == 0
     return sd, rest // n
 
 
-def _entry(X, U, V, pi_d, fill=float('nan')):
+def _entry(X, U, V, pi_d, fill=float('nan'), mp=MP, m_real=M_COLS):
+    """oriana_zi_cell_bound over scratch and out filled with `fill`; mp: the gene count the entry is given, m_real of them real."""
     from oriana_amd._lib import call, ptr, stream_ptr
     n, K = U.shape
-    _, mask, _ = _masks(X)
-    Vp, pip = _padded(V, pi_d)
-    sd, _ = _splits(n, K)
+    _, mask, _ = _masks(X, mp=mp)
+    Vp, pip = _padded(V, pi_d, mp)
+    sd, _ = _splits(n, K, mp)
     scratch = torch.full((sd,), fill, dtype=torch.float64, device=DEV)
     out = torch.full((n,), fill, dtype=torch.float64, device=DEV)
-    call('oriana_zi_cell_bound', ptr(out), ptr(_f64(U)), ptr(Vp), ptr(pip), ptr(mask), ptr(scratch), n, MP, M_COLS, K, stream_ptr())
+    call('oriana_zi_cell_bound', ptr(out), ptr(_f64(U)), ptr(Vp), ptr(pip), ptr(mask), ptr(scratch), n, mp, m_real, K, stream_ptr())
     torch.cuda.synchronize()
     return out.cpu().numpy()
 
