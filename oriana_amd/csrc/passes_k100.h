@@ -52,6 +52,13 @@ template <int SH> __device__ __forceinline__ uint32_t lshl_add(uint32_t a, uint3
     asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(SH), "v"(b));
     return d;
 }
+// a * B for a < 2^24 and a small constant B in one full-rate instruction (left to itself the compiler folds `idx - jr * 24` into the
+// quarter-rate v_mad_u64_u32)
+template <int B> __device__ __forceinline__ uint32_t mul_u24(uint32_t a) {
+    uint32_t d;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(d) : "n"(B), "v"(a));
+    return d;
+}
 // 32-bit LDS addresses: reads whose address is formed by lshl_add go through them, so that no generic-pointer
 // arithmetic (an addition of the image's base per read) is left
 typedef const f4 __attribute__((address_space(3))) *lds_f4_ptr;
@@ -69,15 +76,18 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
 template <int U> __device__ __forceinline__ uint32_t pb_u32(uint32_t v) { return (U >> 1) ? dpp_u32<0xF5>(v) : dpp_u32<0xA0>(v); }
 template <int U> __device__ __forceinline__ float pb_f32(float v) { return (U >> 1) ? dpp_f32<0xF5>(v) : dpp_f32<0xA0>(v); }
 
-// staging of 256 factor rows (global loads before the barrier, LDS stores after it)
+// staging of 256 factor rows (global loads before the barrier, LDS stores after it), every element's address formed on its
+// own: float4 idx = tid + u THREADS of the tile's 256 x 24, factor row idx / 24, chunk idx % 24, `j < jmax` and zero fill per
+// element.  The column kernel k_col_pass2 stages like this (the class form below was built and measured there too: 216 -> 61..68
+// vector instructions per tile and wave and no faster, profiles/restage_ab.txt), and so does the ragged tile of the row kernel.
 template <int THREADS, int TAIL>
-struct Stage {
+struct StageEach {
     static constexpr int KP4 = 24 + TAIL;
     static constexpr int NST = TILE * 24 / THREADS;         // 12 (512 threads) or 6 (1024)
     f4 v[NST];
     f4 t;
     __device__ __forceinline__ void load(const float *__restrict__ F, int64_t j0, int64_t jmax, int tid) {
-        asm volatile("" : "+v"(tid));
+        asm volatile("" : "+v"(tid));                        // (24 addresses are not worth registers)
         #pragma unroll
         for (int u = 0; u < NST; ++u) {
             const int idx = tid + u * THREADS;
@@ -101,6 +111,94 @@ struct Stage {
         }
         if (TAIL && tid < TILE) {
             f4 *tl = img + TILE * ROW4 + tid * TREP;
+            #pragma unroll
+            for (int r = 0; r < TREP; ++r) tl[r] = t;
+        }
+    }
+};
+
+// The same staging with the addresses formed ONCE (the row kernel k_row_pass_k100).
+// Element u of a thread is float4 idx = tid + u THREADS of the tile's 256 x 24 float4: factor row idx / 24, chunk idx % 24.
+// 3 THREADS is a multiple of 24 (512 threads: 64 rows, 1024 threads: 128 rows), so element u + 3 is the SAME chunk JSTEP
+// rows further on: a thread has three (row, chunk) CLASSES b = u % 3, and everything else in an address is a constant
+// ("restaging"; profiles/restage_counts.txt):
+//   * global side: the byte offset g[b] of the class inside the tile (32 bits) under the wave-uniform base of the tile
+//     advanced by JSTEP factor rows per element -- scalar additions, no per-element multiply, division or compare;
+//   * LDS side: the address l[b] of the class in image row jr, every element at a constant distance of JSTEP image rows
+//     (an immediate offset of the ds_write, with one more base where 65535 is exceeded);
+//   * of the chunks c, c + 8, c + 16 (mod 24) of the three classes exactly one is >= 16: which class is stored twice
+//     (chunk groups 4, 5 again at float4 24..31) is fixed per thread -- dup[b], tested once per class, not per element.
+// A FULL tile (j0 + 256 <= jmax: wave-uniform) loads unpredicated; the ragged last tile of a side takes the per-element
+// path of StageEach with the `j < jmax` test and zero fill.  The stores are the same for both.  classes() costs three
+// divisions by 24, once per kernel.  Only Stage<512, TAIL> is instantiated; THREADS stays a parameter (1024: 128 rows per class
+// step) for the follow-up that puts k_col_pass2 on it once its registers allow the classes to be held.
+typedef f4 __attribute__((address_space(3))) *lds_f4_wptr;
+template <int THREADS, int TAIL>
+struct Stage : StageEach<THREADS, TAIL> {
+    using Each = StageEach<THREADS, TAIL>;
+    using Each::v; using Each::t;
+    static constexpr int KP4 = Each::KP4, NST = Each::NST;
+    static constexpr int JSTEP = 3 * THREADS / 24;          // factor rows between elements u and u + 3: 64 or 128
+    static_assert(NST % 3 == 0 && (3 * THREADS) % 24 == 0 && JSTEP * (NST / 3) == TILE, "three classes per thread");
+    struct Classes { uint32_t g[3], l[3]; bool dup[3]; };
+    static __device__ __forceinline__ Classes classes(const f4 *img, int tid) {
+        Classes c;
+        #pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const uint32_t idx = (uint32_t)tid + (uint32_t)(b * THREADS);
+            // idx / 24 for idx < 8192 in full-rate 24-bit multiplies (2731 / 65536 = 1 / 24 + 1 / 196608: the excess stays
+            // below the 1 / 24 that would carry into the next quotient); v_mul_hi and the 64-bit mad run at a quarter
+            static_assert(3 * THREADS + 23 < 8192, "div24");
+            const uint32_t jr = mul_u24<2731>(idx) >> 16, c4 = idx - mul_u24<24>(jr);
+            c.g[b] = (mul_u24<KP4>(jr) + c4) * 16u;
+            c.l[b] = lds_addr(img) + jr * (uint32_t)(ROW4 * 16) + c4 * 16u;
+            c.dup[b] = c4 >= 16u;
+        }
+        return c;
+    }
+    __device__ __forceinline__ void load(const Classes &c, const float *__restrict__ F, int64_t j0, int64_t jmax, int tid) {
+        // (wave-uniform, and kept scalar: of the 64-bit compares only == / != have a scalar form -- `j0 + 256 <= jmax` and the
+        //  unsigned `>= 256` the compiler makes of the shift are vector compares.  A caller's tile has jmax - j0 > 0; should one
+        //  ever not, the sign mask sends it down the per-element path, which tests every row and reads nothing)
+        const int64_t left = jmax - j0;
+        uint64_t neg = (uint64_t)(left >> 63);               // (opaque: the compiler would make a 64-bit vector compare of it)
+        asm volatile("" : "+s"(neg));
+        uint64_t blocks = ((uint64_t)left >> 8) & ~neg;
+        asm volatile("" : "+s"(blocks));
+        if (blocks != 0) {                                   // every factor row of the tile exists
+            const char *base = reinterpret_cast<const char *>(F) + j0 * (KP4 * 16);
+            // (opaque HERE: hoisted out of the tile loop the offsets would be widened to 64 bits there -- six registers --
+            //  and every load would add its base to one of them; like this a load is scalar base + 32-bit offset)
+            uint32_t g0 = c.g[0], g1 = c.g[1], g2 = c.g[2];
+            asm volatile("" : "+v"(g0), "+v"(g1), "+v"(g2));
+            #pragma unroll
+            for (int u = 0; u < NST; ++u)
+                v[u] = *reinterpret_cast<const f4 *>(base + (int64_t)(u / 3) * (JSTEP * KP4 * 16) + (u % 3 == 0 ? g0 : u % 3 == 1 ? g1 : g2));
+            // (256 = four whole waves: the test is a scalar one; the other waves never read t)
+            if (TAIL && __builtin_amdgcn_readfirstlane(tid) < TILE) {
+                asm volatile("" : "+v"(tid));
+                t = *reinterpret_cast<const f4 *>(base + 24 * 16 + __umul24((uint32_t)tid, (uint32_t)(KP4 * 16)));
+            }
+            return;
+        }
+        Each::load(F, j0, jmax, tid);                        // the ragged tile
+    }
+    __device__ __forceinline__ void store(const Classes &c, f4 *img, int tid) const {
+        // (opaque HERE: the further bases past the 65535 of the immediate offset are formed per tile, not held per kernel)
+        uint32_t l[3] = {c.l[0], c.l[1], c.l[2]};
+        asm volatile("" : "+v"(l[0]), "+v"(l[1]), "+v"(l[2]));
+        #pragma unroll
+        for (int u = 0; u < NST; ++u)                        // (in the order the loads return)
+            ((lds_f4_wptr)(uintptr_t)l[u % 3])[(u / 3) * (JSTEP * ROW4)] = v[u];
+        #pragma unroll
+        for (int b = 0; b < 3; ++b)
+            if (c.dup[b]) {                                  // chunk groups 4, 5 again, 8 float4 further on
+                #pragma unroll
+                for (int a = 0; a < NST / 3; ++a) ((lds_f4_wptr)(uintptr_t)l[b])[a * (JSTEP * ROW4) + 8] = v[3 * a + b];
+            }
+        if (TAIL && __builtin_amdgcn_readfirstlane(tid) < TILE) {
+            asm volatile("" : "+v"(tid));                    // (one address per tile, not a register per kernel)
+            const lds_f4_wptr tl = (lds_f4_wptr)(uintptr_t)(lds_addr(img) + (uint32_t)(TILE * ROW4 * 16) + (uint32_t)tid * (uint32_t)(TREP * 16));
             #pragma unroll
             for (int r = 0; r < TREP; ++r) tl[r] = t;
         }
@@ -175,6 +273,8 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
         rowfilled = !(fm == 1.0f);
     }
 
+    // the three staging classes of this thread (Stage), formed once
+    const typename Stage<512, TAIL>::Classes scl = Stage<512, TAIL>::classes(lds, tid);
     const int64_t cb0 = item.cb0, cb1 = item.cb1;
     for (int64_t cb = cb0; cb < cb1; ++cb) {
         const int64_t t = rb * cm.ncb + cb;
@@ -200,9 +300,9 @@ __global__ __launch_bounds__(512) void k_row_pass_k100(oriana_counts cm, const f
         }
         {
         Stage<512, TAIL> stg;
-        stg.load(FV, cb * TILE, cm.m, tid);
+        stg.load(scl, FV, cb * TILE, cm.m, tid);
         __syncthreads();
-        stg.store(lds, tid);
+        stg.store(scl, lds, tid);
         __syncthreads();
         }
         // One step.  Around its FMAs a step keeps only what every slot needs ("step diet"):
@@ -534,7 +634,7 @@ __global__ __launch_bounds__(1024) void k_col_pass2(oriana_counts cm, const floa
     for (int64_t rb = rb0; rb < rb1; ++rb) {
         if (!DUAL) open_stream(stB, rb * cm.ncb + (hasB ? cbB : cbA), hasB);      // in flight during the first tile's loop
         if (Im::DUP) {
-            k100::Stage<1024, TAIL> stg;
+            k100::StageEach<1024, TAIL> stg;
             stg.load(Gm, rb * TILE, cm.n, tid);
             __syncthreads();
             stg.store(lds, tid);
